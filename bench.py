@@ -8,7 +8,11 @@ network/grid sizes (1 GiB colour table), fp32, synthetic inputs already resident
 N > 1: every rank renders its own 1024-ray shard (rays are independent given replicated parameters) and the only
 exchange is one fused 9-float RCCL all-reduce (pose gradient, loss, ray count) per step  ->  "scaling": "weak".
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed step
+computed (DIR/<name>.npy, float32; inputs are seeded, so two builds can be compared output for output).  `--full` adds everything
+else the line can carry: per-kernel and roofline figures (an eager replay of the timed batches), the CPU baseline and the context
+legs (precision modes, small shapes, drop-in, reference-shaped GPU path, mapping iteration), each still skippable with its --no-* flag.
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment) or directly as `python bench.py --gpus N`, which re-executes itself under torch.distributed.run on
 127.0.0.1.  `--global-rays G` fixes the TOTAL batch (G/N rays per GPU) -> "scaling": "strong"; default: 1024 rays per GPU.
@@ -85,7 +89,7 @@ def parse():
     ap.add_argument("--global-rays", type=int, default=0,
                     help="total rays per step over all GPUs (strong scaling: each rank renders global/N); e.g. 4096 = BASELINE "
                          "configs[2], 1024 = configs[1] spread over N GPUs")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the SLAMNetwork.forward + autograd leg (N = 1 only)")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip the SLAMNetwork.forward + autograd leg (N = 1 only)")
     ap.add_argument("--samples", type=int, default=128, help="composite samples per ray (N_samples = S-34)")
     ap.add_argument("--engine", default="auto", choices=["auto", "fused", "composed"])
     ap.add_argument("--param-grads", action="store_true",
@@ -101,10 +105,17 @@ def parse():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16_colour"],
                     help="MLP GEMM operands: fp32 = the reference's precision (default, the BASELINE metric); bf16 / "
                          "bf16_colour = the optional reduced-precision modes of BASELINE configs[2]/[4] (NOT the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-precision-modes", action="store_true", help="skip the bf16 / bf16_colour context rows (N = 1 only)")
-    ap.add_argument("--no-mapping", action="store_true", help="skip the (untimed-for-value) mapping-iteration leg")
-    ap.add_argument("--no-small-shapes", action="store_true", help="skip the strong-scaling-tail rows (128 / 256 / 512 rays; N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel / roofline figures, the CPU baseline and the context legs below (off: a plain "
+                         "run times the steps and prints the line, those fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; e.g. DIR = "
+                         "bench_outputs, which git ignores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-precision-modes", action="store_true", help="with --full: skip the bf16 / bf16_colour context rows (N = 1 only)")
+    ap.add_argument("--no-mapping", action="store_true", help="with --full: skip the (untimed-for-value) mapping-iteration leg")
+    ap.add_argument("--no-small-shapes", action="store_true",
+                    help="with --full: skip the strong-scaling-tail rows (128 / 256 / 512 rays; N = 1 only)")
     ap.add_argument("--cpu-rays", type=int, default=1024)
     ap.add_argument("--cpu-all-cores-rays", type=int, default=0,
                     help="rays of a LIVE second CPU figure taken with torch.set_num_threads(os.cpu_count()) (BASELINE.md section 3); default 0: "
@@ -176,6 +187,29 @@ def synth_batch(gen, n_rays, device):
     idx = torch.randint(H * W, (1, n_rays), generator=gen, device=device)
     uv = torch.stack([(idx % W).float(), (idx // W).float()], -1)
     return uv, torch.rand(n_rays, 3, generator=gen, device=device)
+
+
+def last_step_outputs(stepper, loss):
+    """What the timed path hands its caller after a step: the step's loss, the camera after its Adam update, the pose gradient that
+    update consumed, the frame's candidate camera (arg-min loss) and that loss, and -- KernelTracker, one ray chunk -- the per-ray
+    L1 sums the loss was formed from.  Flat float32 host arrays."""
+    with torch.no_grad():
+        if hasattr(stepper, "red"):          # KernelTracker: red = [g_cam(7), loss, n_rays] (weighted message with N > 1 / chunks)
+            grad = stepper.red[:7] / stepper.red[8] if stepper.message else stepper.red[:7]
+        else:
+            grad = stepper.cam.grad
+        out = {"loss": loss, "camera": stepper.cam, "pose_grad": grad, "candidate_camera": stepper.candidate,
+               "min_loss": stepper.min_loss}
+        if getattr(stepper, "folded", False):
+            out["ray_l1"] = stepper.ray_loss
+        return {k: v.detach().float().reshape(-1).cpu().numpy() for k, v in out.items() if v is not None}
+
+
+def dump_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def self_launch(args):
@@ -298,16 +332,20 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     gc_off.__exit__(None, None, None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(stepper, last))
     last = float(last)
-    # Per-kernel durations: graph nodes cannot be bracketed by events, so the same K batches are run once more,
-    # eagerly, right after the timed region with an event pair around every launch of ours (on the launch stream).
-    eager = stepper if not use_graph else Stepper(model, K, args.rays, stepper.cam.detach(), lr=0.005,
-                                                  use_graph=False, world=1)
-    be.PROFILE = []
-    for i in range(args.warmup, total):
-        eager.step(*batches[i])
-    torch.cuda.synchronize()
-    prof, be.PROFILE = be.PROFILE, None
+    prof, eager = [], None
+    if args.full:
+        # Per-kernel durations: graph nodes cannot be bracketed by events, so the same K batches are run once more,
+        # eagerly, right after the timed region with an event pair around every launch of ours (on the launch stream).
+        eager = stepper if not use_graph else Stepper(model, K, args.rays, stepper.cam.detach(), lr=0.005,
+                                                      use_graph=False, world=1)
+        be.PROFILE = []
+        for i in range(args.warmup, total):
+            eager.step(*batches[i])
+        torch.cuda.synchronize()
+        prof, be.PROFILE = be.PROFILE, None
     t = torch.tensor([dt], device=device, dtype=torch.float64)
     rccl_ranks = 0
     per_rank_ms, exchange_us = None, None
@@ -317,7 +355,7 @@ def main():
         every = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(every, t)
         per_rank_ms = [round(float(x.item()) / args.steps * 1e3, 4) for x in every]
-        if hasattr(stepper, "_exchange"):
+        if args.full and hasattr(stepper, "_exchange"):
             fence()
             t_ex = time.perf_counter()
             for _ in range(50):
@@ -403,18 +441,18 @@ def main():
                                       "note": "of the fp32 matrix line (157.3 TFLOP/s), per GPU"}
         # (the CPU figure is taken on rank 0 of the ONE-GPU run only: with N > 1 the other ranks would sit in the communicator's tear-down
         #  for its 13 s)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args, model, conf)
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(args, model, conf)
         mapping, dropin, ref_gpu, prec_modes, small = None, None, None, None, None
         gather = colour_gather_roofline(agg, args) if agg else None
-        if world == 1 and not args.no_precision_modes and args.engine != "composed" and args.precision == "fp32":
+        legs = args.full and world == 1 and args.engine != "composed" and args.precision == "fp32"     # context legs: --full, N = 1
+        if legs and not args.no_precision_modes:
             prec_modes = precision_modes_leg(args, device, K)
-        if (world == 1 and not args.no_small_shapes and args.engine != "composed" and args.precision == "fp32" and args.rays == 1024
-                and args.samples == 128):
+        if legs and not args.no_small_shapes and args.rays == 1024 and args.samples == 128:
             small = small_shapes_leg(args, device, K, ms)
-        if world == 1 and not args.no_dropin and args.engine != "composed" and args.precision == "fp32":
+        if legs and not args.no_dropin:
             dropin = dropin_leg(args, device, K, batches)
             ref_gpu = reference_shaped_gpu_leg(args, device, K, batches, rays_total / dt)
-        if world == 1 and not args.no_mapping and args.engine != "composed" and args.precision == "fp32":
+        if legs and not args.no_mapping:
             del stepper, eager
             mapping = mapping_leg(device)
         line = {
@@ -434,10 +472,10 @@ def main():
                                    + (", captured in the hipGraph" if collective_in_graph else ", between graph replay and Adam launch"),
                        "per_rank_ms_per_step": per_rank_ms,
                        "exchange_us_per_step": exchange_us if world > 1 else None,
-                       "exchange_measured": None if world == 1 else "all-reduce of the 9-float message + nsa_adam_step_scaled, 50 back-to-back "
+                       "exchange_measured": None if world == 1 or not args.full else "all-reduce of the 9-float message + nsa_adam_step_scaled, 50 back-to-back "
                                             "calls after the timed region (host-issued: includes launch latency, which a step hides "
                                             "behind the graph replay of the next iteration only when collective_in_graph)",
-                       "oversubscribed": oversub or None},
+                       "oversubscribed": oversub or None, "full": args.full},
             "final_loss": round(last, 6),
             "roofline": roof, "colour_gather": gather, "cpu_baseline": cpu, "reference_shaped_gpu": ref_gpu, "dropin": dropin,
             "mapping_iteration": mapping, "precision_modes": prec_modes, "small_shapes": small,

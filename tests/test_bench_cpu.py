@@ -58,3 +58,39 @@ def test_mapping_leg_quotes_committed_profiles_consistently():
     metas = sorted(p for p in os.listdir(os.path.join(ROOT, "profiles")) if p.endswith("_mapping_pmc_meta.json"))
     newest = json.load(open(os.path.join(ROOT, "profiles", metas[-1])))
     assert newest == sig, "the newest committed atomic-request profile was taken with another shape / tiling / key width"
+
+
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, one float32 .npy each; a plain run is the
+    headline only (--full off by default)."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        assert bench.parse().full is False and bench.parse().dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path), "--steps", "5"]
+        args = bench.parse()
+        assert args.full is True and args.dump_outputs == str(tmp_path) and args.steps == 5
+    finally:
+        sys.argv = old
+    red = torch.arange(9, dtype=torch.float32) + 1
+    tracker = types.SimpleNamespace(red=red, message=False, cam=torch.full((7,), 0.5), best=None, candidate=torch.ones(7),
+                                    min_loss=torch.tensor(0.25), folded=True, ray_loss=torch.rand(16))
+    got = bench.last_step_outputs(tracker, red[7])
+    assert set(got) == {"loss", "camera", "pose_grad", "candidate_camera", "min_loss", "ray_l1"}
+    assert np.array_equal(got["pose_grad"], np.arange(1, 8, dtype=np.float32)) and got["loss"].tolist() == [8.0]
+    tracker.message = True                       # weighted message (N > 1 / chunks): the gradient is red[:7] / red[8]
+    assert np.allclose(bench.last_step_outputs(tracker, red[7] / red[8])["pose_grad"], np.arange(1, 8) / 9.0)
+    cam = torch.zeros(7, dtype=torch.float64, requires_grad=True)
+    cam.grad = torch.full((7,), 2.0, dtype=torch.float64)
+    autograd_stepper = types.SimpleNamespace(cam=cam, candidate=cam.detach(), min_loss=torch.tensor(1.0))
+    got = bench.last_step_outputs(autograd_stepper, torch.tensor(1.0))
+    assert set(got) == {"loss", "camera", "pose_grad", "candidate_camera", "min_loss"} and got["pose_grad"].tolist() == [2.0] * 7
+    bench.dump_outputs(str(tmp_path / "d"), got)
+    for name, want in got.items():
+        back = np.load(tmp_path / "d" / (name + ".npy"))
+        assert back.dtype == np.float32 and np.array_equal(back, want)

@@ -215,66 +215,19 @@ def test_mapping_host_guards_without_a_gpu():
         Adam([p]).step()
 
 
-def _parse_conf(text):
-    """the subset of HOCON the shipped run configs use: `name { ... }`, `key = value`, `key = [` ... `]` over several lines"""
-    root, stack, lst = {}, [], None
-    cur = root
-    for raw in text.splitlines():
-        line = raw.strip()
-        if not line:
-            continue
-        if lst is not None:
-            if line.startswith("]"):
-                lst = None
-            else:
-                lst.append(_scalar(line))
-            continue
-        if line.endswith("{"):
-            node = {}
-            cur[line[:-1].strip()] = node
-            stack.append(cur)
-            cur = node
-        elif line == "}":
-            cur = stack.pop()
-        elif line.endswith("{}"):
-            cur[line[:-2].split("=")[0].strip()] = {}
-        else:
-            k, v = [t.strip() for t in line.split("=", 1)]
-            if v == "[":
-                lst = cur[k] = []
-            elif v == "[]":
-                cur[k] = []
-            else:
-                cur[k] = _scalar(v)
-    return root
-
-
-def _scalar(v):
-    v = v.strip().strip('"')
-    if v in ("true", "false"):
-        return v == "true"
-    try:
-        return int(v)
-    except ValueError:
-        try:
-            return float(v)
-        except ValueError:
-            return v
-
-
 def test_conf_presets_equal_the_shipped_run_configs():
-    import os
     """utils/conf.py::model_conf / run_conf against EVERY run config the reference ships (code/confs/**/*.conf): the model subtree key by
-    key, image size, loss block, loop counts.  Needs the reference checkout (build container only)."""
-    import glob
-    ref = "/root/reference/code/confs"
-    files = sorted(glob.glob(os.path.join(ref, "**", "*.conf"), recursive=True))
-    if not files:
-        pytest.skip("reference checkout not present")
+    key, image size, loss block, loop counts.  The configs' values are the fixture tests/golden/reference_confs.json
+    (tests/golden/make_conf_fixture.py)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_confs.json")) as f:
+        confs = json.load(f)
     from nicer_slam_amd.utils.conf import model_conf, run_conf
+    files = sorted(confs)
     assert len(files) == 23
     for path in files:
-        conf = _parse_conf(open(path).read())
+        conf = confs[path]
         # (the two demo files: runconf_demo_1 is an Azure-family conf -- 720 x 1280, coarse radius 1.0 --, runconf_demo_2 a Replica-family one)
         family = "7scenes" if "7scenes" in path else "azure" if ("azure" in path or path.endswith("demo_1.conf")) else "replica"
         mine = dict(model_conf(family))

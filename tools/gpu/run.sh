@@ -12,7 +12,7 @@ for step in "$@"; do
     testsall)     timeout 2400 python -m pytest tests -m gpu -q > $O/tests_all.log 2>&1; echo "rc=$?" >> $O/tests_all.log; grep -E "^(FAILED|ERROR)|passed|failed" $O/tests_all.log | tail -30 ;;
     ab:*)         # ab:<ENV>: bench.py's tracker line with ENV=0 / ENV=1 alternating, three rounds (per-kernel event times in the lines)
                   V=${step#ab:}; for r in 1 2 3; do for f in 0 1; do
-                    env $V=$f timeout 600 python bench.py --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes \
+                    env $V=$f timeout 600 python bench.py --full --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes \
                         > $O/ab_${V}_${f}_$r.json 2>/dev/null
                     python - $O/ab_${V}_${f}_$r.json $V=$f <<'PY'
 import json, sys
@@ -23,7 +23,7 @@ PY
                   done; done ;;
     pmcab:*)      # pmcab:<ENV>: SQ counters of the quad kernels with ENV=0 / ENV=1 (one counter pass each; eager launches)
                   V=${step#pmcab:}; R=$(pwd)
-                  BE="python $R/bench.py --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes --steps 20 --warmup 5 --prewarm-s 0 --prewarm-steps 0 --no-graph"
+                  BE="python $R/bench.py --full --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes --steps 20 --warmup 5 --prewarm-s 0 --prewarm-steps 0 --no-graph"
                   for f in 0 1; do
                     (cd /tmp && env $V=$f timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU \
                         --output-format csv -d /tmp/pmcab_$f -- $BE > /tmp/pmcab_$f.log 2>&1)
@@ -43,7 +43,7 @@ PY
                   done; done ;;
     warmab)       # the driver's command (--steps 20 --warmup 5) under different untimed pre-warm recipes: does the short run reach the long run's clocks?
                   for rnd in 1 2; do for v in "1.0 100" "0 100" "1.0 400" "1.0 1000" "0 1000" "0.3 2000" "3.0 100"; do set -- $v
-                    timeout 300 python bench.py --steps 20 --warmup 5 --prewarm-s $1 --prewarm-steps $2 --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes \
+                    timeout 300 python bench.py --full --steps 20 --warmup 5 --prewarm-s $1 --prewarm-steps $2 --no-cpu-baseline --no-mapping --no-dropin --no-precision-modes --no-small-shapes \
                         2>/dev/null > $O/warm_${1}_${2}_$rnd.json
                     python -c "import json,sys; d=json.loads(open(sys.argv[1]).readline()); print('prewarm_s', sys.argv[2], 'prewarm_steps', sys.argv[3], 'ms', d['ms_per_step'], 'sampler', d['roofline']['all_kernels_us']['k_sampler_sdf'])" $O/warm_${1}_${2}_$rnd.json $1 $2
                   done; done
@@ -75,7 +75,7 @@ PY
                   done; done ;;
     tests:*)      timeout 1500 python -m pytest ${step#tests:} -m gpu -x -q > $O/tests_sel.log 2>&1; echo "rc=$?" >> $O/tests_sel.log; tail -15 $O/tests_sel.log ;;
     smoke)        timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 ;;
-    bench)        timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?"; cut -c1-600 $O/bench.json ;;
+    bench)        timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?"; cut -c1-600 $O/bench.json ;;
     bench:*)      timeout 900 python bench.py ${step#bench:} > $O/bench_opt.json 2> $O/bench_opt.err; echo "rc=$?"; cut -c1-600 $O/bench_opt.json ;;
     seq7)         timeout 1200 python tools/synthetic_sequence.py --conf 7scenes > $O/sequence_ate_7scenes.json 2> $O/seq7.err; echo "rc=$?"; tail -3 $O/seq7.err ;;
     seqA)         timeout 1500 python tools/synthetic_sequence.py --conf azure --n-samples 158 --oracle-frames 0 > $O/sequence_ate_azure.json 2> $O/seqA.err; echo "rc=$?"; tail -3 $O/seqA.err ;;
