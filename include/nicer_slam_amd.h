@@ -81,8 +81,9 @@ typedef struct nsa_grid {
     uint32_t H;                  /* base resolution                                                */
     float divide_factor;         /* x is divided by this before the [-1,1] -> [0,1] map            */
     uint32_t n_hidden;           /* hidden layers of the attached MLP (coarse 1, fine 3)           */
-    uint32_t precision;          /* GEMM operands of the attached MLP: 0 = fp32-faithful (3-way bf16 split, the
-                                  * reference's precision; default), 1 = plain bf16 operands with fp32 accumulation
+    uint32_t precision;          /* GEMM operands of the attached MLP: 0 = fp32-faithful (the reference's precision; default:
+                                  * two fp16 pieces per operand after a per-point power-of-two scale, or three exact bf16
+                                  * pieces in a -DNSA_FORM=3 build, nsa_operand_form), 1 = plain bf16 operands with fp32 accumulation
                                   * (optional "bf16 MLP" mode of BASELINE configs 2/4; encoders, activations,
                                   * compositing and all reductions stay fp32)                       */
     uint32_t tile;               /* tiling of the SDF-network kernels and the matching packed-parameter layout: 16 = quad
@@ -194,9 +195,11 @@ int nsa_colour_coarse_backward(const nsa_points_t *pts, const nsa_grid_t *grid, 
                                const float *g_sdf, nsa_stream_t stream);
 
 /* Mapping-mode backward (parameter gradients): the same kernels as nsa_sdfnet_backward / nsa_colour_backward with two
- * more outputs.  replaces, for a mapping iteration, what torch.autograd does through ImplicitNetworkGrid /
- * RenderingNetwork / _hash_encode.backward / _hash_encode_second_backward (code/model/base_networks.py:195-221,
- * 333-395; code/hashencoder/hashgrid.py:64-141) for the trainable parameters of volsdf_train.py:150-173:
+ * more outputs; the data path is bit-identical to theirs except for the coarse SDF network in the 32-point tiling, whose MAP kernel
+ * keeps the grid Jacobian in LDS where the plain one recomputes it from the corner gathers (same sums, another rounding order).
+ * Replaces, for a mapping iteration, what torch.autograd does through ImplicitNetworkGrid / RenderingNetwork /
+ * _hash_encode.backward / _hash_encode_second_backward (code/model/base_networks.py:195-221, 333-395;
+ * code/hashencoder/hashgrid.py:64-141) for the trainable parameters of volsdf_train.py:150-173:
  *   g_table  gradient of the grid table (same shape as grid->table), ATOMICALLY ACCUMULATED (caller zeroes it):
  *            value path + (SDF grids) the table's share of the double backward through grad sdf; may be NULL.
  *   emit     [nsa_*_emit_rows()][emit_ld] per-point vectors, column = point index (emit_ld >= ceil(P/32)*32 -- the quad tiling writes 16-point tiles, so its padding starts at ceil(P/16)*16 --, columns

@@ -1,7 +1,7 @@
 // mlp_common.hpp -- register-resident batched MLP on the gfx950 matrix cores for the fused render-core kernels.
 //
-// Tiling (wave64, v_mfma_f32_32x32x16_bf16 with fp32 accumulation; fp32 operands enter as three exact bf16 pieces, see
-// the GEMM primitive below):
+// Tiling (wave64, 32x32 matrix instructions with fp32 accumulation; fp32 operands enter as two fp16 pieces after a per-point
+// power-of-two scale -- NSA_FORM 2, the default, point_scale_of below -- or as three exact bf16 pieces in a -DNSA_FORM=3 build):
 //   * a wave owns a tile of 32 points; lane l works for point (l & 31), and the two half-waves h = l >> 5 split every
 //     per-point job in two (half of the grid levels, half of the positional-encoding pairs, half of every activation
 //     vector);
@@ -32,7 +32,8 @@ constexpr int COL_IN_STEPS = 65;   // 129 inputs -> 65 slots per half-wave (one 
 // ---------------------------------------------------------------------------------------------------------------
 // GEMM primitive.  acc[mt] (32 output features x 32 points, fp32) += sum_slots A(mt, slot) * b[slot].
 //
-// fp32-faithful products on the bf16 matrix cores.  Every fp32 operand is split exactly into
+// fp32-faithful products on the 16-bit matrix cores.  What follows is the three-piece form (NSA_FORM 3, rounds 1-6a, a build option
+// since); the default two-piece fp16 form and its per-point scaling are described at NSA_FORM below.  Every fp32 operand is split exactly into
 // three bf16 pieces (8 + 8 + 8 significand bits: x = hi + mid + lo), and the six cross products whose weight is
 // >= 2^-16 are accumulated in fp32 by v_mfma_f32_32x32x16_bf16:
 //     a*b ~= a_lo b_hi + a_hi b_lo + a_mid b_mid + a_mid b_hi + a_hi b_mid + a_hi b_hi          (error <= ~2^-23 |a b|)
@@ -184,20 +185,24 @@ __device__ __forceinline__ void split8_h2(const float (&t)[8], f16x8_t& h0, f16x
 // has combined the lanes' maxima): the operands are multiplied by s = 2^(13 - E), E = exponent of m clamped to +-80, so that the
 // largest lies in [2^13, 2^14); the accumulators (which hold the bias or an earlier partial sum) are multiplied by s 2^9 before the
 // products are added and by its inverse afterwards -- exact (powers of two), and the fp32 additions in between round as they would
-// unscaled.  An all-zero vector scales by 2^93 (harmless).
+// unscaled.  An all-zero vector (m == 0: e.g. the feature cotangent of an SDF backward that was given none, while its accumulator
+// already holds the sdf row's share) leaves the accumulators alone: its products are exactly 0, and the 2^102 of the clamped exponent
+// would turn every accumulator of magnitude 2^26 or more into inf (tests/test_gemm_float64_gpu.py, g_sdf alone at 2^20..2^40).  Otherwise
+// an accumulator overflows only where it exceeds the point's largest operand by 2^106 (below 2^-80: where it is 2^26 or more).
 struct PointScale {
     float s;        // operands x s
     int kpre;       // accumulators x 2^kpre before, x 2^-kpre after (v_ldexp_f32: a multiplication of the accumulator VECTORS by a
 };                  // float would compile to v_pk_mul_f32, which build.py's ISA check refuses)
 __device__ __forceinline__ PointScale point_scale_of(float m) {
-    unsigned e = __float_as_uint(m) >> 23;               // biased exponent (m >= 0)
+    const unsigned bits = __float_as_uint(m);
+    unsigned e = bits >> 23;                             // biased exponent (m >= 0)
     e = e < 47u ? 47u : (e > 207u ? 207u : e);          // (|E| <= 80: an accumulator of magnitude 2^25 still survives the 2^(149 - e) below)
 #ifdef NSA_X_NO_POINT_SCALE      // timing-only ablation (WRONG numbers; tagged builds): no per-point maximum, a constant scale (r6w)
     e = 127u;
 #endif
     PointScale r;
     r.s = __uint_as_float((267u - e) << 23);             // 2^(140 - e)
-    r.kpre = 149 - (int)e;                               // s * 2^9
+    r.kpre = bits == 0u ? 0 : 149 - (int)e;              // s * 2^9; 0 for an all-zero vector (a select, not a branch)
     return r;
 }
 template <int N>

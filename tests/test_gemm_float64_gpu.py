@@ -1,0 +1,714 @@
+"""Every fp32 MLP kernel of the render core against float64 (tests/ref64.py), per point, on adversarial operands.
+
+The default build feeds the 16-bit matrix cores with per-point power-of-two scaled operands (csrc/mlp_common.hpp::point_scale_of,
+DESIGN 4.4): the scale of a point comes from its largest operand, combined across its lanes, or from a bound handed down by the
+previous layer.  A wrong lane partner or hint, or a bad accumulator scaling, shows only at points whose operands are far smaller than
+their neighbours' -- invisible to tolerances relative to a tensor's maximum.  So every error here is PER POINT:
+  * e_k  = |kernel - float64|, e_32 = |oracle fp32 torch - float64| (the yardstick: oracle/render_ref.py on the same fp32 inputs),
+  * backward outputs divided by the point's cotangent scale c_p, forward outputs by the norm of the float64 output (floor 1),
+  * gate: rms(e_k) <= 1.5 rms(e_32) and max(e_k) <= 3 max(e_32) (tests/test_operand_form_gpu.py's, there over all points at once).
+Cotangent scales c_p = 2^U(-60, 40), neighbours alternating between 2^40 and 2^-60, some points all zero (exactly 0 out); each cotangent
+alone and all three at independent scales; g_sdf alone at 2^20..2^40 (the accumulator of the feature GEMM then holds sbar ws while its
+operand vector is zero); weights with max |w| in [64, 127.9] and rows below 2^-11.  Bit-for-bit properties that need no reference:
+point independence (other points' inputs changed, ragged P) and scale equivariance of the backwards (cotangents x 2^k).
+Inputs are explicit fp32 points (colour kernels: one sample per ray at z = 0, so x = o exactly), identical for kernel and references."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import ref64
+from helpers import load, params_of, oracle_config
+
+pytestmark = pytest.mark.gpu
+
+N_BIG = 16411                                   # ragged (16411 = 512 x 32 + 27)
+SMALL_P = (1, 15, 17, 31, 33, 4097)
+KINK = 2e-6                                     # colour ReLU margin left out on both sides (as tests/test_configs_gpu.py)
+REPORT = []
+
+
+def _st():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+# ------------------------------------------------------------------------------------------------------------------ the network
+class Net:
+    """A golden model's parameters with every weight_v perturbed (so that all input columns matter), optionally edited, on the CPU
+    (references) and the GPU (kernels)."""
+
+    def __init__(self, name="full_vis_eval", edit=None, seed=0):
+        from test_model_cpu import build_model
+        fx = dict(load(name))
+        g = torch.Generator().manual_seed(seed)
+        for k in sorted(fx):
+            if k.startswith("param_") and k.endswith("weight_v"):
+                v = torch.from_numpy(np.array(fx[k]))
+                fx[k] = (v + 0.05 * torch.randn(v.shape, generator=g)).numpy()
+        if edit:
+            edit(fx, g)
+        self.fx, self.cfg, self.params = fx, oracle_config(fx), params_of(fx)
+        self.model = build_model(fx).cuda().eval()
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+
+    def sdf(self, which, tile):
+        from nicer_slam_amd.fused import sampler as fs
+        self.model.sdf_tile = tile
+        gd, keep = fs.sdf_grid_desc(self.model, which)
+        return gd, keep, fs.packed_sdf(self.model, which)
+
+    def colour(self):
+        from nicer_slam_amd.fused import render as fr, sampler as fs
+        m = self.model
+        gd, keep = fs.grid_desc(m.rendering_network.encoding, m.rendering_network.divide_factor, 2, 0)
+        return gd, keep, fr.packed_colour(m)
+
+
+def _hl(P):
+    from nicer_slam_amd.fused import render as fr
+    return fr.hl_index(P, "cuda")
+
+
+def _to_hl(v):
+    from nicer_slam_amd.fused import render as fr
+    P = v.shape[0]
+    buf = torch.zeros(fr.hl_size(P), device="cuda")
+    buf[_hl(P)] = v.cuda()
+    return buf
+
+
+def _explicit(x):
+    from nicer_slam_amd._native import PointsDesc
+    return PointsDesc(None, None, None, x.data_ptr(), x.shape[0], 0, None)
+
+
+def _one_per_ray(o, d):
+    """rays with ONE sample at z = 0: x = o + 0 d = o exactly, view dir d (the colour kernels need rays)"""
+    from nicer_slam_amd._native import PointsDesc
+    z = torch.zeros(o.shape[0], 1, device="cuda")
+    return PointsDesc(o.data_ptr(), d.data_ptr(), z.data_ptr(), None, o.shape[0], 1, None), z
+
+
+# ------------------------------------------------------------------------------------------------------------------ kernels
+def k_sdf_forward(net, which, tile, x, accumulate=0, init=None):
+    from nicer_slam_amd._native import lib, check
+    P = x.shape[0]
+    xd = x.cuda().contiguous()
+    gd, _keep, pk = net.sdf(which, tile)
+    sdf = torch.zeros(P, device="cuda") if init is None else init[0].cuda().clone()
+    grad = torch.zeros(P, 3, device="cuda") if init is None else init[1].cuda().clone()
+    feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda") if init is None else _to_hl(init[2])
+    pts = _explicit(xd)
+    check(lib.nsa_sdfnet_forward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), accumulate, sdf.data_ptr(), grad.data_ptr(),
+                                 feat.data_ptr(), _st()))
+    torch.cuda.synchronize()
+    return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
+
+
+def k_sdf_pair(net, x):
+    from nicer_slam_amd._native import lib, check
+    from nicer_slam_amd.fused import sampler as fs
+    P = x.shape[0]
+    xd = x.cuda().contiguous()
+    net.model.sdf_tile = 16
+    gc, kc = fs.sdf_grid_desc(net.model, "coarse", "coarse_pair")
+    gf, kf = fs.sdf_grid_desc(net.model, "fine")
+    pc, pf = fs.packed_sdf(net.model, "coarse", use="coarse_pair"), fs.packed_sdf(net.model, "fine")
+    sdf, grad = torch.full((P,), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
+    feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda")
+    pts = _explicit(xd)
+    check(lib.nsa_sdfnet_forward_pair(ctypes.byref(pts), ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
+                                      sdf.data_ptr(), grad.data_ptr(), feat.data_ptr(), _st()))
+    torch.cuda.synchronize()
+    return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
+
+
+def k_sdf_backward(net, which, tile, x, g_sdf=None, g_feat=None, g_grad=None, accumulate=0, init=None, params=False):
+    from nicer_slam_amd._native import lib, check
+    from nicer_slam_amd.fused import mapping
+    P = x.shape[0]
+    xd = x.cuda().contiguous()
+    gd, _keep, pk = net.sdf(which, tile)
+    gs = g_sdf.cuda().contiguous() if g_sdf is not None else None
+    gf = _to_hl(g_feat) if g_feat is not None else None
+    gg = g_grad.cuda().contiguous() if g_grad is not None else None
+    g_x = torch.zeros(P, 3, device="cuda") if init is None else init.cuda().clone()
+    pts = _explicit(xd)
+    if not params:
+        check(lib.nsa_sdfnet_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
+                                      g_x.data_ptr(), _st()))
+        torch.cuda.synchronize()
+        return dict(x=g_x.cpu())
+    rows = lib.nsa_sdfnet_emit_rows_tile(gd.n_hidden, tile)
+    assert rows > 0
+    emit = torch.full((rows, mapping.emit_ld(P)), float("nan"), device="cuda")
+    check(lib.nsa_sdfnet_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
+                                         g_x.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
+    torch.cuda.synchronize()
+    return dict(x=g_x.cpu()), emit
+
+
+def k_colour_forward(net, x, d, normals, feat):
+    from nicer_slam_amd._native import lib, check
+    from nicer_slam_amd.fused import render as fr
+    P = x.shape[0]
+    o, dd = x.cuda().contiguous(), d.cuda().contiguous()
+    pts, _z = _one_per_ray(o, dd)
+    gd, _keep, pk = net.colour()
+    grad, fh = normals.cuda().contiguous(), _to_hl(feat)
+    rgb = torch.full((P, 3), float("nan"), device="cuda")
+    save = torch.zeros(fr.save_size(P), device="cuda")
+    check(lib.nsa_colour_forward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), rgb.data_ptr(),
+                                 save.data_ptr(), _st()))
+    torch.cuda.synchronize()
+    return rgb.cpu(), (o, dd, _z, grad, fh, save)
+
+
+def k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="plain", coarse_tile=32, g_sdf=None):
+    """kind: plain (nsa_colour_backward), params (nsa_colour_backward_params), coarse (nsa_colour_coarse_backward: + the coarse SDF
+    backward of the same points with g_sdf and the feature / normal cotangents just written)"""
+    from nicer_slam_amd._native import lib, check
+    from nicer_slam_amd.fused import mapping
+    P = x.shape[0]
+    _rgb, (o, dd, z, grad, fh, save) = k_colour_forward(net, x, d, normals, feat)
+    pts, _z = _one_per_ray(o, dd)
+    gd, _keep, pk = net.colour()
+    gr = g_rgb.cuda().contiguous()
+    g_feat = torch.full((((P + 31) // 32) * 2048,), float("nan"), device="cuda")
+    g_grad = torch.zeros(P, 3, device="cuda")
+    g_x, g_dir = torch.full((P, 3), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
+    emit = None
+    if kind == "plain":
+        check(lib.nsa_colour_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), save.data_ptr(),
+                                      gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(), g_x.data_ptr(), g_dir.data_ptr(),
+                                      _st()))
+    elif kind == "params":
+        emit = torch.full((lib.nsa_colour_emit_rows(), mapping.emit_ld(P)), float("nan"), device="cuda")
+        check(lib.nsa_colour_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
+                                             save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
+                                             g_x.data_ptr(), g_dir.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
+    else:
+        gc, _kc, pc = net.sdf("coarse", coarse_tile)
+        gs = g_sdf.cuda().contiguous()
+        check(lib.nsa_colour_coarse_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
+                                             save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
+                                             g_x.data_ptr(), g_dir.data_ptr(), ctypes.byref(gc), pc.data_ptr(), gs.data_ptr(), _st()))
+    torch.cuda.synchronize()
+    out = dict(feat=g_feat[_hl(P)].cpu(), normals=g_grad.cpu(), x=g_x.cpu(), dirs=g_dir.cpu())
+    return (out, emit) if kind == "params" else out
+
+
+# ------------------------------------------------------------------------------------------------------------------ inputs
+def _cube_points(n, seed):
+    """uniform in the cube, an eighth of them within 1e-3 of a face (some exactly on it)"""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.999
+    m = n // 8
+    i, face = torch.arange(m), torch.randint(3, (m,), generator=g)
+    x[i, face] = torch.sign(x[i, face]) * (1 - torch.rand(m, generator=g) * 1e-3)
+    x[i[::17], face[::17]] = torch.sign(x[i[::17], face[::17]])
+    return x[torch.randperm(n, generator=g)].contiguous()
+
+
+def _scales(n, seed, alternate=True, zeros=True):
+    """c_p = 2^U(-60, 40); within the first half neighbours alternate 2^40 / 2^-60; every 97th point 0"""
+    g = torch.Generator().manual_seed(seed)
+    e = torch.randint(-60, 41, (n,), generator=g).double()
+    if alternate:
+        h = torch.arange(n // 2)
+        e[h] = torch.where(h % 2 == 0, 40.0, -60.0).double()
+    c = torch.exp2(e)
+    if zeros:
+        c[torch.arange(n) % 97 == 5] = 0.0
+    return c
+
+
+def _cot(n, seed, shape):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn((n,) + shape, generator=g)
+
+
+def _scaled(base, c):
+    return (base.double() * c.reshape((-1,) + (1,) * (base.dim() - 1))).float()
+
+
+def _colour_inputs(net, n, seed):
+    from oracle import render_ref as R
+    x = _cube_points(n, seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    _s, feat, grad = R.sdf_outputs(net.params, net.cfg, x.clone(), "fine")
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1) * (0.6 + 0.8 * torch.rand(n, 1, generator=g))
+    return x, d.contiguous(), grad.detach().contiguous(), feat.detach().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------ the gate
+def _per_point(e, norm):
+    e = e.reshape(e.shape[0], -1).double().norm(dim=1)
+    return e / norm
+
+
+def gate(what, got, ref, y32, norm, keep=None, failures=None):
+    """per-point errors of kernel (got) and yardstick (y32) against float64 (ref), divided by norm [P]; rows with norm 0 must be
+    exactly 0 in the kernel output and are left out; keep: rows to judge."""
+    got, ref, y32 = (t.reshape(t.shape[0], -1).double() for t in (got, ref, y32))
+    zero = norm == 0
+    if bool(zero.any()):
+        assert bool((got[zero] == 0).all()), f"{what}: a point with all-zero cotangents has a non-zero output"
+    sel = ~zero if keep is None else (~zero & keep)
+    nz = norm.clone()
+    nz[zero] = 1
+    e_k, e_32 = _per_point(got - ref, nz)[sel], _per_point(y32 - ref, nz)[sel]
+    finite = bool(torch.isfinite(got[sel]).all())
+    rms = lambda e: float((e ** 2).mean().sqrt())
+    r = dict(what=what, n=int(sel.sum()), rms_k=rms(e_k), rms_32=rms(e_32), max_k=float(e_k.max()), max_32=float(e_32.max()),
+             finite=finite)
+    ok = finite and r["rms_k"] <= 1.5 * r["rms_32"] and r["max_k"] <= 3.0 * r["max_32"]
+    r["ok"] = ok
+    REPORT.append(r)
+    print(f"  {what:<58s} n={r['n']:6d}  e_k rms {r['rms_k']:.2e} max {r['max_k']:.2e}   e_32 rms {r['rms_32']:.2e} "
+          f"max {r['max_32']:.2e}  {'ok' if ok else 'FAIL'}")
+    if failures is not None and not ok:
+        failures.append(r)
+    return ok
+
+
+def _fwd_norm(ref):
+    return ref.reshape(ref.shape[0], -1).double().norm(dim=1).clamp_min(1.0)
+
+
+@pytest.fixture(scope="module")
+def net():
+    return Net()
+
+
+# ------------------------------------------------------------------------------------------------------------------ forward
+def test_sdf_forward_kernels_vs_float64(net, capsys):
+    from oracle import render_ref as R
+    x = _cube_points(N_BIG, 1)
+    fails = []
+    g = torch.Generator().manual_seed(2)
+    init = (torch.randn(N_BIG, generator=g), torch.randn(N_BIG, 3, generator=g), torch.randn(N_BIG, 64, generator=g))
+    with capsys.disabled():
+        print()
+        for which in ("coarse", "fine"):
+            nets = (which,)
+            ref = ref64.sdf_forward(net.params, net.cfg, x, nets)
+            s32, f32, g32 = ref64.sdf_forward(net.params, net.cfg, x, nets, dtype=torch.float32)
+            so, fo, go = R._net_outputs(net.params, ref64.NETS[which], getattr(net.cfg, which), x.clone())
+            y32 = (so[:, 0].detach(), go.detach(), fo.detach())
+            for tile in (16, 32):
+                for acc in (0, 1):
+                    out = k_sdf_forward(net, which, tile, x, acc, init if acc else None)
+                    for k, r, y, i in zip(("sdf", "grad", "feat"), ref, y32, range(3)):
+                        r_ = r + init[i].double() if acc else r
+                        y_ = (y + init[i]) if acc else y
+                        gate(f"sdfnet_forward {which} tile {tile} acc {acc}: {k}", out[k], r_, y_, _fwd_norm(r_), failures=fails)
+                    if acc == 0:
+                        for P in SMALL_P:
+                            small = k_sdf_forward(net, which, tile, x[:P].contiguous())
+                            for k in small:
+                                assert torch.equal(small[k], out[k][:P]), f"{which} tile {tile}: P = {P} changes {k}"
+        ref = ref64.sdf_forward(net.params, net.cfg, x)
+        so, fo, go = R.sdf_outputs(net.params, net.cfg, x.clone(), "fine")
+        out = k_sdf_pair(net, x)
+        for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
+            gate(f"sdfnet_forward_pair: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+    assert not fails, [f["what"] for f in fails]
+
+
+def test_sampler_vs_float64(net, capsys):
+    """nsa_sampler_sdf at rays along coordinate axes (o on a 1/8 lattice): o + z d rounds once in any fp32 implementation, so the
+    test's points are the kernel's bit for bit; the far plane of rays with zero direction components is the oracle's."""
+    from nicer_slam_amd.fused import sampler as fs
+    from oracle import render_ref as R
+    g = torch.Generator().manual_seed(4)
+    Rn = 509
+    axis, sign = torch.randint(3, (Rn,), generator=g), torch.randint(2, (Rn,), generator=g) * 2 - 1
+    d = torch.zeros(Rn, 3)
+    d[torch.arange(Rn), axis] = sign.float()
+    o = torch.randint(-6, 7, (Rn, 3), generator=g).float() / 8
+    E = net.model.ray_sampler.N_samples_eval
+    t_rand = torch.rand(Rn, E, generator=g)
+    fails = []
+    with capsys.disabled():
+        print()
+        res = {}
+        for tile in (16, 32, 64):
+            net.model.sdf_tile = tile
+            z, sdf, far = (t.cpu() for t in fs.sampler_sdf(net.model, o.cuda(), d.cuda(), t_rand.cuda()))
+            us = net.model.ray_sampler.uniform_sampler
+            far_o = R.cube_far(o, d, float(us.scene_bounding_sphere), float(us.far)).reshape(-1)
+            assert torch.equal(far, far_o), f"far plane (tile {tile}): {int((far != far_o).sum())} rays differ"
+            x = (o.unsqueeze(1) + z.unsqueeze(2) * d.unsqueeze(1)).reshape(-1, 3).contiguous()
+            if tile == 16:
+                ref = ref64.sdf_forward(net.params, net.cfg, x)[0]
+                with torch.no_grad():
+                    y32 = R.sdf_vals(net.params, net.cfg, x.clone()).reshape(-1)
+            res[tile] = (z, sdf)
+            assert torch.equal(z, res[16][0]), f"tile {tile}: z differs from the quad tiling's"
+            gate(f"sampler_sdf tile {tile}: sdf", sdf.reshape(-1), ref, y32, _fwd_norm(ref), failures=fails)
+    assert not fails, [f["what"] for f in fails]
+
+
+# ------------------------------------------------------------------------------------------------------------------ SDF backward
+def _sdf_families(n):
+    """name -> (g_sdf, g_feat, g_grad, c_p): cotangents of O(1) random base values times per-point scales"""
+    base = (_cot(n, 10, ()), _cot(n, 11, (64,)), _cot(n, 12, (3,)))
+    c = _scales(n, 13)
+    fam = {"all three x c_p": tuple(_scaled(b, c) for b in base) + (c,)}
+    for i, name in enumerate(("g_sdf", "g_feat", "g_grad")):
+        fam[name + " alone x c_p"] = tuple(_scaled(b, c) if j == i else None for j, b in enumerate(base)) + (c,)
+    cs = [_scales(n, 20 + i, alternate=(i == 1)) for i in range(3)]
+    fam["independent scales per input"] = tuple(_scaled(b, ci) for b, ci in zip(base, cs)) + (torch.stack(cs).amax(0),)
+    g = torch.Generator().manual_seed(30)
+    ca = torch.exp2(torch.randint(20, 41, (n,), generator=g).double())
+    fam["g_sdf alone at 2^20..2^40 (features, normals NULL)"] = (_scaled(base[0], ca), None, None, ca)
+    return fam
+
+
+def _sdf_refs(net, which, x, fam):
+    from oracle import render_ref as R
+    out = {}
+    xs = x.clone().requires_grad_(True)
+    so, fo, go = R._net_outputs(net.params, ref64.NETS[which], getattr(net.cfg, which), xs)
+    for name, (gs, gf, gg, c) in fam.items():
+        ref = ref64.sdf_backward(net.params, net.cfg, x, gs, gf, gg, (which,))
+        obj = sum((g_ * y).sum() for g_, y in ((gs, so[:, 0]), (gf, fo), (gg, go)) if g_ is not None)
+        (y32,) = torch.autograd.grad(obj, xs, retain_graph=True)
+        out[name] = (ref, y32.detach())
+    return out
+
+
+@pytest.mark.parametrize("which", ["coarse", "fine"])
+def test_sdf_backward_vs_float64(net, which, capsys):
+    x = _cube_points(N_BIG, 5)
+    fam = _sdf_families(N_BIG)
+    refs = _sdf_refs(net, which, x, fam)
+    init = _cot(N_BIG, 40, (3,))
+    fails = []
+    with capsys.disabled():
+        print()
+        for tile in (16, 32):
+            for name, (gs, gf, gg, c) in fam.items():
+                ref, y32 = refs[name]
+                out = k_sdf_backward(net, which, tile, x, gs, gf, gg)["x"]
+                gate(f"sdfnet_backward {which} t{tile}: {name}", out, ref, y32, c, failures=fails)
+                if name == "all three x c_p":
+                    # accumulate 1: onto O(1) values, so only points with c_p ~ 1 are judged; the rest must be the init's
+                    acc = k_sdf_backward(net, which, tile, x, gs, gf, gg, accumulate=1, init=init)["x"]
+                    unit = (c >= 2.0 ** -3) & (c <= 2.0 ** 3)
+                    gate(f"sdfnet_backward {which} t{tile}: accumulate 1, c_p in [1/8, 8]", acc, ref + init.double(),
+                         (y32 + init), torch.ones(N_BIG).double(), keep=unit, failures=fails)
+                    for P in SMALL_P:
+                        small = k_sdf_backward(net, which, tile, x[:P].contiguous(), gs[:P], gf[:P], gg[:P])["x"]
+                        assert torch.equal(small, out[:P]), f"{which} tile {tile}: P = {P} changes d/dx"
+                if "NULL" in name:
+                    assert bool(torch.isfinite(out).all()), f"{which} tile {tile}: non-finite d/dx with g_sdf alone"
+    assert not fails, [f["what"] for f in fails]
+
+
+# ------------------------------------------------------------------------------------------------------------------ colour
+def _colour_refs(net, x, d, normals, feat, g_rgb, grid_grad):
+    from oracle import render_ref as R
+    ref = ref64.colour_backward(net.params, net.cfg, x, normals, d, feat, g_rgb, grid_grad)
+    ins = [t.clone().requires_grad_(True) for t in (x, normals, d, feat)]
+    rgb = R.colour_net(net.params, net.cfg, *ins, color_stage="highfreq" if grid_grad else "base")
+    y32 = dict(zip(("x", "normals", "dirs", "feat"), torch.autograd.grad((g_rgb * rgb).sum(), ins)))
+    return ref, y32
+
+
+def test_colour_kernels_vs_float64(net, capsys):
+    from oracle import render_ref as R
+    x, d, normals, feat = _colour_inputs(net, N_BIG, 7)
+    keep = R.colour_relu_margin(net.params, net.cfg, x, normals, d, feat) >= KINK
+    assert int((~keep).sum()) <= N_BIG // 100, int((~keep).sum())
+    fails = []
+    with capsys.disabled():
+        print(f"\n  colour: {int((~keep).sum())} of {N_BIG} points within {KINK} of a ReLU kink left out")
+        rgb, _bufs = k_colour_forward(net, x, d, normals, feat)
+        ref = ref64.colour_forward(net.params, net.cfg, x, normals, d, feat)
+        with torch.no_grad():
+            y32 = R.colour_net(net.params, net.cfg, x, normals, d, feat)
+        gate("colour_forward: rgb", rgb, ref, y32, _fwd_norm(ref), keep, failures=fails)
+        for P in SMALL_P:
+            small, _b = k_colour_forward(net, x[:P].contiguous(), d[:P].contiguous(), normals[:P].contiguous(), feat[:P].contiguous())
+            assert torch.equal(small, rgb[:P]), f"colour forward: P = {P} changes rgb"
+        c = _scales(N_BIG, 8)
+        g_rgb = _scaled(_cot(N_BIG, 9, (3,)), c)
+        for grid_grad in (0, 1):
+            ref, y32 = _colour_refs(net, x, d, normals, feat, g_rgb, grid_grad)
+            out = k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad)
+            for k in ("feat", "normals", "x", "dirs"):
+                gate(f"colour_backward grid_grad {grid_grad}: d/d {k}", out[k], ref[k], y32[k], c, keep, failures=fails)
+            for P in SMALL_P:
+                small = k_colour_backward(net, x[:P].contiguous(), d[:P].contiguous(), normals[:P].contiguous(), feat[:P].contiguous(),
+                                          g_rgb[:P].contiguous(), grid_grad)
+                for k in small:
+                    assert torch.equal(small[k], out[k][:P]), f"colour backward: P = {P} changes d/d {k}"
+            # colour + coarse SDF backward in one launch: d/dx = colour's + the coarse network's for (g_sdf, the colour's feature and
+            # normal cotangents); the float64 chain takes the float64 cotangents, the yardstick its own fp32 ones
+            g_sdf = _scaled(_cot(N_BIG, 15, ()), c)
+            outc = k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="coarse", g_sdf=g_sdf)
+            for k in ("feat", "normals", "dirs"):
+                assert torch.equal(outc[k], out[k]), f"colour_coarse_backward: d/d {k} differs from nsa_colour_backward's"
+            r_x = ref["x"] + ref64.sdf_backward(net.params, net.cfg, x, g_sdf, ref["feat"], ref["normals"], ("coarse",))
+            xs = x.clone().requires_grad_(True)
+            so, fo, go = R._net_outputs(net.params, "implicit_network.coarse", net.cfg.coarse, xs)
+            (yc,) = torch.autograd.grad((g_sdf * so[:, 0]).sum() + (y32["feat"] * fo).sum() + (y32["normals"] * go).sum(), xs)
+            gate(f"colour_coarse_backward grid_grad {grid_grad}: d/dx", outc["x"], r_x, y32["x"] + yc.detach(), c, keep, failures=fails)
+    assert not fails, [f["what"] for f in fails]
+
+
+# ------------------------------------------------------------------------------------------------------------------ _params twins
+# nsa_sdfnet_backward_params runs the same body as nsa_sdfnet_backward with MAP = true, which also keeps the grid Jacobian in LDS
+# (csrc/sdfnet_bwd_body.inc: kJacLds = (NH > 1) || MAP).  For the fine network (NH = 3) both entries therefore take the LDS path
+# (tangent_from_jac / slots_to_x_jac), and the quad tiling has one path for both: there the data path must be bit-identical.  The
+# coarse network in the 32-point tiling is the exception: its plain kernel recomputes the Jacobian from the corner gathers
+# (x_to_slots_tangent / slots_to_x), its MAP kernel reads the stored one -- the same sums in a different rounding order.  That pair is
+# held to the float64 gate instead, and to point independence across P.
+LDS_JACOBIAN_ONLY_IN_MAP = {("coarse", 32)}
+
+
+@pytest.mark.parametrize("which,tile", [("coarse", 16), ("coarse", 32), ("fine", 16), ("fine", 32)])
+def test_sdf_params_kernel_data_path_and_padding(net, which, tile, capsys):
+    x_big = _cube_points(N_BIG, 11)
+    fam = _sdf_families(N_BIG)
+    gs, gf, gg, c = fam["all three x c_p"]
+    big, smalls = None, []
+    for P in (33, 4097, N_BIG):
+        x = x_big[:P].contiguous()
+        out, emit = k_sdf_backward(net, which, tile, x, gs[:P], gf[:P], gg[:P], params=True)
+        end = -(-P // tile) * tile
+        assert bool((emit[:, P:end] == 0).all()), f"sdfnet_backward_params {which} t{tile} P={P}: padding columns are not 0"
+        del emit
+        if (which, tile) not in LDS_JACOBIAN_ONLY_IN_MAP:
+            plain = k_sdf_backward(net, which, tile, x, gs[:P], gf[:P], gg[:P])["x"]
+            diff = out["x"] != plain
+            assert not bool(diff.any()), (f"sdfnet_backward_params {which} t{tile} P={P}: d/dx differs from nsa_sdfnet_backward's at "
+                                          f"{int(diff.any(1).sum())} points")
+        elif P < N_BIG:
+            smalls.append(out["x"])
+        else:
+            big = out["x"]
+    if (which, tile) in LDS_JACOBIAN_ONLY_IN_MAP:
+        for small in smalls:
+            assert torch.equal(small, big[:small.shape[0]]), f"sdfnet_backward_params: P = {small.shape[0]} changes d/dx"
+        ref, y32 = _sdf_refs(net, which, x_big, {"all three x c_p": fam["all three x c_p"]})["all three x c_p"]
+        with capsys.disabled():
+            print()
+            assert gate(f"sdfnet_backward_params {which} t{tile}: all three x c_p", big, ref, y32, c)
+
+
+@pytest.mark.parametrize("P", [33, 4097, N_BIG])
+def test_colour_params_kernel_data_path_is_bit_identical_and_padding_zero(net, P):
+    xc, d, normals, feat = _colour_inputs(net, P, 12)
+    g_rgb = _scaled(_cot(P, 13, (3,)), _scales(P, 14))
+    for grid_grad in (0, 1):
+        plain = k_colour_backward(net, xc, d, normals, feat, g_rgb, grid_grad)
+        out, emit = k_colour_backward(net, xc, d, normals, feat, g_rgb, grid_grad, kind="params")
+        end = -(-P // 32) * 32
+        assert bool((emit[:, P:end] == 0).all()), "colour_backward_params: padding columns are not 0"
+        for k in plain:
+            assert torch.equal(out[k], plain[k]), f"colour_backward_params grid_grad {grid_grad}: d/d {k} differs"
+
+
+# ------------------------------------------------------------------------------------------------------------------ properties
+def _backward_runs(net, x, xc, d, normals, feat):
+    """name -> f(scale [P]) running one backward kernel with every cotangent of point p multiplied by scale[p]"""
+    P = x.shape[0]
+    base = (_cot(P, 50, ()), _cot(P, 51, (64,)), _cot(P, 52, (3,)))
+    g_rgb, g_sdf = _cot(P, 53, (3,)), _cot(P, 54, ())
+    runs = {}
+    for which in ("coarse", "fine"):
+        for tile in (16, 32):
+            runs[f"sdfnet_backward {which} t{tile}"] = (
+                lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(_scaled(b, s) for b in base)))
+            runs[f"sdfnet_backward_params {which} t{tile}"] = (
+                lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(_scaled(b, s) for b in base), params=True)[0])
+    for grid_grad in (0, 1):
+        runs[f"colour_backward gg {grid_grad}"] = (
+            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad))
+        runs[f"colour_backward_params gg {grid_grad}"] = (
+            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad, kind="params")[0])
+        runs[f"colour_coarse_backward gg {grid_grad}"] = (
+            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad, kind="coarse",
+                                                             g_sdf=_scaled(g_sdf, s)))
+    return runs
+
+
+@pytest.mark.parametrize("P", [33, 4097])
+def test_backwards_are_point_independent_and_scale_equivariant_bit_for_bit(net, P):
+    x = _cube_points(P, 60)
+    xc, d, normals, feat = _colour_inputs(net, P, 61)
+    ones = torch.ones(P).double()
+    odd = torch.arange(P) % 2 == 1
+    g = torch.Generator().manual_seed(62)
+    other = torch.where(odd, torch.exp2(torch.randint(0, 3, (P,), generator=g).double() * 40 - 40), ones)   # 2^-40, 1, 2^40
+    other[odd & (torch.arange(P) % 3 == 0)] = 0.0
+    for name, run in _backward_runs(net, x, xc, d, normals, feat).items():
+        ref = run(ones)
+        moved = run(other)
+        for k in ref:
+            assert torch.equal(moved[k][~odd], ref[k][~odd]), f"{name}: other points' cotangents change d/d {k}"
+        for kexp in (-40, -13, 17, 40):
+            s = torch.where(odd, torch.full((P,), 2.0 ** kexp).double(), ones)
+            out = run(s)
+            for k in ref:
+                want = ref[k].double() * s.reshape((-1,) + (1,) * (ref[k].dim() - 1))
+                assert torch.equal(out[k].double(), want), \
+                    f"{name}: cotangents x 2^{kexp} do not scale d/d {k} by 2^{kexp}: {int((out[k].double() != want).sum())} entries"
+
+
+def test_forwards_are_point_independent(net):
+    P = 4097
+    x = _cube_points(P, 70)
+    odd = torch.arange(P) % 2 == 1
+    x2 = x.clone()
+    x2[odd] = _cube_points(P, 71)[odd]
+    for which in ("coarse", "fine"):
+        for tile in (16, 32):
+            a, b = k_sdf_forward(net, which, tile, x), k_sdf_forward(net, which, tile, x2)
+            for k in a:
+                assert torch.equal(a[k][~odd], b[k][~odd]), f"sdfnet_forward {which} t{tile}: other points' positions change {k}"
+    a, b = k_sdf_pair(net, x), k_sdf_pair(net, x2)
+    for k in a:
+        assert torch.equal(a[k][~odd], b[k][~odd]), f"sdfnet_forward_pair: other points' positions change {k}"
+    xc, d, normals, feat = _colour_inputs(net, P, 72)
+    xc2, d2, n2, f2 = _colour_inputs(net, P, 73)
+    sw = lambda u, v: torch.where(odd.reshape((-1,) + (1,) * (u.dim() - 1)), v, u).contiguous()
+    a, _ = k_colour_forward(net, xc, d, normals, feat)
+    b, _ = k_colour_forward(net, sw(xc, xc2), sw(d, d2), sw(normals, n2), sw(feat, f2))
+    assert torch.equal(a[~odd], b[~odd]), "colour_forward: other points' inputs change rgb"
+    # the sampler: other rays' origins, directions and jitter changed (ragged ray count)
+    from nicer_slam_amd.fused import sampler as fs
+    g = torch.Generator().manual_seed(74)
+    Rn, E = 261, net.model.ray_sampler.N_samples_eval
+    rays = [(((torch.rand(Rn, 3, generator=g) * 2 - 1) * 0.8), torch.nn.functional.normalize(torch.randn(Rn, 3, generator=g), dim=-1),
+             torch.rand(Rn, E, generator=g)) for _ in range(2)]
+    odd_r = torch.arange(Rn) % 2 == 1
+    mixed = [torch.where(odd_r.reshape((-1,) + (1,) * (u.dim() - 1)), v, u).contiguous() for u, v in zip(*rays)]
+    for tile in (16, 32, 64):
+        net.model.sdf_tile = tile
+        a = fs.sampler_sdf(net.model, *(t.cuda() for t in rays[0]))
+        b = fs.sampler_sdf(net.model, *(t.cuda() for t in mixed))
+        for u, v, what in zip(a, b, ("z", "sdf", "far")):
+            assert torch.equal(u[~odd_r.cuda()], v[~odd_r.cuda()]), f"sampler_sdf tile {tile}: other rays change {what}"
+
+
+# ------------------------------------------------------------------------------------------------------------------ weights
+def _big_weights(fx, g):
+    """fine lin1 and colour lin1: max |w| in [64, 127.9] (weight_g of the row with the largest |v| / |v|), eight rows below 2^-11"""
+    for key in ("param_implicit_network.fine.lin1", "param_rendering_network.lin1"):
+        v = torch.from_numpy(np.array(fx[key + ".weight_v"]))
+        wg = torch.from_numpy(np.array(fx[key + ".weight_g"])).clone()
+        ratio = v.abs().amax(1) / v.norm(dim=1)
+        ratio[8:16] = 0
+        r = int(ratio.argmax())
+        wg[r, 0] = 120.0 / float(ratio[r])
+        wg[8:16, 0] = 2.0 ** -14
+        fx[key + ".weight_g"] = wg.numpy()
+
+
+def _max_w(params, prefix):
+    g, v = params[prefix + ".weight_g"].double(), params[prefix + ".weight_v"].double()
+    w = v * (g / v.norm(dim=1, keepdim=True))
+    return float(w.abs().max()), float(w[8:16].abs().max())
+
+
+# Open finding (measured on the MI355X): with max |w| ~ 120 in a hidden layer the 32-point tiling's fine network is further from float64
+# than the fp32 yardstick in the gates named here -- the backward in both operand forms (form 3 1.7x the yardstick's rms, form 2 3.6x),
+# the grad sdf of the forward in form 2 (2.1x) -- while the quad tiling, whose scale hints have the same structure
+# (sdfnet_bwd_body.inc / sdfnet4_bwd_body.inc), is within every gate.  Not yet traced to a line.  Every other gate of this
+# test holds; only these may fail, and the test says so when one of them starts to pass.
+KNOWN_BIG_WEIGHT_MISSES = {2: {"big weights: sdfnet_backward fine t32: all three x c_p", "big weights: sdfnet_forward fine t32: grad"},
+                           3: {"big weights: sdfnet_backward fine t32: all three x c_p"}}
+
+
+@pytest.mark.parametrize("tile", [16, 32])
+def test_weights_near_the_pack_limit_vs_float64(tile, capsys):
+    from oracle import render_ref as R
+    net = Net(edit=_big_weights, seed=3)
+    for prefix in ("implicit_network.fine.lin1", "rendering_network.lin1"):
+        top, small = _max_w(net.params, prefix)
+        assert 64 <= top <= 127.9 and small < 2.0 ** -11, (prefix, top, small)
+    x = _cube_points(N_BIG, 80)
+    fails = []
+    with capsys.disabled():
+        print()
+        ref = ref64.sdf_forward(net.params, net.cfg, x, ("fine",))
+        so, fo, go = R._net_outputs(net.params, "implicit_network.fine", net.cfg.fine, x.clone())
+        fam = _sdf_families(N_BIG)
+        refs = _sdf_refs(net, "fine", x, {k: fam[k] for k in ("all three x c_p", "g_sdf alone at 2^20..2^40 (features, normals NULL)")})
+        out = k_sdf_forward(net, "fine", tile, x)
+        for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
+            gate(f"big weights: sdfnet_forward fine t{tile}: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+        for name, (r, y) in refs.items():
+            gs, gf, gg, c = fam[name]
+            gate(f"big weights: sdfnet_backward fine t{tile}: {name}", k_sdf_backward(net, "fine", tile, x, gs, gf, gg)["x"],
+                 r, y, c, failures=fails)
+        xc, d, normals, feat = _colour_inputs(net, N_BIG, 81)
+        keep = R.colour_relu_margin(net.params, net.cfg, xc, normals, d, feat) >= KINK
+        assert int((~keep).sum()) <= N_BIG // 100
+        rgb, _b = k_colour_forward(net, xc, d, normals, feat)
+        r = ref64.colour_forward(net.params, net.cfg, xc, normals, d, feat)
+        with torch.no_grad():
+            y = R.colour_net(net.params, net.cfg, xc, normals, d, feat)
+        gate("big weights: colour_forward: rgb", rgb, r, y, _fwd_norm(r), keep, failures=fails)
+        c = _scales(N_BIG, 82)
+        g_rgb = _scaled(_cot(N_BIG, 83, (3,)), c)
+        ref_c, y32 = _colour_refs(net, xc, d, normals, feat, g_rgb, 1)
+        out = k_colour_backward(net, xc, d, normals, feat, g_rgb, 1)
+        for k in ("feat", "normals", "x", "dirs"):
+            gate(f"big weights: colour_backward: d/d {k}", out[k], ref_c[k], y32[k], c, keep, failures=fails)
+    from nicer_slam_amd.fused import pack
+    known = {w for w in KNOWN_BIG_WEIGHT_MISSES.get(pack.operand_form(), set()) if f" t{tile}:" in w}
+    missed = {f["what"] for f in fails}
+    assert missed <= known, sorted(missed - known)
+    assert missed == known, f"known misses now within the gate (update KNOWN_BIG_WEIGHT_MISSES and DESIGN 4.4): {sorted(known - missed)}"
+
+
+def test_a_weight_past_the_pack_limit_is_loud_in_form_2(capsys):
+    """|w| = 130 packs to +-inf in form 2 (fused/pack.py::split_f16x2): every output that depends on it must be non-finite, never
+    finite and wrong.  Form 3 takes such a weight exactly: there the same network must pass the float64 gate."""
+    from nicer_slam_amd.fused import pack
+    from oracle import render_ref as R
+
+    def edit(fx, g):
+        key = "param_implicit_network.fine.lin1"
+        v = torch.from_numpy(np.array(fx[key + ".weight_v"]))
+        wg = torch.from_numpy(np.array(fx[key + ".weight_g"])).clone()
+        wg[5, 0] = 130.0 * float(v[5].norm()) / float(v[5].abs().max())
+        fx[key + ".weight_g"] = wg.numpy()
+
+    net = Net(edit=edit, seed=4)
+    top, _ = _max_w(net.params, "implicit_network.fine.lin1")
+    assert abs(top - 130.0) < 1e-3, top
+    x = _cube_points(4097, 90)
+    c = _scales(4097, 91, zeros=False)
+    gs, gf, gg = (_scaled(b, c) for b in (_cot(4097, 92, ()), _cot(4097, 93, (64,)), _cot(4097, 94, (3,))))
+    form = pack.operand_form()
+    fails = []
+    with capsys.disabled():
+        print(f"\n  operand form {form}")
+        for tile in (16, 32):
+            out = k_sdf_forward(net, "fine", tile, x)
+            bwd = k_sdf_backward(net, "fine", tile, x, gs, gf, gg)["x"]
+            if form == 2:
+                for k, v in list(out.items()) + [("d/dx", bwd)]:
+                    assert not bool(torch.isfinite(v).any()), f"form 2, |w| = 130, tile {tile}: {k} has finite entries"
+            else:
+                ref = ref64.sdf_forward(net.params, net.cfg, x, ("fine",))
+                so, fo, go = R._net_outputs(net.params, "implicit_network.fine", net.cfg.fine, x.clone())
+                for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
+                    gate(f"|w| = 130, form 3: sdfnet_forward fine t{tile}: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+                r, y = _sdf_refs(net, "fine", x, {"b": (gs, gf, gg, c)})["b"]
+                gate(f"|w| = 130, form 3: sdfnet_backward fine t{tile}: all three x c_p", bwd, r, y, c, failures=fails)
+    # (the 32-point fine backward with large weights is a known miss of the float64 gate, see KNOWN_BIG_WEIGHT_MISSES)
+    missed = {f["what"] for f in fails}
+    assert missed <= {"|w| = 130, form 3: sdfnet_backward fine t32: all three x c_p"}, sorted(missed)
