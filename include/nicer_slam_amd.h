@@ -36,6 +36,7 @@ extern "C" {
 #define NSA_ELAUNCH 3          /* hipGetLastError() != hipSuccess after a launch */
 #define NSA_EBADARG 4          /* null pointer / inconsistent sizes */
 #define NSA_EUNSUPPORTED_NET 5 /* fused core: network shape outside the compiled set */
+#define NSA_EMESH_TOO_LARGE 6  /* marching cubes: a vertex or face total does not fit int32 */
 
 #define NSA_MAX_LEVELS 32
 
@@ -549,6 +550,32 @@ typedef struct nsa_copy_seg {
     uint32_t n; /* floats */
 } nsa_copy_seg_t;
 int nsa_copy_segments(const nsa_copy_seg_t *segs, uint32_t n_segs, nsa_stream_t stream);
+
+/* ---- Section 7: mesh extraction (marching cubes over a dense fp32 volume; DESIGN 4f, csrc/mesh_extract.hip) ------------- */
+
+/* vol[nx, ny, nz] C-contiguous, sample (x, y, z) at (x * ny + y) * nz + z -- the layout nicer_slam_amd.inference.sdf_grid returns.
+ * Inside is value < level.  One vertex per grid edge whose two samples are finite and on opposite sides, at
+ *   t = (level - f0) / (f1 - f0),  p_k = origin_k + spacing_k * c_k,  c_k = (float)i_k (k != axis a), c_a = (float)i_a + t
+ * (fp32, no FMA contraction; f0 at the edge's lower sample i).  Its normal is the central-difference volume gradient
+ * (one-sided on the border) interpolated with t and normalised, pointing towards increasing value (0 when the interpolated
+ * gradient is zero or not finite).  A cell with a non-finite corner emits no faces.  Vertices are ordered by (lower sample,
+ * axis), faces [F,3] int32 by (cell, case-table order; csrc/mc_table.hpp), oriented inside -> outside.  nx * ny * nz <= 2^31;
+ * a dimension below 2 gives an empty mesh.  Nothing is allocated or synchronised; the workspace belongs to the caller.
+ * Together these replace skimage.measure.marching_cubes (code/utils/plots.py:128, spacing :130-134, origin :136). */
+
+/* bytes of workspace for a volume of nx * ny * nz samples */
+uint64_t nsa_marching_cubes_workspace(uint32_t nx, uint32_t ny, uint32_t nz);
+
+/* Phase 1: classify every cell and edge and write totals[2] = {vertices, faces} (uint64, device) for nsa_marching_cubes_emit. */
+int nsa_marching_cubes_count(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, void *workspace,
+                             uint64_t *totals, nsa_stream_t stream);
+
+/* Phase 2, after phase 1 on the same volume, level and workspace: verts[n_verts, 3], normals[n_verts, 3], faces[n_faces, 3]
+ * with n_verts, n_faces the totals of phase 1 (read by the caller to size the outputs; nothing past them is written).
+ * origin_host[3] / spacing_host[3] per axis (spacing finite and > 0).  A total above INT32_MAX returns NSA_EMESH_TOO_LARGE. */
+int nsa_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, float level, const float *origin_host,
+                            const float *spacing_host, void *workspace, uint64_t n_verts, uint64_t n_faces, float *verts,
+                            float *normals, int32_t *faces, nsa_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -275,3 +275,12 @@ lib.nsa_masked_l1_workspace.restype = _u64
 lib.nsa_masked_l1_workspace.argtypes = [_u64]
 EXPORTS += ["nsa_patch_warp_forward", "nsa_patch_warp_backward", "nsa_patch_warp_workspace", "nsa_flow_forward",
             "nsa_flow_backward", "nsa_flow_workspace", "nsa_masked_l1", "nsa_masked_l1_workspace"]
+
+lib.nsa_marching_cubes_workspace.restype = _u64
+lib.nsa_marching_cubes_workspace.argtypes = [_u32, _u32, _u32]
+lib.nsa_marching_cubes_count.restype = _i
+lib.nsa_marching_cubes_count.argtypes = [_p, _u32, _u32, _u32, _f32, _p, _p, _p]
+lib.nsa_marching_cubes_emit.restype = _i
+lib.nsa_marching_cubes_emit.argtypes = [_p, _u32, _u32, _u32, _f32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _p, _u64, _u64, _p,
+                                        _p, _p, _p]
+EXPORTS += ["nsa_marching_cubes_workspace", "nsa_marching_cubes_count", "nsa_marching_cubes_emit"]

@@ -335,6 +335,7 @@ const char* nsa_strerror(int code) {
         case NSA_ELAUNCH: return "HIP kernel launch failed";
         case NSA_EBADARG: return "bad argument (null pointer or inconsistent sizes)";
         case NSA_EUNSUPPORTED_NET: return "fused render core: network shape outside the compiled set";
+        case NSA_EMESH_TOO_LARGE: return "marching cubes: the vertex or face count does not fit int32";
         default: return "unknown error";
     }
 }

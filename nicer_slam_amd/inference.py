@@ -3,13 +3,16 @@ evaluation on dense grids for mesh extraction.  Same kernels as the training pat
 
 Reference: utils.general.split_input / merge_output (code/utils/general.py:169-204), the vis loop of
 VolSDFTrainRunner.vis (code/training/volsdf_train.py:255-290), get_grid_uniform / get_surface_trace's grid evaluation
-(code/utils/plots.py:102-166).  Marching cubes / PNG / PLY writing stay with the caller (offline tooling, out of scope).
+(code/utils/plots.py:102-166), and the mesh that get_surface_trace extracts from that grid: marching cubes on the device
+(csrc/mesh_extract.hip), vertex colours from the fused colour kernels, a binary PLY writer (plots.py:87-155).
+PNG writing stays with the caller.
 """
 import ctypes
 
+import numpy as np
 import torch
 
-from ._native import lib, check
+from ._native import lib, check, PointsDesc
 from .fused.sampler import grid_desc, packed_sdf, precision_of, sdf_grid_desc, supported as fused_supported
 
 
@@ -101,3 +104,123 @@ def sdf_grid(model, resolution, grid_boundary=(-2.0, 2.0), stage="fine", chunk=1
         pts = torch.stack([ax[ix], ax[iy], ax[iz]], -1)
         out[lo:lo + flat.numel()] = sdf_values(model, pts, stage, chunk)
     return out.view(resolution, resolution, resolution).permute(1, 0, 2).contiguous()
+
+
+@torch.no_grad()
+def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Surface ``volume == level`` of a CUDA fp32 volume [nx, ny, nz] indexed (x, y, z) (what ``sdf_grid`` returns), on the device:
+    dict(verts [V,3] f32, normals [V,3] f32, faces [F,3] int32).  Inside is ``value < level``; a vertex sits at
+    ``origin + spacing * (sample index + t * axis)``; normals point towards increasing value; faces are oriented inside -> outside;
+    the order is canonical.  Replaces skimage.measure.marching_cubes + the origin shift (plots.py:128-136).
+    Offline inference: the call reads the two totals back to the host once (a synchronisation) to size the outputs."""
+    if not (volume.is_cuda and volume.dtype == torch.float32 and volume.dim() == 3):
+        raise ValueError("marching_cubes: needs a CUDA float32 volume [nx, ny, nz]")
+    vol = volume.contiguous()
+    nx, ny, nz = vol.shape
+    dev = vol.device
+    ws = torch.empty(max(1, lib.nsa_marching_cubes_workspace(nx, ny, nz)), dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    check(lib.nsa_marching_cubes_count(vol.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), totals.data_ptr(), st))
+    V, F = (int(v) for v in totals.cpu())
+    verts = torch.empty(V, 3, device=dev)
+    normals = torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    spc = (ctypes.c_float * 3)(*[float(v) for v in spacing])
+    check(lib.nsa_marching_cubes_emit(vol.data_ptr(), nx, ny, nz, float(level), org, spc, ws.data_ptr(), V, F,
+                                      verts.data_ptr() if V else None, normals.data_ptr() if V else None,
+                                      faces.data_ptr() if F else None, st))
+    return dict(verts=verts, normals=normals, faces=faces)
+
+
+@torch.no_grad()
+def vertex_colours(model, verts, normals, chunk=1 << 20):
+    """rgb [V,3] of the colour network at ``verts`` seen along ``-normals``: the COMBINE's "fine" outputs (sdf gradient and
+    feature) followed by the colour network with color_stage "highfreq" -- plots.py:137-147 -- through the fused kernels.
+    The vertices travel as one-sample rays (o = vertex, d = -normal, z = 0), for which the kernels' point o + 0 * d is o."""
+    from .fused.render import grid_desc, hl_size, packed_colour, supported as render_supported
+    from .fused.sampler import forward_pair_ok
+    if not (verts.is_cuda and render_supported(model)):
+        raise RuntimeError("vertex_colours: needs CUDA vertices and a model configuration covered by the fused kernels")
+    dev = verts.device
+    V = verts.shape[0]
+    out = torch.empty(V, 3, device=dev)
+    if V == 0:
+        return out
+    gc, keep_c = sdf_grid_desc(model, "coarse")
+    gf, keep_f = sdf_grid_desc(model, "fine")
+    gr, keep_r = grid_desc(model.rendering_network.encoding, model.rendering_network.divide_factor, 2, precision_of(model, "colour"))
+    pc, pf, pr = packed_sdf(model, "coarse"), packed_sdf(model, "fine"), packed_colour(model)
+    pair = forward_pair_ok(model)
+    if pair:
+        gcp, keep_cp = sdf_grid_desc(model, "coarse", "coarse_pair")
+        pcp = packed_sdf(model, "coarse", use="coarse_pair")
+    verts = verts.contiguous().float()
+    dirs = (-normals).contiguous().float()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    n_max = min(chunk, V)
+    z = torch.zeros(n_max, device=dev)
+    sdf = torch.empty(n_max, device=dev)
+    grad = torch.empty(n_max, 3, device=dev)
+    feat = torch.empty(hl_size(n_max), device=dev)
+    for lo in range(0, V, chunk):
+        n = min(chunk, V - lo)
+        pts = PointsDesc(verts[lo:].data_ptr(), dirs[lo:].data_ptr(), z.data_ptr(), None, n, 1, None)
+        if pair:
+            check(lib.nsa_sdfnet_forward_pair(ctypes.byref(pts), ctypes.byref(gcp), ctypes.byref(gf), pcp.data_ptr(), pf.data_ptr(),
+                                              sdf.data_ptr(), grad.data_ptr(), feat.data_ptr(), st))
+        else:
+            check(lib.nsa_sdfnet_forward(ctypes.byref(pts), ctypes.byref(gc), pc.data_ptr(), 0, sdf.data_ptr(), grad.data_ptr(),
+                                         feat.data_ptr(), st))
+            check(lib.nsa_sdfnet_forward(ctypes.byref(pts), ctypes.byref(gf), pf.data_ptr(), 1, sdf.data_ptr(), grad.data_ptr(),
+                                         feat.data_ptr(), st))
+        check(lib.nsa_colour_forward(ctypes.byref(pts), ctypes.byref(gr), pr.data_ptr(), grad.data_ptr(), feat.data_ptr(),
+                                     out[lo:].data_ptr(), None, st))
+    return out
+
+
+@torch.no_grad()
+def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22):
+    """get_surface_trace on the device (plots.py:87-155): ``sdf_grid`` -> ``marching_cubes`` with the grid's spacing and origin
+    -> (``color``) ``vertex_colours``.  Returns the marching_cubes dict, plus ``colors`` [V,3] in [0,1] when ``color`` is set.
+    A level outside the volume's range gives empty tensors (the reference prints "NO MESH" and writes nothing)."""
+    vol = sdf_grid(model, resolution, grid_boundary, stage, chunk)
+    ax = torch.linspace(grid_boundary[0], grid_boundary[1], resolution, dtype=torch.float64)     # get_grid_uniform's axis
+    step = float(ax[1] - ax[0]) if resolution > 1 else 1.0
+    mesh = marching_cubes(vol, level, (step,) * 3, (float(ax[0]),) * 3)
+    if color:
+        mesh["colors"] = vertex_colours(model, mesh["verts"], mesh["normals"], min(chunk, 1 << 20))
+    return mesh
+
+
+def write_ply(path, mesh):
+    """Binary little-endian PLY of a ``marching_cubes`` / ``extract_mesh`` dict: per vertex float x y z nx ny nz (+ uchar
+    red green blue when ``colors`` is present, round(255 * clamp(c, 0, 1))), faces as a uchar-counted int32 list."""
+    v = mesh["verts"].detach().cpu().numpy().astype("<f4")
+    n = mesh["normals"].detach().cpu().numpy().astype("<f4")
+    f = mesh["faces"].detach().cpu().numpy().astype("<i4")
+    col = mesh.get("colors")
+    vfields = [(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]
+    if col is not None:
+        vfields += [(k, "u1") for k in ("red", "green", "blue")]
+    vrec = np.empty(v.shape[0], dtype=vfields)
+    for i, k in enumerate(("x", "y", "z")):
+        vrec[k] = v[:, i]
+        vrec["n" + k] = n[:, i]
+    if col is not None:
+        c = np.rint(np.clip(col.detach().float().cpu().numpy(), 0, 1) * 255).astype(np.uint8)
+        for i, k in enumerate(("red", "green", "blue")):
+            vrec[k] = c[:, i]
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = f
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    head += [f"property float {k}" for k in ("x", "y", "z", "nx", "ny", "nz")]
+    if col is not None:
+        head += [f"property uchar {k}" for k in ("red", "green", "blue")]
+    head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
