@@ -577,6 +577,48 @@ int nsa_marching_cubes_emit(const float *vol, uint32_t nx, uint32_t ny, uint32_t
                             const float *spacing_host, void *workspace, uint64_t n_verts, uint64_t n_faces, float *verts,
                             float *normals, int32_t *faces, nsa_stream_t stream);
 
+/* ---- Section 8: mesh evaluation (exact nearest neighbours, surface sampling; DESIGN 4g, csrc/mesh_eval.hip) -------------- */
+
+/* Exact nearest neighbour, point cloud to point cloud.  targets[n_targets, 3] and queries[n_queries, 3] fp32, C-contiguous.
+ * For query q the answer is the target i with the smallest fp32
+ *     d2 = (dx * dx + dy * dy) + dz * dz,   dk = t_ik - q_k,   every operation rounded on its own (no FMA contraction),
+ * ties to the LOWEST index; dist = the correctly rounded fp32 square root of d2 (IEEE sqrtf).  Any fp32 brute force with this operation order reproduces
+ * (idx, dist) bit for bit.  A target with a non-finite coordinate is never returned; a non-finite query gives (-1, NaN).
+ * Radius: with max_dist < +inf a target is accepted only if d2 < (float)(max_dist * max_dist) -- strictly, as the radius search
+ * of open3d's KDTreeFlann::SearchHybrid inside registration_icp (eval_rec.py:197-203); a query with no accepted target gives
+ * (-1, +inf).  max_dist = +inf is the plain search (scipy cKDTree.query, eval_rec.py:18, :111, :172-186).
+ * The index is a uniform grid over the bulk of the targets with per-cell bounding boxes; it is built once and
+ * reused by every query on it.  Counts are below 2^31.  Nothing is allocated or synchronised; the index buffer belongs to the
+ * caller and must stay alive, and the targets unchanged, only while nsa_nn_build runs (the index holds its own copy). */
+
+/* bytes of the index buffer for n_targets (>= 1) targets; 0 for an invalid count */
+uint64_t nsa_nn_workspace(uint32_t n_targets);
+
+/* Build the index over targets into `index` (nsa_nn_workspace(n_targets) bytes, device, 256-byte aligned). */
+int nsa_nn_build(const float *targets, uint32_t n_targets, void *index, nsa_stream_t stream);
+
+/* idx[n_queries] int32, dist[n_queries] fp32 for queries against an index built by nsa_nn_build with the same n_targets.
+ * max_dist > 0 (+inf: no radius). */
+int nsa_nn_query(const void *index, uint32_t n_targets, const float *queries, uint32_t n_queries, double max_dist, int32_t *idx,
+                 float *dist, nsa_stream_t stream);
+
+/* Area-weighted surface sampling: restates trimesh.sample.sample_surface (eval_rec.py:158, :222, :225).  verts[n_verts, 3] fp32,
+ * faces[n_faces, 3] int32 (a face with an index outside [0, n_verts) has area 0).  Areas a_f = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz),
+ * c = (v1 - v0) x (v2 - v0) in float64; cum[f] = boff[b] + local[f] with local the sequential inclusive scan within blocks of
+ * 1024 faces and boff the sequential sum of the earlier block totals, so cum is non-decreasing; total = cum[F - 1].
+ * Sample s draws Philox4x32-10 with key = seed, counter = (s, 0, 0, 0) -> (c0, c1, c2, c3):
+ *   face_idx[s] = first f with cum[f] >= ((c0 >> 8) + 1) * 2^-24 * total   (u in (0, 1]: zero-area faces are never picked)
+ *   a = (c1 >> 8) * 2^-24, b = (c2 >> 8) * 2^-24 (fp32); when a + b > 1 (fp32): a = 1 - a, b = 1 - b
+ *   points[s] = (v0 + a * (v1 - v0)) + b * (v2 - v0), fp32, each operation rounded on its own.
+ * total_area (device, may be NULL) receives the total; when it is 0 or not finite the samples are meaningless and the caller
+ * rejects the mesh.  Nothing is allocated or synchronised; the workspace belongs to the caller. */
+
+/* bytes of workspace for n_faces (>= 1) faces; 0 for an invalid count */
+uint64_t nsa_surface_sample_workspace(uint32_t n_faces);
+
+int nsa_surface_sample(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, uint32_t n_samples,
+                       uint64_t seed, void *workspace, float *points, int32_t *face_idx, double *total_area, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,3 +284,15 @@ lib.nsa_marching_cubes_emit.restype = _i
 lib.nsa_marching_cubes_emit.argtypes = [_p, _u32, _u32, _u32, _f32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _p, _u64, _u64, _p,
                                         _p, _p, _p]
 EXPORTS += ["nsa_marching_cubes_workspace", "nsa_marching_cubes_count", "nsa_marching_cubes_emit"]
+
+lib.nsa_nn_workspace.restype = _u64
+lib.nsa_nn_workspace.argtypes = [_u32]
+lib.nsa_nn_build.restype = _i
+lib.nsa_nn_build.argtypes = [_p, _u32, _p, _p]
+lib.nsa_nn_query.restype = _i
+lib.nsa_nn_query.argtypes = [_p, _u32, _p, _u32, ctypes.c_double, _p, _p, _p]
+lib.nsa_surface_sample_workspace.restype = _u64
+lib.nsa_surface_sample_workspace.argtypes = [_u32]
+lib.nsa_surface_sample.restype = _i
+lib.nsa_surface_sample.argtypes = [_p, _u32, _p, _u32, _u32, _u64, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_nn_workspace", "nsa_nn_build", "nsa_nn_query", "nsa_surface_sample_workspace", "nsa_surface_sample"]

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "sdf_net.hpp"
+#include "radix_sort.hpp"
 
 namespace nsa {
 
@@ -551,6 +552,34 @@ static void radix_geometry(uint32_t P, uint32_t& nb, uint32_t& per_wave) {
     per_wave = (uint32_t)((((uint64_t)P + waves - 1) / waves + 63) / 64 * 64);
 }
 
+}  // extern "C"
+
+namespace nsa {
+
+// (declared in radix_sort.hpp: nsa_morton_order's passes, shared with mesh_eval.hip)
+void radix_argsort(uint32_t* const keys[2], uint32_t* tmp, uint32_t* order, uint32_t* counts, uint32_t P, uint32_t shift0,
+                   uint32_t passes, nsa_stream_t stream) {
+    RadixArgs a;
+    a.P = P;
+    radix_geometry(P, a.nb, a.per_wave);
+    a.counts = counts;
+    for (uint32_t i = 0; i < passes; ++i) {
+        uint32_t* v_out = ((passes - 1 - i) & 1u) ? tmp : order;
+        const uint32_t* v_in = i == 0 ? nullptr : (((passes - i) & 1u) ? tmp : order);
+        a.keys_in = keys[i & 1];
+        a.keys_out = i + 1 < passes ? keys[(i + 1) & 1] : nullptr;
+        a.vals_in = v_in;
+        a.vals_out = v_out;
+        a.shift = shift0 + 8 * i;
+        hipLaunchKernelGGL(k_radix_hist, dim3(a.nb), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(a.nb), dim3(256), 0, (hipStream_t)stream, a);
+    }
+}
+
+}  // namespace nsa
+
+extern "C" {
+
 uint64_t nsa_morton_order_workspace(uint32_t P) {
     uint32_t nb, per_wave;
     radix_geometry(P, nb, per_wave);
@@ -568,23 +597,8 @@ int nsa_morton_order(const nsa_points_t* pts, int32_t* order, uint32_t* workspac
     uint32_t* counts = workspace + 3ull * P;
     const int rc = nsa_morton_keys(pts, reinterpret_cast<int32_t*>(keys[0]), stream);
     if (rc != NSA_OK) return rc;
-    RadixArgs a;
-    a.P = P;
-    radix_geometry(P, a.nb, a.per_wave);
-    a.counts = counts;
-    const uint32_t passes = (key_bits + 7) / 8, shift0 = 30 - key_bits;
     launch_begin();
-    for (uint32_t i = 0; i < passes; ++i) {
-        uint32_t* v_out = ((passes - 1 - i) & 1u) ? tmp : reinterpret_cast<uint32_t*>(order);
-        const uint32_t* v_in = i == 0 ? nullptr : (((passes - i) & 1u) ? tmp : reinterpret_cast<uint32_t*>(order));
-        a.keys_in = keys[i & 1];
-        a.keys_out = i + 1 < passes ? keys[(i + 1) & 1] : nullptr;
-        a.vals_in = v_in;
-        a.vals_out = v_out;
-        a.shift = shift0 + 8 * i;
-        hipLaunchKernelGGL(k_radix_hist, dim3(a.nb), dim3(256), 0, (hipStream_t)stream, a);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(a.nb), dim3(256), 0, (hipStream_t)stream, a);
-    }
+    radix_argsort(keys, tmp, reinterpret_cast<uint32_t*>(order), counts, P, 30 - key_bits, (key_bits + 7) / 8, stream);
     return launch_end();
 }
 

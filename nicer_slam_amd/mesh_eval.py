@@ -1,0 +1,265 @@
+"""Reconstruction metrics on the device: what code/evaluation/eval_rec.py computes with scipy's cKDTree, open3d's ICP and
+trimesh's surface sampling.
+
+* ``NNIndex`` / ``nearest``: exact fp32 nearest neighbours (C ABI Section 8, csrc/mesh_eval.hip), ties to the lowest index.
+* ``sample_surface``: area-weighted surface samples from the engine's Philox stream (trimesh.sample.sample_surface).
+* ``icp_point_to_point``: open3d's registration_icp with TransformationEstimationPointToPoint and default criteria.
+* ``mesh_metrics``: calc_3d_metric + calc_normal_consistency (eval_rec.py:143-166, 207-236) from one ICP and one sample set.
+* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply``: the reference's printout.
+
+Reductions over the distance arrays (means, counts, ICP's centroids and cross-covariance) run in torch float64: they are small
+and deterministic.  There is no CPU path: a missing GPU is an error.
+"""
+import argparse
+import math
+
+import numpy as np
+import torch
+
+from ._native import lib, check
+
+F_THRESHOLDS = (0.010, 0.015, 0.020)       # np.linspace(1/1000, 1, 1000)[[9, 14, 19]] of eval_pointcloud
+COMPLETION_RATIO_THRESHOLD = 0.05          # completion_ratio's dist_th (eval_rec.py:168)
+
+
+def _points(x, name):
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise ValueError(f"{name}: needs a CUDA tensor [n, 3]")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: needs shape [n, 3], got {tuple(x.shape)}")
+    if x.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 points")
+    return x.detach().float().contiguous()
+
+
+class NNIndex:
+    """Exact nearest-neighbour index over fp32 targets [n, 3] on the device, built once and queried any number of times.
+    The index keeps its own copy of the targets (sorted by grid cell); the tensor passed in may change afterwards."""
+
+    @torch.no_grad()
+    def __init__(self, targets):
+        t = _points(targets, "NNIndex")
+        self.n = t.shape[0]
+        if self.n == 0:
+            raise ValueError("NNIndex: no targets")
+        self.device = t.device
+        self.buf = torch.empty(lib.nsa_nn_workspace(self.n), dtype=torch.uint8, device=t.device)
+        check(lib.nsa_nn_build(t.data_ptr(), self.n, self.buf.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
+
+    @torch.no_grad()
+    def query(self, queries, max_dist=math.inf):
+        """(dist [m] fp32, idx [m] int64): the nearest target of each query, ties to the lowest index.  With a finite
+        ``max_dist`` only targets with d2 < fp32(max_dist^2) count (open3d's hybrid search); none gives (+inf, -1).
+        A non-finite query gives (NaN, -1)."""
+        q = _points(queries, "NNIndex.query")
+        if q.device != self.device:
+            raise ValueError("NNIndex.query: queries on another device than the index")
+        if not max_dist > 0:
+            raise ValueError("NNIndex.query: max_dist must be > 0")
+        m = q.shape[0]
+        idx = torch.empty(m, dtype=torch.int32, device=q.device)
+        dist = torch.empty(m, dtype=torch.float32, device=q.device)
+        if m:
+            check(lib.nsa_nn_query(self.buf.data_ptr(), self.n, q.data_ptr(), m, float(max_dist), idx.data_ptr(), dist.data_ptr(),
+                                   torch.cuda.current_stream(q.device).cuda_stream))
+        return dist, idx.long()
+
+    def grid(self):
+        """(lo [3], cell size [3], cells per axis [3], per-cell point counts [Rx, Ry, Rz]) of the built grid (host copies;
+        a synchronisation -- for measurements, not for the query path)."""
+        head = self.buf[:64].cpu().numpy()
+        lo, h = head[:12].view(np.float32), head[12:24].view(np.float32)
+        R = head[36:48].view(np.uint32).astype(np.int64)
+        ncells = int(R.prod())
+        start = self.buf[256:256 + 4 * (ncells + 1)].view(torch.int32).long()
+        counts = (start[1:] - start[:-1]).view(*R.tolist())
+        return lo.copy(), h.copy(), R, counts
+
+
+@torch.no_grad()
+def nearest(queries, targets, max_dist=math.inf):
+    """(dist, idx) of the nearest target of each query (``NNIndex(targets).query(queries, max_dist)``)."""
+    return NNIndex(targets).query(queries, max_dist)
+
+
+@torch.no_grad()
+def sample_surface(verts, faces, n, seed=0):
+    """(points [n, 3] fp32, face_idx [n] int64): ``n`` area-weighted samples of the triangle mesh, from Philox4x32-10 with
+    key = seed and counter = sample index (trimesh.sample.sample_surface, restated in include/nicer_slam_amd.h Section 8).
+    Raises ValueError for a mesh without faces or with zero (or non-finite) total area."""
+    v = _points(verts, "sample_surface")
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("sample_surface: faces must be a CUDA tensor [F, 3]")
+    f = faces.to(torch.int32).contiguous()
+    V, F = v.shape[0], f.shape[0]
+    if V == 0 or F == 0:
+        raise ValueError("sample_surface: empty mesh")
+    if F >= 1 << 31 or n >= 1 << 31 or n < 0:
+        raise ValueError("sample_surface: count out of range")
+    if int(f.min()) < 0 or int(f.max()) >= V:
+        raise ValueError("sample_surface: face index out of range")
+    ws = torch.empty(lib.nsa_surface_sample_workspace(F), dtype=torch.uint8, device=v.device)
+    pts = torch.empty(n, 3, device=v.device)
+    fidx = torch.empty(n, dtype=torch.int32, device=v.device)
+    total = torch.empty(1, dtype=torch.float64, device=v.device)
+    check(lib.nsa_surface_sample(v.data_ptr(), V, f.data_ptr(), F, n, int(seed) & (2 ** 64 - 1), ws.data_ptr(),
+                                 pts.data_ptr() if n else None, fidx.data_ptr() if n else None, total.data_ptr(),
+                                 torch.cuda.current_stream(v.device).cuda_stream))
+    a = float(total)
+    if not (a > 0 and math.isfinite(a)):
+        raise ValueError(f"sample_surface: total area {a} (zero-area or non-finite mesh)")
+    return pts, fidx.long()
+
+
+def _transform(p, T):
+    """p [n, 3] float64 -> R p + t, as ((R0 x + R1 y) + R2 z) + t with every operation rounded on its own."""
+    R, t = T[:3, :3], T[:3, 3]
+    cols = [((R[k, 0] * p[:, 0] + R[k, 1] * p[:, 1]) + R[k, 2] * p[:, 2]) + t[k] for k in range(3)]
+    return torch.stack(cols, -1)
+
+
+def _kabsch(src, tgt):
+    """Rigid 4x4 (no scale) minimising |R src + t - tgt| (Eigen::umeyama without scaling, as open3d's
+    TransformationEstimationPointToPoint); float64 sums on the device, the 3x3 SVD on the host."""
+    ms, mt = src.mean(0), tgt.mean(0)
+    cov = ((tgt - mt).T @ (src - ms)) / src.shape[0]
+    sums = torch.cat([ms, mt, cov.reshape(-1)]).cpu().numpy()
+    ms, mt, cov = sums[:3], sums[3:6], sums[6:].reshape(3, 3)
+    U, _, Vt = np.linalg.svd(cov)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1.0
+    R = U @ S @ Vt
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = mt - R @ ms
+    return T
+
+
+@torch.no_grad()
+def icp_point_to_point(source, target, max_corr=0.1, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, index=None):
+    """open3d's registration_icp(source, target, max_corr, init, TransformationEstimationPointToPoint()) with default
+    ICPConvergenceCriteria (eval_rec.py:190-204).  Correspondences: each source point's nearest target with d2 <
+    fp32(max_corr^2); fitness = correspondences / source points; inlier_rmse = sqrt(mean of the squared correspondence
+    distances) (both 0 without correspondences).  Each iteration left-multiplies the Kabsch update onto the transformation and
+    moves the float64 source by it; it stops when |d fitness| < rel_fitness and |d rmse| < rel_rmse, or after max_iter.
+    Returns dict(transformation [4,4] float64 numpy, fitness, inlier_rmse, iterations).  ``index``: a prebuilt NNIndex of target."""
+    src = _points(source, "icp_point_to_point").double()
+    if src.shape[0] == 0:
+        raise ValueError("icp_point_to_point: empty source")
+    tgt = _points(target, "icp_point_to_point").double()
+    index = index if index is not None else NNIndex(target)
+    T = np.eye(4) if init is None else np.asarray(init, dtype=np.float64).reshape(4, 4).copy()
+    cur = _transform(src, torch.from_numpy(T).to(src.device))
+
+    def evaluate(p):
+        d, i = index.query(p.float(), max_corr)
+        ok = i >= 0
+        k = int(ok.sum())
+        if k == 0:
+            return 0.0, 0.0, ok, i
+        d64 = d[ok].double()
+        return k / p.shape[0], math.sqrt(float((d64 * d64).sum()) / k), ok, i
+
+    fit, rmse, ok, i = evaluate(cur)
+    it = 0
+    for it in range(max_iter):
+        if int(ok.sum()) == 0:
+            upd = np.eye(4)
+        else:
+            upd = _kabsch(cur[ok], tgt[i[ok]])
+        T = upd @ T
+        cur = _transform(cur, torch.from_numpy(upd).to(src.device))
+        prev = (fit, rmse)
+        fit, rmse, ok, i = evaluate(cur)
+        if abs(prev[0] - fit) < rel_fitness and abs(prev[1] - rmse) < rel_rmse:
+            break
+    return dict(transformation=T, fitness=fit, inlier_rmse=rmse, iterations=it + 1 if max_iter > 0 else 0)
+
+
+def _face_normals(v, f):
+    """unit face normals [F, 3] float64 (trimesh's face_normals; sampled faces never have zero area)"""
+    v = v.double()
+    e1, e2 = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+    n = torch.linalg.cross(e1, e2)
+    return n / n.norm(dim=-1, keepdim=True).clamp_min(1e-300)
+
+
+def _as_cuda_mesh(m, device):
+    v = torch.as_tensor(np.asarray(m["verts"].cpu() if torch.is_tensor(m["verts"]) else m["verts"]), dtype=torch.float32)
+    f = torch.as_tensor(np.asarray(m["faces"].cpu() if torch.is_tensor(m["faces"]) else m["faces"]), dtype=torch.int64)
+    return v.reshape(-1, 3).to(device), f.reshape(-1, 3).to(device)
+
+
+@torch.no_grad()
+def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda"):
+    """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
+    ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
+    reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
+    ``seed`` for rec, ``seed + 1`` for gt).  Returns, in scene units: accuracy, completion, completion ratio (< 0.05),
+    normals (mean |dot| of the face normals, both directions), chamfer-L1, chamfer-L2, f-score / f-score-15 / f-score-20
+    (thresholds 0.010 / 0.015 / 0.020, <=), and transformation / icp fitness / icp rmse.
+    Departure: one ICP and one sample set per mesh serve every metric (the reference draws and aligns twice)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("mesh_metrics: needs a GPU")
+    rv, rf = _as_cuda_mesh(rec, device)
+    gv, gf = _as_cuda_mesh(gt, device)
+    if rv.shape[0] == 0 or rf.shape[0] == 0:
+        raise ValueError("mesh_metrics: empty reconstruction")
+    if gv.shape[0] == 0 or gf.shape[0] == 0:
+        raise ValueError("mesh_metrics: empty ground truth")
+    rv, gv = (rv.double() / scale).float(), (gv.double() / scale).float()
+    T, fit, rmse = np.eye(4), None, None
+    if align:
+        icp = icp_point_to_point(rv, gv, 0.1)
+        T, fit, rmse = icp["transformation"], icp["fitness"], icp["inlier_rmse"]
+        rv = _transform(rv.double(), torch.from_numpy(T).to(rv.device)).float()
+    rp, ri = sample_surface(rv, rf, n_points, seed)
+    gp, gi = sample_surface(gv, gf, n_points, seed + 1)
+    out = metrics_from_samples(rp, _face_normals(rv, rf)[ri], gp, _face_normals(gv, gf)[gi])
+    out.update({"transformation": T, "icp fitness": fit, "icp rmse": rmse})
+    return out
+
+
+@torch.no_grad()
+def metrics_from_samples(rec_pts, rec_normals, gt_pts, gt_normals):
+    """eval_pointcloud / calc_3d_metric arithmetic on two sample sets (fp32 points, float64 unit normals)."""
+    d_acc, i_acc = nearest(rec_pts, gt_pts)          # accuracy: reconstruction -> ground truth
+    d_com, i_com = nearest(gt_pts, rec_pts)          # completion: ground truth -> reconstruction
+    acc, com = d_acc.double(), d_com.double()
+    n_acc = (gt_normals[i_acc] * rec_normals).sum(-1).abs().mean()
+    n_com = (rec_normals[i_com] * gt_normals).sum(-1).abs().mean()
+    out = {"accuracy": float(acc.mean()), "completion": float(com.mean()),
+           "completion ratio": float((com < COMPLETION_RATIO_THRESHOLD).double().mean()),
+           "normals": float(0.5 * n_com + 0.5 * n_acc),
+           "chamfer-L1": float(0.5 * (com.mean() + acc.mean())),
+           "chamfer-L2": float(0.5 * ((com * com).mean() + (acc * acc).mean()))}
+    for key, th in zip(("f-score", "f-score-15", "f-score-20"), F_THRESHOLDS):
+        p, r = float((acc <= th).double().mean()), float((com <= th).double().mean())
+        out[key] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    return out
+
+
+def main(argv=None):
+    from .inference import read_ply
+    ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_eval", description=__doc__.splitlines()[0])
+    ap.add_argument("rec")
+    ap.add_argument("gt")
+    ap.add_argument("--no-align", action="store_true")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--points", type=int, default=200000)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale)
+    print("accuracy: ", m["accuracy"] * 100, "cm")
+    print("completion: ", m["completion"] * 100, "cm")
+    print("completion ratio: ", m["completion ratio"] * 100, "%")
+    print("Normal Consistency", f"{m['normals'] * 100:.4f} %")
+    for k in ("chamfer-L1", "chamfer-L2", "f-score", "f-score-15", "f-score-20", "icp fitness", "icp rmse"):
+        print(f"{k}: {m[k]}")
+    print("transformation:\n" + np.array2string(m["transformation"], precision=8))
+    return m
+
+
+if __name__ == "__main__":
+    main()
