@@ -619,6 +619,33 @@ uint64_t nsa_surface_sample_workspace(uint32_t n_faces);
 int nsa_surface_sample(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, uint32_t n_samples,
                        uint64_t seed, void *workspace, float *points, int32_t *face_idx, double *total_area, nsa_stream_t stream);
 
+/* ---- Section 9: rendering metrics (PSNR and SSIM of image pairs in float64; DESIGN 4h, csrc/image_metrics.hip) ------------ */
+
+/* pred[n_images, height * width, 3] and gt[same] fp32, C-contiguous, pixel (r, c) at r * width + c -- the layout of rgb_values
+ * and ground_truth["rgb"].  Per image, the SSIM of code/utils/SSIM with size_average=True (as rend_util.get_ssim calls it) and
+ * the sum of squared errors of rend_util.get_psnr, every value converted to float64 before any arithmetic:
+ *   window   g_k = (float)exp(-(k - 5)^2 / 4.5), k = 0..10, each divided (fp32) by their correctly rounded fp32 sum;
+ *            w_ij = g_i * g_j EXACTLY (float64; the reference rounds it to fp32, which moves SSIM by < 4e-7)
+ *   moments  per channel, zero padding of 5 on every side: mu_x = sum w x, mu_y = sum w y, e_xx = sum w x^2,
+ *            e_yy = sum w y^2, e_xy = sum w x y (float64)
+ *   map      ((2 mu_x mu_y + C1)(2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2)),  C1 = 1e-4, C2 = 9e-4,
+ *            s_xx = e_xx - mu_x^2, s_yy = e_yy - mu_y^2, s_xy = e_xy - mu_x mu_y, each operation rounded on its own
+ *   ssim_mean[i]  = (sum of the map over the 3 channels and height * width pixels) / (3 * height * width)   (float64)
+ *   sq_err_sum[i] = sum over the 3 * height * width values of (x - y)^2   (float64; PSNR = -10 log10(sq_err_sum / count))
+ *   ssim_map[i, r, c] (optional, fp32 [n_images, height, width]) = the float64 mean of the three channels' map values, rounded.
+ * An image scored against itself gives ssim_mean = 1 and sq_err_sum = 0 exactly.  Any non-finite value in either image of a pair
+ * makes both of its outputs NaN (the map is NaN within 5 pixels of it).  The sums are taken in a fixed order: results are
+ * bit-reproducible and do not depend on the other images of the batch.  n_images * height * width * 3 < 2^31.  Nothing is
+ * allocated or synchronised; the workspace belongs to the caller.  Together these replace rend_util.get_psnr / get_ssim
+ * (code/evaluation/eval_rendering.py). */
+
+/* bytes of workspace for n_images images of height x width; 0 for invalid sizes */
+uint64_t nsa_image_metrics_workspace(uint32_t n_images, uint32_t height, uint32_t width);
+
+/* ssim_mean[n_images], sq_err_sum[n_images] (device, float64); ssim_map may be NULL (no map). */
+int nsa_image_metrics(const float *pred, const float *gt, uint32_t n_images, uint32_t height, uint32_t width, void *workspace,
+                      double *ssim_mean, double *sq_err_sum, float *ssim_map, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,3 +296,9 @@ lib.nsa_surface_sample_workspace.argtypes = [_u32]
 lib.nsa_surface_sample.restype = _i
 lib.nsa_surface_sample.argtypes = [_p, _u32, _p, _u32, _u32, _u64, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_nn_workspace", "nsa_nn_build", "nsa_nn_query", "nsa_surface_sample_workspace", "nsa_surface_sample"]
+
+lib.nsa_image_metrics_workspace.restype = _u64
+lib.nsa_image_metrics_workspace.argtypes = [_u32, _u32, _u32]
+lib.nsa_image_metrics.restype = _i
+lib.nsa_image_metrics.argtypes = [_p, _p, _u32, _u32, _u32, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_image_metrics_workspace", "nsa_image_metrics"]
