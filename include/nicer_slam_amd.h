@@ -646,6 +646,58 @@ uint64_t nsa_image_metrics_workspace(uint32_t n_images, uint32_t height, uint32_
 int nsa_image_metrics(const float *pred, const float *gt, uint32_t n_images, uint32_t height, uint32_t width, void *workspace,
                       double *ssim_mean, double *sq_err_sum, float *ssim_map, nsa_stream_t stream);
 
+/* ---- Section 10: depth fusion into a dense TSDF volume (csrc/tsdf_fuse.hip) ---------------------------------- */
+
+/* A dense truncated-signed-distance volume over an axis-aligned box: nx * ny * nz voxels, voxel (x, y, z) at
+ * i = (x * ny + y) * nz + z -- the layout nsa_marching_cubes_* reads -- in three device arrays owned by the caller:
+ * tsdf[nx * ny * nz] and weight[same] fp32, and colour, fp32, PLANAR: channel c of voxel i at colour[c * nx * ny * nz + i]
+ * (may be NULL: no colour).  Planar because the integration kernel runs its lanes along z: every load and store of the state
+ * is then one contiguous run of 4-byte words per wave, which the interleaved form (12-byte stride) is not.  A fresh volume is
+ * all zeros (weight 0 = never observed).  nx * ny * nz <= 2^31.  The centre of voxel (x, y, z) is
+ *   c_a = origin_a + voxel_length * ((float)i_a + 0.5f),   a = x, y, z. */
+typedef struct nsa_tsdf_volume {
+    float *tsdf, *weight, *colour;
+    uint32_t nx, ny, nz;
+    float origin[3];     /* the box's lower corner (NOT the centre of voxel 0), finite                                    */
+    float voxel_length;  /* finite, > 0                                                                                   */
+    float sdf_trunc;     /* finite, > 0, and 1.0f / sdf_trunc finite                                                      */
+} nsa_tsdf_volume_t;
+
+/* Integrate n depth frames IN ORDER k = 0 .. n-1: the running average of the projective truncated signed distance, the rule of
+ * uniform TSDF integration (open3d's ScalableTSDFVolume::Integrate as preprocess/get_mesh_7scenes.py drives it, restated; this
+ * statement is the contract).  depth[n, H, W] fp32, z-depth along the camera axis in the volume's units; rgb[n, H * W, 3] fp32
+ * (required when the volume has colour, ignored otherwise, may then be NULL); w2c[n, 3, 4] fp32 world-to-camera rows
+ * (R_r0 R_r1 R_r2 t_r); K[n or 1][4] = (fx, fy, cx, cy) fp32, one per frame when K_per_frame is non-zero, else one for all.
+ * All fp32, every operation rounded on its own (no FMA contraction), IEEE division.  Per voxel and frame k:
+ *   p_r  = ((R_r0 * c_x + R_r1 * c_y) + R_r2 * c_z) + t_r,   r = 0, 1, 2                 (camera frame)
+ *   skip unless p_2 > 0
+ *   u_f  = ((p_0 * fx) / p_2 + cx) + 0.5f ;  v_f = ((p_1 * fy) / p_2 + cy) + 0.5f        (pixel centres at integer (u, v))
+ *   skip unless 0 <= u_f < (float)W and 0 <= v_f < (float)H ;  u = (int)u_f, v = (int)v_f
+ *   d    = depth[k, v, u] ;  skip unless d > 0 and d <= depth_trunc                      (0, negative, NaN: no measurement)
+ *   sdf  = d - p_2 ;  skip unless sdf > -sdf_trunc
+ *   x    = sdf * inv,  inv = 1.0f / sdf_trunc ;  t = x < 1.0f ? x : 1.0f
+ *   den  = weight + 1.0f
+ *   tsdf = (tsdf * weight + t) / den ;  colour_c = (colour_c * weight + rgb[k, v * W + u, c]) / den ;  weight = den
+ * ("skip" leaves the voxel's state untouched by that frame; a comparison with a NaN operand is false.)  Every voxel coordinate
+ * is formed from its index as above, so the result does not depend on how the kernel maps threads to voxels, and n frames in
+ * one call equal n calls of one frame bit for bit.  The kernel keeps a voxel's state in registers over the whole batch (one
+ * read and one write of the state per call) and skips, per brick of voxels, the frames whose frustum or depth range the brick
+ * cannot meet; that test is conservative and never changes a result.
+ * H, W < 2^24; depth_trunc > 0 (+inf: none).  frame_zmax: 33 * n floats of device workspace (the largest accepted depth of
+ * each frame and its 32 partial maxima, written by two small kernels first).  n = 0 is a no-op.  Nothing is allocated or synchronised.
+ * replaces the integrate loop of preprocess/get_mesh_7scenes.py (open3d ScalableTSDFVolume) on a dense box. */
+int nsa_tsdf_integrate(const nsa_tsdf_volume_t *vol, const float *depth, const float *rgb, const float *w2c, const float *K,
+                       int K_per_frame, uint32_t n, uint32_t H, uint32_t W, float depth_trunc, float *frame_zmax,
+                       nsa_stream_t stream);
+
+/* Colour of the volume at m arbitrary points (mesh vertices): points[m, 3] -> out[m, 3], fp32, every operation rounded on its own.
+ *   g_a = (p_a - origin_a) / voxel_length - 0.5f ;  b_a = floorf(g_a) ;  f_a = g_a - b_a        (voxel-centre grid coordinate)
+ *   corner (dx, dy, dz) in {0, 1}^3 is voxel (b_x + dx, b_y + dy, b_z + dz) with
+ *   w = (wx * wy) * wz,  wa = da ? f_a : 1.0f - f_a ;  it SURVIVES when it lies inside the volume and its weight > 0
+ *   s = sum of w, a_c = sum of w * colour_c over the surviving corners, added in the order dx outermost, dz innermost
+ *   out_c = a_c / s when s > 0, else 0 (also for a point with a non-finite coordinate or outside every cell). */
+int nsa_tsdf_sample_colour(const nsa_tsdf_volume_t *vol, const float *points, uint64_t m, float *out, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

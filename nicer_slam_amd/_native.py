@@ -302,3 +302,17 @@ lib.nsa_image_metrics_workspace.argtypes = [_u32, _u32, _u32]
 lib.nsa_image_metrics.restype = _i
 lib.nsa_image_metrics.argtypes = [_p, _p, _u32, _u32, _u32, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_image_metrics_workspace", "nsa_image_metrics"]
+
+
+class TsdfVolumeDesc(ctypes.Structure):
+    """nsa_tsdf_volume_t"""
+    _fields_ = [("tsdf", _p), ("weight", _p), ("colour", _p), ("nx", _u32), ("ny", _u32), ("nz", _u32), ("origin", _f32 * 3),
+                ("voxel_length", _f32), ("sdf_trunc", _f32)]
+
+
+_tp = ctypes.POINTER(TsdfVolumeDesc)
+lib.nsa_tsdf_integrate.restype = _i
+lib.nsa_tsdf_integrate.argtypes = [_tp, _p, _p, _p, _p, _i, _u32, _u32, _u32, _f32, _p, _p]
+lib.nsa_tsdf_sample_colour.restype = _i
+lib.nsa_tsdf_sample_colour.argtypes = [_tp, _p, _u64, _p, _p]
+EXPORTS += ["nsa_tsdf_integrate", "nsa_tsdf_sample_colour"]
