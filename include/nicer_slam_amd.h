@@ -698,6 +698,58 @@ int nsa_tsdf_integrate(const nsa_tsdf_volume_t *vol, const float *depth, const f
  *   out_c = a_c / s when s > 0, else 0 (also for a point with a non-finite coordinate or outside every cell). */
 int nsa_tsdf_sample_colour(const nsa_tsdf_volume_t *vol, const float *points, uint64_t m, float *out, nsa_stream_t stream);
 
+/* ---- Section 11: mesh components (connected components of a triangle mesh and their statistics; DESIGN 4j, csrc/mesh_clean.hip) - */
+
+/* Labelling.  faces[n_faces, 3] int32 over n_verts vertices; n_verts, n_faces < 2^31.  A face is VALID when its three indices lie
+ * in [0, n_verts); a valid face connects its three vertices (a degenerate one, (a, a, b), too); an invalid face connects nothing.
+ * A component is an equivalence class of vertices under "used by a common valid face", closed transitively, and its LABEL is
+ * the smallest vertex index in it.  Connectivity is by index only: coordinates play no part, and unwelded duplicates are
+ * different vertices (trimesh with process=False, as eval_rec.py loads meshes).
+ *   vertex_label[n_verts]  the label of the vertex's component, -1 for a vertex no valid face uses
+ *   face_label[n_faces]    the label of the face's vertices, -1 for an invalid face
+ *   totals[3]              (uint64, device) {components, referenced vertices, status}; the caller reads them once to size the
+ *                          statistics, as it reads the totals of nsa_marching_cubes_count
+ * The outputs are a function of the face list alone.  Inside, a lock-free union-find reaches the fixed point with compare-and-swap
+ * (parent[x] <= x throughout, larger root hooked under smaller), so atomics are used but decide nothing in the output.  Every
+ * device loop also has a step cap (a walk to the root: n_verts steps; hook retries: n_verts); a cap that trips sets a bit of
+ * status (1: walk, 2: hook) and the labels are then meaningless.  status is 0 for every input unless the implementation is
+ * wrong; the entry point does not synchronise, so the caller sees it when it reads the totals.
+ * Departure from trimesh's split (code/utils/viz.py:136-141), which joins faces that share an EDGE: here faces that share a
+ * VERTEX are joined, so a component here is a union of trimesh's; the two agree on manifold meshes.
+ * n_verts = n_faces = 0 is a no-op that returns 0 and launches nothing.  n_faces = 0 with n_verts > 0 writes every
+ * vertex_label = -1 and totals = {0, 0, 0}.  Nothing is allocated or synchronised; the workspace belongs to the caller. */
+
+/* bytes of workspace for n_verts (>= 1) vertices; 0 for an invalid count */
+uint64_t nsa_mesh_components_workspace(uint32_t n_verts);
+
+int nsa_mesh_components(const int32_t *faces, uint32_t n_faces, uint32_t n_verts, void *workspace, int32_t *vertex_label,
+                        int32_t *face_label, uint64_t *totals, nsa_stream_t stream);
+
+/* Statistics, after nsa_mesh_components on the same mesh, with n_components = totals[0] (<= n_faces).  The components in
+ * ascending label order have RANK c = 0 .. n_components - 1:
+ *   label[C] int32      the label of component c
+ *   n_faces[C] int32    its valid faces
+ *   n_verts[C] int32    its vertices
+ *   area[C] float64     the sum of its face areas a_f = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz) of Section 8 (the same device
+ *                       function); a face that touches a vertex with a non-finite coordinate counts 0
+ *   lo[C, 3], hi[C, 3]  fp32 minimum / maximum of its vertices per axis, a non-finite coordinate skipped (per axis); -0 orders
+ *                       below +0; (+inf, -inf) when none is finite
+ *   vertex_comp[n_verts], face_comp[n_faces] int32   the rank of the element's component, -1 where its label is -1
+ * Order of the area sum: the faces are argsorted stably by rank (equal ranks keep their index order); within each aligned block
+ * of 1024 sorted positions the run of a component is summed left to right from 0.0; a component's total is its first run plus
+ * the runs at the heads of the following blocks, added in block order.  Counts and boxes are integer sums / minima / maxima
+ * (the box on an order-preserving integer image of the fp32 value) and do not depend on any order: every output is
+ * bit-reproducible.  A count other than the labelling's gives -1 ranks for the components past it and never writes out of
+ * bounds.  n_components = 0 writes only the two rank arrays.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace; 0 for invalid counts (n_verts = 0, a count >= 2^31, n_components > n_faces or > n_verts) */
+uint64_t nsa_mesh_component_stats_workspace(uint32_t n_verts, uint32_t n_faces, uint32_t n_components);
+
+int nsa_mesh_component_stats(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                             const int32_t *vertex_label, const int32_t *face_label, uint32_t n_components, void *workspace,
+                             int32_t *label, int32_t *n_faces_out, int32_t *n_verts_out, double *area, float *lo, float *hi,
+                             int32_t *vertex_comp, int32_t *face_comp, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -316,3 +316,14 @@ lib.nsa_tsdf_integrate.argtypes = [_tp, _p, _p, _p, _p, _i, _u32, _u32, _u32, _f
 lib.nsa_tsdf_sample_colour.restype = _i
 lib.nsa_tsdf_sample_colour.argtypes = [_tp, _p, _u64, _p, _p]
 EXPORTS += ["nsa_tsdf_integrate", "nsa_tsdf_sample_colour"]
+
+lib.nsa_mesh_components_workspace.restype = _u64
+lib.nsa_mesh_components_workspace.argtypes = [_u32]
+lib.nsa_mesh_components.restype = _i
+lib.nsa_mesh_components.argtypes = [_p, _u32, _u32, _p, _p, _p, _p, _p]
+lib.nsa_mesh_component_stats_workspace.restype = _u64
+lib.nsa_mesh_component_stats_workspace.argtypes = [_u32, _u32, _u32]
+lib.nsa_mesh_component_stats.restype = _i
+lib.nsa_mesh_component_stats.argtypes = [_p, _u32, _p, _u32, _p, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_components_workspace", "nsa_mesh_components", "nsa_mesh_component_stats_workspace",
+            "nsa_mesh_component_stats"]

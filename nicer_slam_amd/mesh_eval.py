@@ -3,9 +3,12 @@ trimesh's surface sampling.
 
 * ``NNIndex`` / ``nearest``: exact fp32 nearest neighbours (C ABI Section 8, csrc/mesh_eval.hip), ties to the lowest index.
 * ``sample_surface``: area-weighted surface samples from the engine's Philox stream (trimesh.sample.sample_surface).
-* ``icp_point_to_point``: open3d's registration_icp with TransformationEstimationPointToPoint and default criteria.
-* ``mesh_metrics``: calc_3d_metric + calc_normal_consistency (eval_rec.py:143-166, 207-236) from one ICP and one sample set.
-* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply``: the reference's printout.
+* ``icp_point_to_point``: open3d's registration_icp with TransformationEstimationPointToPoint and default criteria;
+  ``with_scaling`` estimates a scale as well (CloudCompare's -ICP -ADJUST_SCALE, eval_rec.py:274).
+* ``mesh_metrics``: calc_3d_metric + calc_normal_consistency (eval_rec.py:143-166, 207-236) from one ICP and one sample set,
+  optionally after the similarity of the trajectory evaluation and the removal of stray components (eval_rec.py:259-272,
+  nicer_slam_amd/mesh_clean.py).
+* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale]``: the reference's printout.
 
 Reductions over the distance arrays (means, counts, ICP's centroids and cross-covariance) run in torch float64: they are small
 and deterministic.  There is no CPU path: a missing GPU is an error.
@@ -118,18 +121,27 @@ def _transform(p, T):
     return torch.stack(cols, -1)
 
 
-def _kabsch(src, tgt):
-    """Rigid 4x4 (no scale) minimising |R src + t - tgt| (Eigen::umeyama without scaling, as open3d's
-    TransformationEstimationPointToPoint); float64 sums on the device, the 3x3 SVD on the host."""
+def _kabsch(src, tgt, with_scaling=False):
+    """4x4 minimising |c R src + t - tgt| (Eigen::umeyama, as open3d's TransformationEstimationPointToPoint): rigid (c = 1)
+    unless ``with_scaling``, then c = trace(D S) / mean |src - mean src|^2 with D the singular values of the cross-covariance.
+    float64 sums on the device, the 3x3 SVD on the host."""
     ms, mt = src.mean(0), tgt.mean(0)
     cov = ((tgt - mt).T @ (src - ms)) / src.shape[0]
-    sums = torch.cat([ms, mt, cov.reshape(-1)]).cpu().numpy()
-    ms, mt, cov = sums[:3], sums[3:6], sums[6:].reshape(3, 3)
-    U, _, Vt = np.linalg.svd(cov)
+    parts = [ms, mt, cov.reshape(-1)]
+    if with_scaling:
+        ds = src - ms
+        parts.append(((ds * ds).sum() / src.shape[0]).reshape(1))
+    sums = torch.cat(parts).cpu().numpy()
+    ms, mt, cov = sums[:3], sums[3:6], sums[6:15].reshape(3, 3)
+    U, D, Vt = np.linalg.svd(cov)
     S = np.eye(3)
     if np.linalg.det(U) * np.linalg.det(Vt) < 0:
         S[2, 2] = -1.0
     R = U @ S @ Vt
+    if with_scaling:
+        if not sums[15] > 0:
+            raise ValueError("icp_point_to_point: the matched source points coincide; no scale can be estimated")
+        R = ((D[0] * S[0, 0] + D[1] * S[1, 1]) + D[2] * S[2, 2]) / sums[15] * R
     T = np.eye(4)
     T[:3, :3] = R
     T[:3, 3] = mt - R @ ms
@@ -137,12 +149,15 @@ def _kabsch(src, tgt):
 
 
 @torch.no_grad()
-def icp_point_to_point(source, target, max_corr=0.1, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, index=None):
+def icp_point_to_point(source, target, max_corr=0.1, init=None, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, index=None,
+                       with_scaling=False):
     """open3d's registration_icp(source, target, max_corr, init, TransformationEstimationPointToPoint()) with default
     ICPConvergenceCriteria (eval_rec.py:190-204).  Correspondences: each source point's nearest target with d2 <
     fp32(max_corr^2); fitness = correspondences / source points; inlier_rmse = sqrt(mean of the squared correspondence
     distances) (both 0 without correspondences).  Each iteration left-multiplies the Kabsch update onto the transformation and
     moves the float64 source by it; it stops when |d fitness| < rel_fitness and |d rmse| < rel_rmse, or after max_iter.
+    ``with_scaling``: every update is Umeyama WITH scale (open3d's TransformationEstimationPointToPoint(with_scaling=True),
+    CloudCompare's -ADJUST_SCALE), so the transformation is a similarity; everything else in the loop is unchanged.
     Returns dict(transformation [4,4] float64 numpy, fitness, inlier_rmse, iterations).  ``index``: a prebuilt NNIndex of target."""
     src = _points(source, "icp_point_to_point").double()
     if src.shape[0] == 0:
@@ -167,7 +182,7 @@ def icp_point_to_point(source, target, max_corr=0.1, init=None, max_iter=30, rel
         if int(ok.sum()) == 0:
             upd = np.eye(4)
         else:
-            upd = _kabsch(cur[ok], tgt[i[ok]])
+            upd = _kabsch(cur[ok], tgt[i[ok]], with_scaling)
         T = upd @ T
         cur = _transform(cur, torch.from_numpy(upd).to(src.device))
         prev = (fit, rmse)
@@ -192,14 +207,21 @@ def _as_cuda_mesh(m, device):
 
 
 @torch.no_grad()
-def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda"):
+def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda", pre_transform=None, clean=None,
+                 region=None, adjust_scale=False):
     """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
     ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
     reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
     ``seed`` for rec, ``seed + 1`` for gt).  Returns, in scene units: accuracy, completion, completion ratio (< 0.05),
     normals (mean |dot| of the face normals, both directions), chamfer-L1, chamfer-L2, f-score / f-score-15 / f-score-20
     (thresholds 0.010 / 0.015 / 0.020, <=), and transformation / icp fitness / icp rmse.
-    Departure: one ICP and one sample set per mesh serve every metric (the reference draws and aligns twice)."""
+    Departure: one ICP and one sample set per mesh serve every metric (the reference draws and aligns twice).
+    The steps eval_rec.py's __main__ (:259-272) does before the metrics, in its order, each off by default:
+    ``pre_transform`` (4x4 similarity, alignment_transformation_sim3.npy) moves the scaled reconstruction; ``clean``
+    ("largest", or "touching" / "not_touching" with ``region`` = (lo, hi)) keeps those components of it
+    (mesh_clean.keep_components) and adds "components" (count before cleaning) and "kept area fraction" to the result;
+    ``adjust_scale`` lets the ICP estimate a scale as well.  Departure: that one ICP does what CloudCompare's
+    -ICP -ADJUST_SCALE and open3d's registration_icp do one after the other in the reference."""
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_metrics: needs a GPU")
     rv, rf = _as_cuda_mesh(rec, device)
@@ -209,15 +231,26 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     if gv.shape[0] == 0 or gf.shape[0] == 0:
         raise ValueError("mesh_metrics: empty ground truth")
     rv, gv = (rv.double() / scale).float(), (gv.double() / scale).float()
+    extra = {}
+    if pre_transform is not None or clean is not None:
+        from . import mesh_clean
+        if pre_transform is not None:
+            _, P = mesh_clean.check_similarity(pre_transform)
+            rv = _transform(rv.double(), torch.from_numpy(P).to(rv.device)).float()
+        if clean is not None:
+            kept, st = mesh_clean.keep_components({"verts": rv, "faces": rf}, clean, region, device)
+            rv, rf = kept["verts"], kept["faces"]
+            extra = {"components": st["n_components"], "kept area fraction": st["kept_area_fraction"]}
     T, fit, rmse = np.eye(4), None, None
     if align:
-        icp = icp_point_to_point(rv, gv, 0.1)
+        icp = icp_point_to_point(rv, gv, 0.1, with_scaling=adjust_scale)
         T, fit, rmse = icp["transformation"], icp["fitness"], icp["inlier_rmse"]
         rv = _transform(rv.double(), torch.from_numpy(T).to(rv.device)).float()
     rp, ri = sample_surface(rv, rf, n_points, seed)
     gp, gi = sample_surface(gv, gf, n_points, seed + 1)
     out = metrics_from_samples(rp, _face_normals(rv, rf)[ri], gp, _face_normals(gv, gf)[gi])
     out.update({"transformation": T, "icp fitness": fit, "icp rmse": rmse})
+    out.update(extra)
     return out
 
 
@@ -249,8 +282,16 @@ def main(argv=None):
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--points", type=int, default=200000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--sim3", metavar="T.npy", help="4x4 similarity applied to REC first (alignment_transformation_sim3.npy)")
+    ap.add_argument("--clean", choices=("largest", "touching", "not_touching"), help="keep these components of REC")
+    ap.add_argument("--region", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--adjust-scale", action="store_true", help="the ICP estimates a scale as well")
     a = ap.parse_args(argv)
-    m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale)
+    if (a.clean in ("touching", "not_touching")) != (a.region is not None):
+        ap.error("--region goes with --clean touching or not_touching, and they need it")
+    m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,
+                     pre_transform=np.load(a.sim3) if a.sim3 else None, clean=a.clean,
+                     region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale)
     print("accuracy: ", m["accuracy"] * 100, "cm")
     print("completion: ", m["completion"] * 100, "cm")
     print("completion ratio: ", m["completion ratio"] * 100, "%")
@@ -258,6 +299,8 @@ def main(argv=None):
     for k in ("chamfer-L1", "chamfer-L2", "f-score", "f-score-15", "f-score-20", "icp fitness", "icp rmse"):
         print(f"{k}: {m[k]}")
     print("transformation:\n" + np.array2string(m["transformation"], precision=8))
+    if "components" in m:
+        print(f"components: {m['components']}  kept area fraction: {m['kept area fraction']}")
     return m
 
 
