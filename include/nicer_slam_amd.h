@@ -750,6 +750,118 @@ int nsa_mesh_component_stats(const float *verts, uint32_t n_verts, const int32_t
                              int32_t *label, int32_t *n_faces_out, int32_t *n_verts_out, double *area, float *lo, float *hi,
                              int32_t *vertex_comp, int32_t *face_comp, nsa_stream_t stream);
 
+/* ---- Section 12: mesh rasterisation and visibility (z-buffered images of a triangle mesh; DESIGN 4k, csrc/mesh_raster.hip) ---- */
+
+/* What code/utils/viz.py leaves to open3d's OpenGL window, and the depth image of a mesh that visibility culling needs.  There is no
+ * renderer to be bit-equal to, so this statement is the contract: all floating point is fp32, every operation rounded on its own
+ * (no FMA contraction), IEEE division and square root; all coverage arithmetic is exact int64.  tests/raster_ref.py restates it in
+ * numpy and the kernels equal it bit for bit.
+ *
+ * Inputs.  verts[V, 3] fp32, faces[F, 3] int32, and a batch of n views: w2c[n, 3, 4] fp32 world-to-camera rows (the caller inverts
+ * camera-to-world in float64 and rounds once), K[n or 1][4] = (fx, fy, cx, cy), an image of H x W pixels whose centres sit at
+ * integer (i, j) = (column, row) -- the conventions of Section 10 -- and near.  1 <= H, W <= NSA_RASTER_GUARD_PIXELS;
+ * 0 < near < NSA_RASTER_FAR; V, F, F + P < 2^31.
+ *
+ * Vertex v in a view:
+ *   p_r = ((R_r0 * v_x + R_r1 * v_y) + R_r2 * v_z) + t_r,  r = 0, 1, 2
+ *   DEPTH test   near < p_2 <= NSA_RASTER_FAR                                  (false for NaN)
+ *   x = (p_0 * fx) / p_2 + cx ;  y = (p_1 * fy) / p_2 + cy
+ *   GUARD test   |x| <= G and |y| <= G,  G = NSA_RASTER_GUARD_PIXELS            (false for NaN)
+ *   X = (int32)rint(x * 256.0f), Y likewise: a grid of 1/256 pixel (round half to even; x * 256 is exact).  |X| <= 2^22, so every
+ *   product of two coordinate differences is below 2^47 and the edge functions below are exact in int64.
+ *   Against the exact projection of the fp32 inputs, with u = 2^-24, m_r = |R_r0 v_x| + |R_r1 v_y| + |R_r2 v_z| + |t_r|:
+ *     |x - x_exact| <= u * (4 fx m_0 / p_2 + |x - cx| * (2 + 4 m_2 / p_2) + |x|)  to first order (four roundings in p_0 and in p_2,
+ *     one each in the product, the quotient and the sum), so |X - 256 x_exact| <= 1/2 + 256 times that: below 0.6 units
+ *     inside a 340 x 600 image of a room at a focal length of 300 pixels.
+ * Face.  Its indices are first rotated so that the smallest comes first, (A, B, C), keeping the winding: the image of a face depends
+ * on its vertex set and winding, not on which vertex the file lists first.  A face is DRAWN in a view unless, tested in this order:
+ *   1 an index lies outside [0, V) (Section 11's validity)    2 a vertex fails the DEPTH test (NaN, behind the camera, across near)
+ *   3 a vertex fails the GUARD test    4 area2 = (B_X - A_X)(C_Y - A_Y) - (B_Y - A_Y)(C_X - A_X) = 0
+ *   5 cull_backface is set and area2 > 0 (the normal (B - A) x (C - A) points away from the camera; x right, y down, z forward)
+ * A face that is not drawn is skipped WHOLE and counted: totals[c] += 1 per (face, view) with c the number above, totals[0] for drawn.
+ * DEPARTURE: there is no near-plane clipping; a face with one vertex behind near vanishes instead of being cut.
+ * When area2 < 0, B and C (and their 1/z) are exchanged and area2 negated, so that orient(A, B, C) > 0 below.
+ * Coverage of pixel centre P = (256 i, 256 j), with orient(a, b, p) = (b_X - a_X)(p_Y - a_Y) - (b_Y - a_Y)(p_X - a_X) in int64:
+ *   w_0 = orient(B, C, P), w_1 = orient(C, A, P), w_2 = orient(A, B, P)          (w_0 + w_1 + w_2 = area2)
+ *   edge a -> b OWNS the centres exactly on it when b_Y < a_Y, or b_Y = a_Y and b_X > a_X (left and top edges: the top-left rule)
+ *   covered  <=>  for each k: w_k > 0, or w_k = 0 and its edge owns.
+ *   Two drawn faces on opposite sides of a shared edge run it in opposite directions, exactly one direction owns, and w is exact:
+ *   a centre on the edge belongs to exactly one of them.  Candidates are the centres inside the bounding box of the snapped vertices,
+ *   clamped to the image: i from max(0, ceil(min X / 256)) to min(W - 1, floor(max X / 256)), j likewise.
+ * Depth at a covered pixel:
+ *   l_k = (float)w_k / (float)area2      (int64 -> fp32 round to nearest, then one division)
+ *   z_inv = (l_0 * (1.0f / p_2A) + l_1 * (1.0f / p_2B)) + l_2 * (1.0f / p_2C) ;  depth = 1.0f / z_inv       (z-depth, as Section 10)
+ *   Since 1/z is affine on the screen, the only error beyond rounding is the snap: every snapped vertex lies within
+ *   s = 1/512 pixel (plus the projection error above) of its projection per axis, so z_inv is the plane's exact 1/z at a point
+ *   within s of the centre, and |depth - exact| <= depth * exact * (|d(1/z)/di| + |d(1/z)/dj|) * s  plus a few ulp.
+ * Winner.  zbuf[n, H, W] uint64, empty = all ones.  key = (uint64)(bits of depth) << 32 | id with id = the face index; every
+ * covered (face, pixel) does one unsigned 64-bit atomic minimum.  depth is positive and finite, so keys order as depths, and ties in
+ * depth go to the smaller id.  The minimum is independent of arrival order: the image is a function of the inputs alone.
+ * Points.  points[P, 3] fp32 drawn as squares of point_size (1 .. NSA_RASTER_MAX_POINT_SIZE) pixels with id = F + index: a point that
+ * passes DEPTH and GUARD covers the centres with X - h <= 256 i < X + h and Y - h <= 256 j < Y + h, h = 128 * point_size, all at
+ * depth = p_2 (totals[9] drawn, totals[10] skipped, per (point, view)).
+ * Large faces.  A drawn face with more than large_threshold candidate centres is cut into (face, view, 64 x 64 screen tile) items in
+ * a queue in the workspace and drawn by a second kernel, one wave per item; 0 sends every face that way, 0xFFFFFFFF none.  Both
+ * ways apply the same rule, so the image does not depend on large_threshold or queue_capacity (a face whose items do not fit the
+ * queue is drawn the first way).  totals[6] = atomic minima issued = covered (face or point, pixel) pairs, totals[7] = (face, view)
+ * pairs that asked for the queue, totals[8] = items queued; [7] and [8] depend on large_threshold, [8] on the capacity, nothing else does.
+ * Nothing is allocated or synchronised; zbuf, totals and the workspace belong to the caller. */
+#define NSA_RASTER_GUARD_PIXELS 16384
+#define NSA_RASTER_FAR 1e30f
+#define NSA_RASTER_MAX_POINT_SIZE 64
+#define NSA_RASTER_TOTALS 12
+
+typedef struct nsa_raster_views {
+    const float *w2c;    /* [n, 3, 4]                                                                                     */
+    const float *K;      /* [n, 4] when K_per_view is non-zero, else [1, 4]                                               */
+    uint32_t n;          /* views in the batch, 1 .. 2^20, n * H * W < 2^40                                               */
+    int K_per_view;
+    uint32_t H, W;
+    float near;
+} nsa_raster_views_t;
+
+/* bytes of workspace for a queue of queue_capacity items (16 bytes each, after a 16-byte header) */
+uint64_t nsa_mesh_raster_workspace(uint32_t queue_capacity);
+
+/* Faces and points into zbuf for a batch of views.  clear non-zero: zbuf is first set to all ones and totals[NSA_RASTER_TOTALS]
+ * (uint64, device) to zero; zero: both are accumulated into, so several calls can draw into one image (ids are the caller's to
+ * keep apart).  points may be NULL with n_points = 0, faces with n_faces = 0. */
+int nsa_mesh_raster(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const float *points,
+                    uint32_t n_points, uint32_t point_size, const nsa_raster_views_t *views, int cull_backface, int clear,
+                    uint32_t large_threshold, void *workspace, uint32_t queue_capacity, uint64_t *zbuf, uint64_t *totals,
+                    nsa_stream_t stream);
+
+/* Resolve, per pixel of a finished zbuf; every output [n, H, W (, 3)] is optional (NULL), at least one is required:
+ *   face_id int32   the winner's id (a point: F + index), -1 where empty
+ *   depth fp32      the key's depth, 0 where empty (Section 10's "no measurement": the image feeds nsa_tsdf_integrate unchanged)
+ * and for a face, recomputed from its id and the same integers (a point: normal 0, shade 1, colour = palette[point_colour[index]],
+ * 0 when that index is outside [0, n_palette); empty: all 0):
+ *   normal   c = (B - A) x (C - A) of the rotated, unswapped face, each component a difference of two products;
+ *            len = sqrt((c_x c_x + c_y c_y) + c_z c_z); n = c / len, or 0 unless 0 < len <= 3e38.  With flip_to_camera, n is negated
+ *            for a face with area2 > 0, so that every normal faces the camera by the same integer test that culls.
+ *   colour   q_k = l_k * (1.0f / p_2k); colour_c = ((q_0 * c_Ac + q_1 * c_Bc) + q_2 * c_Cc) / ((q_0 + q_1) + q_2) with colours[V, 3]
+ *            (perspective-correct; B and C as exchanged above); 0 when colours is NULL
+ *   shade    the headlight term |n_c . d|: n_c,r = (R_r0 n_x + R_r1 n_y) + R_r2 n_z (before the flip), d_x = ((float)i - cx) / fx,
+ *            d_y = ((float)j - cy) / fy, shade = |((n_c0 * d_x + n_c1 * d_y) + n_c2) / sqrt((d_x d_x + d_y d_y) + 1.0f)|. */
+int nsa_mesh_raster_resolve(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const float *colours,
+                            const int32_t *point_colour, uint32_t n_points, const float *palette, uint32_t n_palette,
+                            const nsa_raster_views_t *views, const uint64_t *zbuf, int flip_to_camera, int32_t *face_id,
+                            float *depth, float *normal, float *colour, float *shade, nsa_stream_t stream);
+
+/* Visibility of faces in the finished views of zbuf.  A vertex is SEEN in a view when it passes DEPTH and GUARD, 0 <= x <= W - 1 and
+ * 0 <= y <= H - 1, and p_2 <= (1.0f + rel) * z_max, z_max = the largest zbuf depth over the four centres (i0, j0), (i1, j0), (i0, j1),
+ * (i1, j1), i0 = (int)floor(x), i1 = min(i0 + 1, W - 1), j likewise; an empty pixel counts as +inf.  A face with valid indices is
+ * visible in a view when any (NSA_VISIBLE_ANY) or all three (NSA_VISIBLE_ALL) of its vertices are seen in it; NSA_VISIBLE_FRUSTUM is
+ * ANY without the depth comparison (zbuf may be NULL).  visible[F] uint8 gets a plain store of 1 for a face visible in some view of the
+ * batch and is otherwise left alone, so calls over several batches OR into it (the caller zeroes it first).  Visibility is decided at
+ * vertices against the depth image because a face smaller than a pixel covers no centre and would never appear in face_id.
+ * 0 <= rel <= 1. */
+#define NSA_VISIBLE_ANY 0
+#define NSA_VISIBLE_ALL 1
+#define NSA_VISIBLE_FRUSTUM 2
+int nsa_mesh_visible(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const nsa_raster_views_t *views,
+                     const uint64_t *zbuf, int mode, float rel, uint8_t *visible, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -327,3 +327,20 @@ lib.nsa_mesh_component_stats.restype = _i
 lib.nsa_mesh_component_stats.argtypes = [_p, _u32, _p, _u32, _p, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_components_workspace", "nsa_mesh_components", "nsa_mesh_component_stats_workspace",
             "nsa_mesh_component_stats"]
+
+
+class RasterViews(ctypes.Structure):
+    """nsa_raster_views_t"""
+    _fields_ = [("w2c", _p), ("K", _p), ("n", _u32), ("K_per_view", _i), ("H", _u32), ("W", _u32), ("near", _f32)]
+
+
+_rv = ctypes.POINTER(RasterViews)
+lib.nsa_mesh_raster_workspace.restype = _u64
+lib.nsa_mesh_raster_workspace.argtypes = [_u32]
+lib.nsa_mesh_raster.restype = _i
+lib.nsa_mesh_raster.argtypes = [_p, _u32, _p, _u32, _p, _u32, _u32, _rv, _i, _i, _u32, _p, _u32, _p, _p, _p]
+lib.nsa_mesh_raster_resolve.restype = _i
+lib.nsa_mesh_raster_resolve.argtypes = [_p, _u32, _p, _u32, _p, _p, _u32, _p, _u32, _rv, _p, _i, _p, _p, _p, _p, _p, _p]
+lib.nsa_mesh_visible.restype = _i
+lib.nsa_mesh_visible.argtypes = [_p, _u32, _p, _u32, _rv, _p, _i, _f32, _p, _p]
+EXPORTS += ["nsa_mesh_raster_workspace", "nsa_mesh_raster", "nsa_mesh_raster_resolve", "nsa_mesh_visible"]

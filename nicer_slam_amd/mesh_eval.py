@@ -208,7 +208,7 @@ def _as_cuda_mesh(m, device):
 
 @torch.no_grad()
 def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda", pre_transform=None, clean=None,
-                 region=None, adjust_scale=False):
+                 region=None, adjust_scale=False, cull=None):
     """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
     ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
     reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
@@ -221,7 +221,12 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     ("largest", or "touching" / "not_touching" with ``region`` = (lo, hi)) keeps those components of it
     (mesh_clean.keep_components) and adds "components" (count before cleaning) and "kept area fraction" to the result;
     ``adjust_scale`` lets the ICP estimate a scale as well.  Departure: that one ICP does what CloudCompare's
-    -ICP -ADJUST_SCALE and open3d's registration_icp do one after the other in the reference."""
+    -ICP -ADJUST_SCALE and open3d's registration_icp do one after the other in the reference.
+    ``cull`` (off by default; not a step of the reference): dict(c2w=, intrinsics=, size=(H, W) [, mode=, rel=, near=]) keeps the faces of
+    the reconstruction that some of these cameras saw (mesh_render.cull_mesh), after ``pre_transform`` and ``clean`` and
+    before the ICP, and adds "culled face fraction" to the result.  The cameras look at the reconstruction AS IT IS AT THAT POINT: the
+    poses (and the default near of 0.01) are in the frame and units the vertices have after the division by ``scale`` and after
+    ``pre_transform`` -- with ``scale`` other than 1, poses in the mesh file's own units would look at a mesh of another size."""
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_metrics: needs a GPU")
     rv, rf = _as_cuda_mesh(rec, device)
@@ -241,6 +246,14 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
             kept, st = mesh_clean.keep_components({"verts": rv, "faces": rf}, clean, region, device)
             rv, rf = kept["verts"], kept["faces"]
             extra = {"components": st["n_components"], "kept area fraction": st["kept_area_fraction"]}
+    if cull is not None:
+        from . import mesh_render
+        n_before = rf.shape[0]
+        kept = mesh_render.cull_mesh({"verts": rv, "faces": rf}, **cull)
+        rv, rf = kept["verts"], kept["faces"]
+        if rf.shape[0] == 0:
+            raise ValueError("mesh_metrics: culling left no face of the reconstruction")
+        extra["culled face fraction"] = 1.0 - rf.shape[0] / n_before
     T, fit, rmse = np.eye(4), None, None
     if align:
         icp = icp_point_to_point(rv, gv, 0.1, with_scaling=adjust_scale)
@@ -286,12 +299,25 @@ def main(argv=None):
     ap.add_argument("--clean", choices=("largest", "touching", "not_touching"), help="keep these components of REC")
     ap.add_argument("--region", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
     ap.add_argument("--adjust-scale", action="store_true", help="the ICP estimates a scale as well")
+    ap.add_argument("--cull-poses", metavar="POSES", help="cull REC to what these camera-to-world poses saw (.npy, text or a directory); the poses are in the frame REC has "
+                    "after --scale and --sim3 have been applied, not in the file's own units")
+    ap.add_argument("--cull-intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"))
+    ap.add_argument("--cull-size", type=int, nargs=2, metavar=("H", "W"))
+    ap.add_argument("--cull-mode", choices=("any", "all", "frustum"), default="any")
     a = ap.parse_args(argv)
+    if a.cull_poses and not (a.cull_intrinsics and a.cull_size):
+        ap.error("--cull-poses needs --cull-intrinsics and --cull-size")
+    if not a.cull_poses and (a.cull_intrinsics or a.cull_size):
+        ap.error("--cull-intrinsics and --cull-size go with --cull-poses")
+    cull = None
+    if a.cull_poses:
+        from .mesh_render import read_poses
+        cull = dict(c2w=read_poses(a.cull_poses), intrinsics=a.cull_intrinsics, size=tuple(a.cull_size), mode=a.cull_mode)
     if (a.clean in ("touching", "not_touching")) != (a.region is not None):
         ap.error("--region goes with --clean touching or not_touching, and they need it")
     m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,
                      pre_transform=np.load(a.sim3) if a.sim3 else None, clean=a.clean,
-                     region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale)
+                     region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale, cull=cull)
     print("accuracy: ", m["accuracy"] * 100, "cm")
     print("completion: ", m["completion"] * 100, "cm")
     print("completion ratio: ", m["completion ratio"] * 100, "%")
@@ -301,6 +327,8 @@ def main(argv=None):
     print("transformation:\n" + np.array2string(m["transformation"], precision=8))
     if "components" in m:
         print(f"components: {m['components']}  kept area fraction: {m['kept area fraction']}")
+    if "culled face fraction" in m:
+        print(f"culled face fraction: {m['culled face fraction']}")
     return m
 
 
