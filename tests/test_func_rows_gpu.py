@@ -94,3 +94,6 @@ def test_a11_a13_density_and_weights_in_the_composite_kernel(fx):
     assert_close(w, ref_w.numpy(), 1e-6, 1e-5, "weights")
     assert_close(rgbv, (ref_w[..., None] * rgb.cpu().view(Rn, S, 3)).sum(1).numpy(), 2e-6, 1e-5, "rgb_values")
     assert_close(dep, ((ref_w * z).sum(1) / (ref_w.sum(1) + 1e-8)).numpy(), 2e-6, 1e-5, "depth")
+    g = grad.cpu().view(Rn, S, 3)
+    assert_close(nm, (ref_w[..., None] * (g / (g.norm(2, -1, keepdim=True) + 1e-6))).sum(1).numpy(), 2e-6, 1e-5, "nmap")
+    assert_close(ent, (-ref_w * torch.log(ref_w + 1e-4)).sum(-1).numpy(), 2e-6, 1e-5, "entropy")
