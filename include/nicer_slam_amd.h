@@ -472,7 +472,7 @@ int nsa_slam_loss(const nsa_loss_t *in, float *workspace /* nsa_slam_loss_worksp
                   nsa_stream_t stream);
 uint64_t nsa_slam_loss_workspace(uint32_t bs, uint32_t n, uint32_t E);
 
-/* ---- Section 5: keyframe re-projection blocks of a mapping iteration (patch warp, flow) and their masked-L1 terms ---- */
+/* ---- Section 5: keyframe re-projection blocks of a mapping iteration (patch warp, flow), their masked-L1 and patch-SSIM terms ---- */
 
 /* Shared description of a mapping batch: b keyframes x n sampled pixels.  `images` / `depths` are the resident full frames
  * ([frames,H,W,3] / [frames,H,W] fp32, pixel (y,x) at y*W+x -- the reference's ground_truth['full_rgb'] / ['full_depth'],
@@ -525,6 +525,21 @@ uint64_t nsa_flow_workspace(uint32_t b, uint32_t n, uint32_t ne, int want_pose);
 int nsa_masked_l1(const float *pred, const float *target, const uint8_t *mask, uint64_t items, uint32_t channels, float *loss,
                   float *g_pred, float *workspace, nsa_stream_t stream);
 uint64_t nsa_masked_l1_workspace(uint64_t items);
+
+/* The SSIM form of the patch-warp term (warp_loss_type = "ssim", code/model/loss.py:51-55,145-152: pytorch_msssim's SSIM with
+ * data_range 1 and a sigma-1.5 Gaussian window as large as the patch, so one value per patch and channel).  pred, target:
+ * [n_patches, patch^2, 3] fp32; mask: [n_patches, patch^2] bytes or NULL (all); both images count as 0 where the mask is
+ * false (zeroed, not excluded).  Per patch and channel, in float64 with w_ij = g_i * g_j the exact product of the fp32 window:
+ *   mu_x = sum w x, mu_y = sum w y, s_xx = sum w x^2 - mu_x^2, s_yy = sum w y^2 - mu_y^2, s_xy = sum w x y - mu_x mu_y
+ *   SSIM = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) * (2 s_xy + C2) / (s_xx + s_yy + C2),   C1 = 1e-4, C2 = 9e-4
+ * loss[0] = 1 - mean of the 3 * n_patches values, rounded once to fp32 (the reference's term is 0.05 * loss[0]); a wholly masked
+ * patch counts with SSIM exactly 1; pred == target gives exactly 0; n_patches == 0 gives NaN (torch's mean of nothing) and is not
+ * an error.  g_pred (optional, pred's layout) = d loss[0] / d pred, rounded once, exactly 0 where the mask is false.
+ * patch: odd, 3 .. 11, and 3 * patch^2 * n_patches < 2^31.  workspace: nsa_patch_ssim_workspace() floats, 8-byte aligned.
+ * Two launches, no atomics: bit-identical from run to run, and a patch's gradient does not depend on its place in the batch. */
+int nsa_patch_ssim(const float *pred, const float *target, const uint8_t *mask, uint64_t n_patches, uint32_t patch, float *loss,
+                   float *g_pred, float *workspace, nsa_stream_t stream);
+uint64_t nsa_patch_ssim_workspace(uint64_t n_patches);
 
 /* ---- Section 6: per-iteration input batch from frames resident in HBM ------------------------------------------------ */
 

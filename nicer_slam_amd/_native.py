@@ -275,6 +275,11 @@ lib.nsa_masked_l1_workspace.restype = _u64
 lib.nsa_masked_l1_workspace.argtypes = [_u64]
 EXPORTS += ["nsa_patch_warp_forward", "nsa_patch_warp_backward", "nsa_patch_warp_workspace", "nsa_flow_forward",
             "nsa_flow_backward", "nsa_flow_workspace", "nsa_masked_l1", "nsa_masked_l1_workspace"]
+lib.nsa_patch_ssim.restype = _i
+lib.nsa_patch_ssim.argtypes = [_p, _p, _p, _u64, _u32, _p, _p, _p, _p]
+lib.nsa_patch_ssim_workspace.restype = _u64
+lib.nsa_patch_ssim_workspace.argtypes = [_u64]
+EXPORTS += ["nsa_patch_ssim", "nsa_patch_ssim_workspace"]
 
 lib.nsa_marching_cubes_workspace.restype = _u64
 lib.nsa_marching_cubes_workspace.argtypes = [_u32, _u32, _u32]

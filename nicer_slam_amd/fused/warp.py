@@ -183,6 +183,55 @@ def masked_l1(pred, target, mask, channels):
     return _MaskedL1.apply(pred, target, mask, channels)
 
 
+SSIM_MAX_PATCH = 11      # what nsa_patch_ssim covers (odd, 3 .. 11); larger odd patches: model/warp.py::patch_ssim_term
+
+
+class _PatchSSIM(torch.autograd.Function):
+    """1 - mean SSIM of the masked p x p patches (window = patch, float64 per patch; csrc/patch_ssim.hip) with its gradient formed
+    in the forward (two launches, no host round trip)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, patch):
+        patch = int(patch)
+        p2 = patch * patch
+        if patch < 3 or patch % 2 == 0 or patch > SSIM_MAX_PATCH:
+            raise ValueError(f"patch_ssim: patch {patch} must be odd and in 3 .. {SSIM_MAX_PATCH}")
+        # the kernel indexes target like pred and mask per pixel: anything else would read out of bounds
+        if pred.dim() < 2 or tuple(pred.shape[-2:]) != (p2, 3):
+            raise ValueError(f"patch_ssim: pred {tuple(pred.shape)} is not [..., {p2}, 3]")
+        if target.shape != pred.shape:
+            raise ValueError(f"patch_ssim: target {tuple(target.shape)} must have the shape of pred {tuple(pred.shape)}")
+        if mask is not None and mask.shape != pred.shape[:-1]:
+            raise ValueError(f"patch_ssim: mask {tuple(mask.shape)} must be {tuple(pred.shape[:-1])}")
+        dev = pred.device
+        pred_, target_ = _c(pred), _c(target).to(dev)
+        n = pred_.numel() // (3 * p2)
+        m = None
+        if mask is not None:
+            m = mask.to(dev).contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else (m != 0).view(torch.uint8)
+        loss = torch.empty(1, device=dev)
+        g = torch.empty_like(pred_) if ctx.needs_input_grad[0] else None
+        ws = torch.empty((int(lib.nsa_patch_ssim_workspace(n)) + 1) // 2, device=dev, dtype=torch.float64)
+        with _timed("k_patch_ssim", pred_.numel() * 4 * (2 if g is None else 3) + (0 if m is None else m.numel())):
+            check(lib.nsa_patch_ssim(pred_.data_ptr(), target_.data_ptr(), None if m is None else m.data_ptr(), n, patch,
+                                     loss.data_ptr(), None if g is None else g.data_ptr(), ws.data_ptr(), _stream()))
+        ctx.g = g
+        ctx.shape = pred.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        g = ctx.g
+        return (None if g is None else (g * g_loss).reshape(ctx.shape)), None, None, None
+
+
+def patch_ssim(pred, target, mask, patch):
+    """pred, target: [..., patch^2, 3] fp32 device tensors; mask: [..., patch^2] bool or None -> 1 - mean SSIM (a scalar; the
+    reference's term is 0.05 times this).  Pixels outside the mask count as 0 in both patches; the inputs are not modified."""
+    return _PatchSSIM.apply(pred, target, mask, patch)
+
+
 def patch_warp(model, uv, pose, intrinsics, rendered_depth, ground_truth, batch_size):
     """Same contract as model/warp.py::patch_warp: {patch: (gt_warp_rgbs, target_sampled_rgb, total_warp_mask, ray_level)}."""
     H, W = model.H, model.W

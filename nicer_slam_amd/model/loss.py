@@ -7,8 +7,10 @@ builds ``loss_class(**conf.loss, ...)`` can switch.  On the GPU the per-ray term
 (fused/loss.py -> csrc/loss_terms.hip: rgb, eikonal, smooth, ssi depth, gt depth, normals); the torch restatement below is the
 same arithmetic for CPU tensors, for the ray-sharded depth reduction and for non-L1 colour losses; the flow and patch-warp terms
 are masked-L1 means (fused/warp.py::masked_l1 -> csrc/warp_terms.hip on the GPU) over the tensors the model's re-projection
-kernels produce.  The tracking objective (rgb L1 only) additionally exists as a HIP kernel for the
-graph-captured tracker (csrc/track_tail.hip::k_l1_loss).
+kernels produce; with warp_loss_type = "ssim" the patches larger than one pixel are scored by a per-patch
+SSIM in float64 instead (fused/warp.py::patch_ssim -> csrc/patch_ssim.hip on the GPU, model/warp.py::patch_ssim_term elsewhere).
+The tracking objective (rgb L1 only) additionally exists as a HIP kernel for the graph-captured tracker
+(csrc/track_tail.hip::k_l1_loss).
 """
 import torch
 from torch import nn
@@ -84,7 +86,10 @@ class SLAMLoss(nn.Module):
         self.gt_depth_weight, self.flow_weight = gt_depth_weight, flow_weight
         self.warp_loss_weight, self.warp_loss_type, self.rgb_loss_weight = warp_loss_weight, warp_loss_type, rgb_loss_weight
         self.rgb_loss = get_class(rgb_loss)(reduction="mean") if isinstance(rgb_loss, str) else rgb_loss
-        self._ssim = {}
+
+    def __setstate__(self, state):
+        state.pop("_ssim", None)          # (pickles made when the SSIM term kept a cache of pytorch_msssim modules)
+        super().__setstate__(state)
 
     # ---- individual terms (same names as the reference so callers/plots can reuse them) ----
     def get_rgb_loss(self, rgb_values, rgb_gt, mask=None):
@@ -137,18 +142,16 @@ class SLAMLoss(nn.Module):
                     total = total + masked_l1(sampled, gt_rgb, mask, 3)
                 else:
                     total = total + (sampled[mask] - gt_rgb[mask]).abs().mean()
-            else:   # "ssim": needs pytorch_msssim, exactly as the reference does
-                try:
-                    from pytorch_msssim import SSIM
-                except ImportError as e:
-                    raise NotImplementedError("warp_loss_type='ssim' needs the pytorch_msssim package") from e
-                if patchsize not in self._ssim:
-                    self._ssim[patchsize] = SSIM(data_range=1, win_size=patchsize, size_average=True, channel=3)
-                a = torch.where(mask[..., None], sampled, torch.zeros_like(sampled))
-                b = torch.where(mask[..., None], gt_rgb, torch.zeros_like(gt_rgb))
-                a = a.reshape(-1, patchsize, patchsize, 3).permute(0, 3, 1, 2)
-                b = b.reshape(-1, patchsize, patchsize, 3).permute(0, 3, 1, 2)
-                total = total + 0.05 * (1 - self._ssim[patchsize](a, b))
+            else:   # "ssim": window = patch, one SSIM value per patch and channel, in float64
+                term = None
+                if self._kernels(sampled):
+                    from ..fused import warp as fw
+                    if patchsize <= fw.SSIM_MAX_PATCH:
+                        term = 0.05 * fw.patch_ssim(sampled, gt_rgb, mask, patchsize)
+                if term is None:      # CPU tensors, other dtypes, engine == "torch", patches larger than the kernel covers
+                    from .warp import patch_ssim_term
+                    term = patch_ssim_term(sampled, gt_rgb, mask, patchsize)
+                total = total + term
         return total
 
     def _fused_ok(self, model_outputs):

@@ -5,6 +5,8 @@ For every patch size: the patch around each sampled pixel of every keyframe is l
 projected into every keyframe, and the full images are sampled there; the loss compares with the patch read directly
 from the source image.  Returns {patchsize: (gt_warp_rgbs, target_sampled_rgb, total_warp_mask, depth_mask_ray_level)}
 with the reference's shapes: [target, reference, n_pixels, patch^2, (3)]."""
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -76,3 +78,40 @@ def flow_reproject(uv, pose, intrinsics, rendered_depth, edges):
     cam_pts = w2c[:, :3, :3] @ pts[idii] + w2c[:, :3, 3:]
     proj = (intrinsics[idjj][:, :3, :3] @ cam_pts).permute(0, 2, 1)
     return proj[..., :2] / (proj[..., 2:] + 1e-8) - uv[idii]
+
+
+def ssim_window_1d(patch):
+    """The p-tap sigma-1.5 Gaussian of pytorch_msssim's _fspecial_gauss_1d as csrc/patch_ssim.hip builds it: fp32 values of exp at the
+    fp32 arguments -(k - p//2)^2 / 4.5, divided (in fp32) by their correctly rounded fp32 sum.  A CPU fp32 tensor [p]."""
+    d = torch.arange(patch, dtype=torch.float32) - (patch // 2)
+    arg = -(d * d) / 4.5
+    g = torch.tensor([math.exp(float(a)) for a in arg], dtype=torch.float64).to(torch.float32)
+    return g / g.double().sum().to(torch.float32)          # (the float64 sum of these few fp32 values is exact)
+
+
+def patch_ssim_term(sampled, gt_rgb, mask, patch):
+    """The SSIM form of the patch-warp term for one patch size (reference code/model/loss.py:145-152: pytorch_msssim's SSIM with
+    win_size = patch, data_range 1): 0.05 * (1 - mean over patches and channels of SSIM), any dtype, any device, any odd
+    patch >= 3.  The composed twin of fused/warp.py::patch_ssim, same definition (csrc/patch_ssim.hip): both patches are 0 outside
+    the mask (zeroed, not excluded; the inputs are left alone), the 2-D weights are the exact products of the fp32 window, and
+    the moments and the SSIM formula are evaluated in float64 -- sigma^2 = E[x^2] - mu^2 cancels on flat patches -- before
+    1 - mean is rounded to the input's dtype.  A wholly masked patch counts with SSIM 1, as in the reference."""
+    patch = int(patch)
+    if patch < 3 or patch % 2 == 0:
+        raise ValueError(f"patch_ssim_term: patch {patch} must be odd and >= 3")
+    p2 = patch * patch
+    wide = torch.promote_types(sampled.dtype, torch.float64)
+    g = ssim_window_1d(patch).double()
+    w = (g[:, None] * g[None, :]).reshape(1, p2, 1).to(sampled.device)
+    m = mask.reshape(-1, p2, 1)
+    x = sampled.reshape(-1, p2, 3)
+    y = gt_rgb.to(sampled.device).reshape(-1, p2, 3)
+    x = torch.where(m, x, torch.zeros_like(x)).to(wide)
+    y = torch.where(m, y, torch.zeros_like(y)).to(wide)
+    c1, c2 = 1e-4, 9e-4
+    mx, my = (w * x).sum(1), (w * y).sum(1)
+    sxx = (w * x * x).sum(1) - mx * mx
+    syy = (w * y * y).sum(1) - my * my
+    sxy = (w * x * y).sum(1) - mx * my
+    ssim = (2 * mx * my + c1) / (mx * mx + my * my + c1) * ((2 * sxy + c2) / (sxx + syy + c2))
+    return 0.05 * (1 - ssim.mean()).to(sampled.dtype)
