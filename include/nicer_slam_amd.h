@@ -877,6 +877,46 @@ int nsa_mesh_raster_resolve(const float *verts, uint32_t n_verts, const int32_t 
 int nsa_mesh_visible(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const nsa_raster_views_t *views,
                      const uint64_t *zbuf, int mode, float rel, uint8_t *visible, nsa_stream_t stream);
 
+/* ---- Section 13: optical-flow ground truth from depth and poses (csrc/flow_cues.hip) ---- */
+
+/* What the reference reads from its *_pair directories (preprocess/extract_flows.py: GMFlow and a forward-backward consistency
+ * check; code/training/volsdf_train.py:312-361: the edge graph, the files and the per-iteration gather).  With depth frames and
+ * poses the flow between two frames is geometry, and this statement is the contract (tests/flow_ref.py restates it in float64).
+ * Conventions are Section 10's: pixel centres at integer (u, v) = (column, row), z-depth, K rows (fx, fy, cx, cy).  All arithmetic is
+ * float64 per pixel and every output is rounded once on its store.  Each entry point is ONE launch over all its edges or pairs, of
+ * fewer than 2^24 workgroups of 256 lanes (a lane owns 1 to 4 pixels or one sample), more is NSA_EBADARG;
+ * nothing is allocated or synchronised; empty work (no edges, no pairs, n = 0) returns 0 without a launch.
+ *
+ * Induced flow.  depth[n_frames, H, W] fp32; K[n_frames or 1][4] float64; rel[n_edges, 3, 4] float64 rows [R_e | t_e] of
+ * inv(c2w_j) * c2w_i, composed by the caller in float64, i = src[e], j = dst[e] (int32, device).  Pixel (u, v) of frame i, depth d:
+ *   X = ((u - cx_i) / fx_i * d, (v - cy_i) / fy_i * d, d) ;  Y = R_e X + t_e
+ *   flow[e, v, u] = (fx_j * Y_0 / Y_2 + cx_j - u,  fy_j * Y_1 / Y_2 + cy_j - v)            [n_edges, H, W, 2] fp32
+ *   valid[e, v, u] = isfinite(d) and d > 0 and Y_2 > near                                  [n_edges, H, W] uint8; invalid: flow (0, 0)
+ * Leaving the image does not make a pixel invalid (that is the consistency rule's to find).  An edge whose src or dst lies outside
+ * [0, n_frames) reads nothing and is invalid everywhere.  H * W < 2^31, 0 <= near < inf. */
+int nsa_flowcue_induced(const float *depth, uint32_t n_frames, uint32_t H, uint32_t W, const double *K, int K_per_frame,
+                        const double *rel, const int32_t *src, const int32_t *dst, uint32_t n_edges, double near, float *flow,
+                        uint8_t *valid, nsa_stream_t stream);
+
+/* Forward-backward consistency (GMFlow's rule, as extract_flows.py applies it).  fwd, bwd [n_pairs, H, W, 2] fp32; per pixel p = (u, v):
+ *   mag = |fwd(p)| + |bwd(p)|                                    (both at the SAME pixel: the rule's own quirk, kept)
+ *   wb  = bilinear sample of bwd at p + fwd(p) in pixel coordinates, taps outside the image count as zero
+ *   fwd_occ(p) = |fwd(p) + wb| > alpha * mag + beta              1 = occluded; bwd_occ likewise with the roles exchanged
+ * With validity maps (both or neither, [n_pairs, H, W] uint8) a pixel is also occluded when it is itself invalid, or when the bilinear
+ * sample of the partner's invalidity map (1 - valid, zero outside the image) at its landing point exceeds 1e-3.  A non-finite landing
+ * point reads nothing.  H, W >= 2, H * W < 2^31, alpha and beta finite and >= 0. */
+int nsa_flowcue_consistency(const float *fwd, const float *bwd, const uint8_t *fwd_valid, const uint8_t *bwd_valid, uint32_t n_pairs,
+                            uint32_t H, uint32_t W, double alpha, double beta, uint8_t *fwd_occ, uint8_t *bwd_occ,
+                            nsa_stream_t stream);
+
+/* The per-iteration gather (select_flow_uv): flows[n_edges, n_pixels, 2] fp32 and masks[n_edges, n_pixels] bytes resident on the
+ * device, sampling_idx[b, n] and idii[n_edges] int64:
+ *   out_flow[e, k] = flows[e, s], out_mask[e, k] = masks[e, s] != 0,  s = sampling_idx[idii[e], k]
+ * and flow 0, mask 0 when s lies outside [0, n_pixels) or idii[e] outside [0, b): nothing is ever read out of range.
+ * 0 < n_pixels < 2^31. */
+int nsa_flowcue_select(const float *flows, const uint8_t *masks, uint32_t n_edges, uint64_t n_pixels, const int64_t *sampling_idx,
+                       uint32_t b, uint32_t n, const int64_t *idii, float *out_flow, uint8_t *out_mask, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -349,3 +349,12 @@ lib.nsa_mesh_raster_resolve.argtypes = [_p, _u32, _p, _u32, _p, _p, _u32, _p, _u
 lib.nsa_mesh_visible.restype = _i
 lib.nsa_mesh_visible.argtypes = [_p, _u32, _p, _u32, _rv, _p, _i, _f32, _p, _p]
 EXPORTS += ["nsa_mesh_raster_workspace", "nsa_mesh_raster", "nsa_mesh_raster_resolve", "nsa_mesh_visible"]
+
+_f64 = ctypes.c_double
+lib.nsa_flowcue_induced.restype = _i
+lib.nsa_flowcue_induced.argtypes = [_p, _u32, _u32, _u32, _p, _i, _p, _p, _p, _u32, _f64, _p, _p, _p]
+lib.nsa_flowcue_consistency.restype = _i
+lib.nsa_flowcue_consistency.argtypes = [_p, _p, _p, _p, _u32, _u32, _u32, _f64, _f64, _p, _p, _p]
+lib.nsa_flowcue_select.restype = _i
+lib.nsa_flowcue_select.argtypes = [_p, _p, _u32, _u64, _p, _u32, _u32, _p, _p, _p, _p]
+EXPORTS += ["nsa_flowcue_induced", "nsa_flowcue_consistency", "nsa_flowcue_select"]

@@ -335,12 +335,13 @@ def make_student(teacher, H, W, n_images, colour_grid=None, seed=11, family="rep
 
 def run_slam(engine, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_grid=None, map_every=5, map_iters=100, track_iters=100,
              map_pixels=8192, track_pixels=1024, lr=0.002, cam_lr=0.005, ba_lr=0.001, window=15, log=None, schedule="reference", seed=11,
-             family="replica", none_grad="skip", const_speed=False):
+             family="replica", none_grad="skip", const_speed=False, flow=False):
     """Tracking AND mapping in the reference's loop shape (volsdf_train.py:363-613) on `engine`: frame 0 at its ground-truth pose and
     `map_iters` mapping iterations on it; every later frame tracked from the constant-speed initialisation against the map learned so far;
     every `map_every`-th frame a mapping round over the keyframe window (every 10th frame + the current one; the frames since the last
     keyframe join half-way), coarse -> fine and base -> highfreq schedules, bundle adjustment of the window's cameras in the last 30 % of a
-    round (poses written back as :584-594 does).  Objective: the shipped SLAMLoss weights without the warp / flow terms; the monocular
+    round (poses written back as :584-594 does).  Objective: the shipped SLAMLoss weights without the warp terms (and without the flow
+    term unless `flow`); the monocular
     depth / normal cues are the teacher's renderings.  schedule = "reference": stage / colour-stage schedule of volsdf_train.py:550-555;
     "fine": every round at stage "fine" / "highfreq" -- on this synthetic scene the coarse-only quarter of a later round is BISTABLE
     (tools/diag_slam_mapping.py, profiles/r05_slam_mapping_rounds.txt: from one and the same state the round ends at loss 0.044 or loses the
@@ -348,7 +349,12 @@ def run_slam(engine, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_gr
     family: the conf family (model subtree + loss weights, utils/conf.py).  none_grad: the mapping optimizer's treatment of a table outside its
     stage -- "skip" = the installed torch (zero_grad() sets .grad = None, the table is not stepped), "zeros" = torch 1.11, the reference's
     environment (zero_grad() leaves zero tensors, the table keeps moving along its momentum; nicer_slam_amd/optim.py).
+    flow: add the flow term at the family's flow_weight.  Its ground truth is what a depth sensor and a pose source would give
+    (nicer_slam_amd/flow_cues.py): the flow the sequence's depth frames and ground-truth poses induce between the window's keyframes
+    (build_graph: frame numbers that are multiples of 10, at most 30 apart), masked by the forward-backward consistency rule, resident in a
+    FlowStore per keyframe window and gathered at the iteration's sampling_idx.
     -> final pose estimates [frames,4,4] (CPU), seconds spent in (tracking, mapping)."""
+    from nicer_slam_amd import flow_cues
     from nicer_slam_amd.feed import FrameFeed
     from nicer_slam_amd.model.loss import SLAMLoss
     from nicer_slam_amd.optim import Adam as HipAdam
@@ -370,10 +376,12 @@ def run_slam(engine, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_gr
     ]
     para_list = [g for g in para_list if len(g["params"])]
     optimizer = HipAdam(para_list, betas=(0.9, 0.99), eps=1e-15, none_grad=none_grad)   # (torch.optim.Adam's arithmetic, one pass per tensor)
-    # the family's loss block (runconf_replica_1.conf:45-57 / runconf_7scenes_1.conf:46-58) without the warp / flow terms
+    # the family's loss block (runconf_replica_1.conf:45-57 / runconf_7scenes_1.conf:46-58) without the warp terms; the flow term on request
     loss_fn = SLAMLoss(model=student, rgb_loss=lw["rgb_loss"], assign_scale_shift_init=lw["assign_scale_shift_init"],
                        eikonal_weight=lw["eikonal_weight"], smooth_weight=lw["smooth_weight"], depth_weight=lw["depth_weight"],
-                       normal_l1_weight=lw["normal_l1_weight"], normal_cos_weight=lw["normal_cos_weight"])
+                       normal_l1_weight=lw["normal_l1_weight"], normal_cos_weight=lw["normal_cos_weight"],
+                       flow_weight=lw["flow_weight"] if flow else 0.0)
+    flow_gt = [None, None, None]                                         # the live keyframe window, its edges and its FlowStore
     tracking_loss = SLAMLoss(model=student, rgb_loss="torch.nn.L1Loss", eikonal_weight=0, smooth_weight=0, depth_weight=0,
                              normal_l1_weight=0, normal_cos_weight=0)
     feed = FrameFeed((H, W), device=dev, capacity=frames)
@@ -387,6 +395,15 @@ def run_slam(engine, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_gr
             kf = list(local)
             feed.change_sampling_idx(max(1, map_pixels // len(kf)))
             indices, model_input, ground_truth = feed.batch(kf, full="store")
+            if flow:
+                if flow_gt[0] != kf:
+                    edges = flow_cues.build_graph(kf, device=dev)
+                    store = flow_cues.FlowStore.from_depth(depth[kf].reshape(len(kf), H, W), gt[kf], K, edges) if edges[0].numel() else None
+                    flow_gt[:] = [list(kf), edges, store]
+                _, edges, store = flow_gt
+                if store is not None:
+                    ground_truth["flow"], ground_truth["flow_mask"] = store.select(model_input["sampling_idx"], edges[0])
+                    ground_truth["edges"] = edges
             ba = frame_idx != 0 and it > int(map_iters * 0.7)
             if ba:
                 cams = torch.stack([get_tensor_from_camera((gt[0] if k == 0 else feed.frames[k]["pose"]).cpu()) for k in kf])
@@ -466,9 +483,11 @@ def run_slam(engine, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_gr
 
 
 def run_slam_table(frames=50, H=340, W=600, colour_grid=None, map_iters=100, track_iters=100, engines=("fused", "composed"), verbose=False,
-                   schedule="reference", seeds=(11,), family="replica", none_grads=("skip",), const_speed=False, analytic=False):
+                   schedule="reference", seeds=(11,), family="replica", none_grads=("skip",), const_speed=False, analytic=False,
+                   flow=False):
     """The mini-SLAM table: ATE of tracking + mapping on the synthetic sequence, fused engine beside the composed one; `none_grads`: the
-    optimizer semantics to run ("skip" = installed torch, "zeros" = the reference's torch 1.11)."""
+    optimizer semantics to run ("skip" = installed torch, "zeros" = the reference's torch 1.11).  flow: every cell is run twice, without
+    and with the flow term (run_slam(flow=True), keys ending in "_flow"), same seeds."""
     dev = torch.device("cuda", 0)
     teacher = build_teacher(H, W, colour_grid=colour_grid, device=dev, family=family)
     teacher.engine = "fused"
@@ -489,8 +508,12 @@ def run_slam_table(frames=50, H=340, W=600, colour_grid=None, map_iters=100, tra
            "frames": frames, "image": [H, W], "map_iters": map_iters, "track_iters": track_iters, "schedule": schedule,
            "no_tracking_baseline": summarise(gt, gt[:1].repeat(frames, 1, 1), scale)}
     log = (lambda f, l, what: print(f"  frame {f}: loss {l:.5f}  {what}", file=sys.stderr)) if verbose else None
-    for none_grad in none_grads:
-        tag = "" if none_grad == "skip" else "_none_grad_" + none_grad
+    if flow:
+        from nicer_slam_amd.utils.conf import run_conf
+        out["flow_term"] = {"flow_weight": run_conf(family)["loss"]["flow_weight"],
+                            "ground_truth": "flow_cues.FlowStore.from_depth on the sequence's depth frames and ground-truth poses, per keyframe window"}
+    for none_grad, with_flow in [(g, f) for g in none_grads for f in ((False, True) if flow else (False,))]:
+        tag = ("" if none_grad == "skip" else "_none_grad_" + none_grad) + ("_flow" if with_flow else "")
         for spec in engines:                     # "engine" or "engine:seed,seed,..." (the composed engine is ~11x slower: fewer seeds)
             eng, _, sd = spec.partition(":")
             runs = []
@@ -500,7 +523,7 @@ def run_slam_table(frames=50, H=340, W=600, colour_grid=None, map_iters=100, tra
                 t0 = time.perf_counter()
                 est, t_track, t_map = run_slam(eng, teacher, rgb, depth, normal, K, gt, H, W, frames, colour_grid, map_iters=map_iters,
                                                track_iters=track_iters, log=log, schedule=schedule, seed=seed, family=family,
-                                               none_grad=none_grad, const_speed=const_speed)
+                                               none_grad=none_grad, const_speed=const_speed, flow=with_flow)
                 runs.append(dict(summarise(gt, est, scale), seed=seed, wall_s=round(time.perf_counter() - t0, 1), tracking_s=round(t_track, 1),
                                  mapping_s=round(t_map, 1)))
             ates = [r["ate_rmse_scene_units"] for r in runs]
@@ -632,6 +655,7 @@ if __name__ == "__main__":
     ap.add_argument("--small-colour-grid", action="store_true", help="64 MiB colour table instead of the shipped 1 GiB (quick runs)")
     ap.add_argument("--no-free", action="store_true")
     ap.add_argument("--slam", action="store_true", help="the tracking + mapping table (map learned from the frames) instead of the tracking one")
+    ap.add_argument("--flow", action="store_true", help="--slam: run every cell without and with the flow term (ground truth from the sequence's depth)")
     ap.add_argument("--map-iters", type=int, default=100)
     ap.add_argument("--engines", default="fused,composed")
     ap.add_argument("--schedule", default="reference", choices=["reference", "fine"])
@@ -644,7 +668,7 @@ if __name__ == "__main__":
     if a.slam:
         print(json.dumps(run_slam_table(a.frames, H, W, cg, a.map_iters, a.iters, tuple(a.engines.split(",")), a.verbose, a.schedule,
                                         seeds=tuple(int(x) for x in a.seeds.split(",")), family=a.conf,
-                                        none_grads=tuple(a.none_grad.split(",")), const_speed=cs, analytic=a.analytic), indent=1))
+                                        none_grads=tuple(a.none_grad.split(",")), const_speed=cs, analytic=a.analytic, flow=a.flow), indent=1))
         sys.exit(0)
     print(json.dumps(run(a.frames, a.iters, a.pixels, H, W, a.oracle_frames, a.oracle_pixels, a.oracle_iters, cg,
                          not a.no_free, a.verbose, family=a.conf, const_speed=cs, n_samples=a.n_samples), indent=1))
