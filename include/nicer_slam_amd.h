@@ -917,6 +917,90 @@ int nsa_flowcue_consistency(const float *fwd, const float *bwd, const uint8_t *f
 int nsa_flowcue_select(const float *flows, const uint8_t *masks, uint32_t n_edges, uint64_t n_pixels, const int64_t *sampling_idx,
                        uint32_t b, uint32_t n, const int64_t *idii, float *out_flow, uint8_t *out_mask, nsa_stream_t stream);
 
+/* ---- Section 14: closest point on a triangle mesh (csrc/mesh_closest.hip) ---- */
+
+/* What trimesh.proximity.closest_point gives eval_rec.py:120-129 (distance_p2m): for every query point the closest point of a
+ * triangle mesh, the distance to it and the face it lies on.  verts[n_verts, 3] fp32, faces[n_faces, 3] int32, queries[n_queries, 3]
+ * fp32, all C-contiguous; counts below 2^31.  tests/p2m_ref.py restates this statement in numpy float64.
+ *
+ * Per (query q, face (a, b, c) in the order listed).  All arithmetic is float64 on the fp32 inputs, every operation rounded on its own
+ * (no FMA contraction), divisions are IEEE, and dot(u, v) = (u_x * v_x + u_y * v_y) + u_z * v_z:
+ *   ab = b - a ; ac = c - a ; ap = q - a ; bp = q - b ; cp = q - c                                        (component by component)
+ *   d1 = dot(ab, ap) ; d2 = dot(ac, ap) ; d3 = dot(ab, bp) ; d4 = dot(ac, bp) ; d5 = dot(ab, cp) ; d6 = dot(ac, cp)
+ *   vc = d1 * d4 - d3 * d2 ; vb = d5 * d2 - d1 * d6 ; va = d3 * d6 - d5 * d4
+ * The region classification of Ericson, Real-Time Collision Detection 5.1.5, in the book's order; (s, t) is that of the FIRST line
+ * whose test holds:
+ *   1 vertex a   d1 <= 0 and d2 <= 0                         s = 0 ; t = 0
+ *   2 vertex b   d3 >= 0 and d4 <= d3                        s = 1 ; t = 0
+ *   3 edge ab    vc <= 0 and d1 >= 0 and d3 <= 0             s = d1 / (d1 - d3) ; t = 0
+ *   4 vertex c   d6 >= 0 and d5 <= d6                        s = 0 ; t = 1
+ *   5 edge ac    vb <= 0 and d2 >= 0 and d6 <= 0             s = 0 ; t = d2 / (d2 - d6)
+ *   6 edge bc    va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0   w = (d4 - d3) / ((d4 - d3) + (d5 - d6)) ; s = 1 - w ; t = w
+ *   7 interior   otherwise                                   e = 1 / ((va + vb) + vc) ; s = vb * e ; t = vc * e
+ *   p = (a + s * ab) + t * ac ;  r = q - p ;  d2(q, face) = (r_x * r_x + r_y * r_y) + r_z * r_z
+ *
+ * Skipped faces.  A face is skipped -- never returned -- and counted in totals[3] (uint32, device; may be NULL) under the FIRST cause
+ * that holds:  totals[0] an index lies outside [0, n_verts);  totals[1] a vertex has a non-finite coordinate;  totals[2] ab x ac,
+ * (ab_y * ac_z - ab_z * ac_y, ab_z * ac_x - ab_x * ac_z, ab_x * ac_y - ab_y * ac_x) in float64, is exactly (0, 0, 0).  Dropping
+ * zero-area faces changes the surface on a set of measure zero only and keeps 1 / 0 out of line 7.
+ *
+ * Result per query.  The winner is the face with the smallest d2 over the faces not skipped (a NaN d2 never wins), ties to the LOWEST
+ * face index:  face_idx = its index;  d2 = its float64 d2;  closest (may be NULL) = its p, rounded once to fp32 on the store.
+ * A query with a non-finite coordinate gives (-1, NaN); a mesh without a usable face gives (-1, +inf); closest is NaN in both cases.
+ * The result is a function of (queries, verts, faces) alone and equals a brute force over all faces in this operation order on every
+ * input: the index only skips work.  No atomic takes part (the skip counts are a block reduction).
+ *
+ * Index: Section 8's grid -- bulk quantiles of a strided subsample, near-cubic cells, border clamping -- over the fp32
+ * centroids fp32(((a + b) + c) / 3) of the usable faces, at most min(2 * n_faces, 2^22) cells, each with the union of its faces'
+ * boxes.  A face longer than 2 cells on an axis, or with sigma = Lmax^2 / |ab x ac|^2 (Lmax its longest edge) above 2^16 / hmax^2
+ * (hmax the longest cell edge), or with its centroid more than 256 cells outside the grid, is kept on a separate list that every
+ * query walks (the large-face queue of Section 12 is the precedent).  Margins of the conservative bounds, each against the rounding of the quantity it bounds:
+ *   boxes        every bound moved outwards by 2^-40 of the larger bound's magnitude on that axis, then rounded outwards to fp32:
+ *                (a + s * ab) + t * ac is within 2^-50 of that magnitude of the exact combination;
+ *   (s, t)       in line 7 va, vb, vc are differences of products of magnitude L^2 D^2 (L the longest edge, D the largest distance
+ *                from q to a vertex of the face), each within 40 * 2^-53 * L^2 D^2 of its exact value, while their exact sum is
+ *                |ab x ac|^2; so p lies within rho * L of the triangle, rho = 2^-43 * sigma * D^2 (a factor 6 above that count), as
+ *                long as rho <= 1/4.  Lines 1-6 give s, t in [0, 1] by the monotonicity of rounding;
+ *   skip rule    a box (of a face, a cell, or of everything beyond a ring) at distance g is skipped only when rho <= 1/4 and
+ *                (g - rho * diag)^2 > best * (1 + 2^-40), with diag >= L; the 2^-40 is far above the float64 rounding of g^2.  With
+ *                rho > 1/4 nothing is skipped: a brute force.  Grid faces share one rho per query: sigma <= 2^16 / hmax^2,
+ *                L <= 2 |h|, and D <= the distance to the far corner of the grid faces' box, which is the box of all usable faces
+ *                clipped to 259 cells around the grid (a centroid at most 256 cells outside, a box of at most 2 cells, one cell
+ *                of margin).  A grid measures at most 2^10 cells a side, so rho <= 2^-27 * 3 * (1024 + 518)^2 = 0.053 for every
+ *                query inside that box, and reaches 1/4 when its far corner is 2^12.5 cells away.  A stray component farther out
+ *                than 256 cells goes on the list and costs every query a box test per face, not the pruning.  A listed face uses
+ *                its own sigma and D <= g + diag;
+ *   ring stop    per axis and side the cell plane at the ring, less 2^-9 cell (the fp32 cell index is off by less than 2^-12 cell),
+ *                less 2 cells and the padding (how far a grid face reaches beyond its centroid), combined with the query's
+ *                distance to the grid faces' box on the other axes, under the skip rule.
+ * The reach is the bound the construction gives (a box of at most 2 cells around a centroid inside it), not the largest extent found
+ * in the mesh: that would take a reduction over the faces for a stop rule at most 2/3 cell tighter.
+ * Worst cases: every face in one cell, every face on the list, or rho > 1/4 (a query 2^12.5 cells away) -- all are
+ * a brute force, slow and never wrong.
+ *
+ * Workspace: a function of n_faces alone, for any mesh:  with B = min(2 * n_faces, 2^22) and every array rounded up to 256 bytes,
+ *   256 + 4 (B + 3) + 24 B + 32 F + 5 * 4 F + 2^18   bytes   (<= 108 * n_faces + 2^18 + 3072).
+ * Nothing is allocated or synchronised; arguments are checked before the device is touched (NSA_EBADARG: a NULL array, n_verts = 0,
+ * n_faces = 0, a count of 2^31 or more); the index buffer belongs to the caller.  The index refers to the mesh by face number: the
+ * verts and faces given to nsa_tri_query are those given to nsa_tri_build, unchanged. */
+
+/* bytes of the index buffer for n_faces (>= 1) faces; 0 for an invalid count */
+uint64_t nsa_tri_workspace(uint32_t n_faces);
+
+/* Build the index into `index` (nsa_tri_workspace(n_faces) bytes, device, 256-byte aligned); totals[3] as above (may be NULL). */
+int nsa_tri_build(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, void *index, uint32_t *totals,
+                  nsa_stream_t stream);
+
+/* face_idx[n_queries] int32, d2[n_queries] float64, closest[n_queries, 3] fp32 or NULL.  n_queries = 0 returns 0 without a launch. */
+int nsa_tri_query(const void *index, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                  const float *queries, uint32_t n_queries, int32_t *face_idx, double *d2, float *closest, nsa_stream_t stream);
+
+/* The same query; evaluated[n_queries] uint32 (may be NULL) receives how many faces went through the full evaluation for each query
+ * -- a measurement of the index (tools/bench_mesh_closest.py), not part of the answer. */
+int nsa_tri_query_counted(const void *index, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                          const float *queries, uint32_t n_queries, int32_t *face_idx, double *d2, float *closest,
+                          uint32_t *evaluated, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -358,3 +358,13 @@ lib.nsa_flowcue_consistency.argtypes = [_p, _p, _p, _p, _u32, _u32, _u32, _f64, 
 lib.nsa_flowcue_select.restype = _i
 lib.nsa_flowcue_select.argtypes = [_p, _p, _u32, _u64, _p, _u32, _u32, _p, _p, _p, _p]
 EXPORTS += ["nsa_flowcue_induced", "nsa_flowcue_consistency", "nsa_flowcue_select"]
+
+lib.nsa_tri_workspace.restype = _u64
+lib.nsa_tri_workspace.argtypes = [_u32]
+lib.nsa_tri_build.restype = _i
+lib.nsa_tri_build.argtypes = [_p, _u32, _p, _u32, _p, _p, _p]
+lib.nsa_tri_query.restype = _i
+lib.nsa_tri_query.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p, _p]
+lib.nsa_tri_query_counted.restype = _i
+lib.nsa_tri_query_counted.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_tri_workspace", "nsa_tri_build", "nsa_tri_query", "nsa_tri_query_counted"]

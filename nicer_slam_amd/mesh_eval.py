@@ -8,7 +8,12 @@ trimesh's surface sampling.
 * ``mesh_metrics``: calc_3d_metric + calc_normal_consistency (eval_rec.py:143-166, 207-236) from one ICP and one sample set,
   optionally after the similarity of the trajectory evaluation and the removal of stray components (eval_rec.py:259-272,
   nicer_slam_amd/mesh_clean.py).
-* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale]``: the reference's printout.
+* ``TriIndex`` / ``closest_point`` / ``distance_p2m``: the exact closest point of a triangle mesh for each query point, in float64
+  (C ABI Section 14, csrc/mesh_closest.hip; trimesh.proximity.closest_point of eval_rec.py:120-129).
+* ``mesh_metrics(..., surface="mesh")``: the same metrics from the distance of each sample to the other mesh's SURFACE, which a
+  perfect reconstruction scores 0 on; the default ``surface="samples"`` is the reference's sample-to-sample form.
+* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale] [--surface mesh]``: the
+  reference's printout.
 
 Reductions over the distance arrays (means, counts, ICP's centroids and cross-covariance) run in torch float64: they are small
 and deterministic.  There is no CPU path: a missing GPU is an error.
@@ -114,6 +119,107 @@ def sample_surface(verts, faces, n, seed=0):
     return pts, fidx.long()
 
 
+def _faces(faces, name):
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError(f"{name}: faces must be a CUDA tensor [F, 3]")
+    if faces.shape[0] >= 1 << 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 faces")
+    if faces.dtype != torch.int32 and faces.numel() and (int(faces.min()) < -(1 << 31) or int(faces.max()) >= 1 << 31):
+        raise ValueError(f"{name}: face index outside int32")
+    return faces.to(torch.int32).contiguous()
+
+
+class TriIndex:
+    """Exact closest-point index over a triangle mesh (fp32 verts [V, 3], integer faces [F, 3]) on the device, built once and
+    queried any number of times (include/nicer_slam_amd.h Section 14).  The index refers to the mesh by face number, so it keeps
+    its own fp32 / int32 copies of both arrays; the tensors passed in may change afterwards.  Faces with an index outside
+    [0, V), a non-finite vertex or zero area are skipped and counted in ``skipped`` (in that order)."""
+
+    @torch.no_grad()
+    def __init__(self, verts, faces):
+        v = _points(verts, "TriIndex")
+        f = _faces(faces, "TriIndex")
+        if v.device != f.device:
+            raise ValueError("TriIndex: verts and faces on different devices")
+        if v.shape[0] == 0 or f.shape[0] == 0:
+            raise ValueError("TriIndex: empty mesh")
+        self.verts = v.clone() if v.data_ptr() == verts.data_ptr() else v
+        self.faces = f.clone() if f.data_ptr() == faces.data_ptr() else f
+        self.V, self.F = v.shape[0], f.shape[0]
+        self.device = v.device
+        self.buf = torch.empty(lib.nsa_tri_workspace(self.F), dtype=torch.uint8, device=v.device)
+        self._totals = torch.zeros(3, dtype=torch.int32, device=v.device)
+        check(lib.nsa_tri_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, self.buf.data_ptr(),
+                                self._totals.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
+
+    @property
+    def skipped(self):
+        """(bad index, non-finite vertex, zero area) face counts (a host copy: a synchronisation)"""
+        return tuple(int(x) for x in self._totals.cpu())
+
+    @torch.no_grad()
+    def query(self, points, counts=False, squared=False):
+        """(dist [m] float64, face [m] int64, closest [m, 3] fp32): the closest point of the mesh for each query, the distance
+        to it (the square root, in torch float64, of the kernel's float64 d2) and the face it lies on, ties to the lowest face
+        index.  A non-finite query gives (NaN, -1, NaN); a mesh without a usable face (+inf, -1, NaN).  ``squared=True`` returns the
+        kernel's d2 itself in place of dist; ``counts=True`` appends the number of faces fully evaluated per query [m] int64 (a
+        measurement of the index)."""
+        q = _points(points, "TriIndex.query")
+        if q.device != self.device:
+            raise ValueError("TriIndex.query: points on another device than the index")
+        m = q.shape[0]
+        face = torch.empty(m, dtype=torch.int32, device=q.device)
+        d2 = torch.empty(m, dtype=torch.float64, device=q.device)
+        closest = torch.empty(m, 3, dtype=torch.float32, device=q.device)
+        n_eval = torch.zeros(m, dtype=torch.int32, device=q.device) if counts else None
+        if m:
+            check(lib.nsa_tri_query_counted(self.buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F,
+                                            q.data_ptr(), m, face.data_ptr(), d2.data_ptr(), closest.data_ptr(),
+                                            n_eval.data_ptr() if counts else None,
+                                            torch.cuda.current_stream(q.device).cuda_stream))
+        out = (d2 if squared else torch.sqrt(d2), face.long(), closest)
+        return out + (n_eval.long(),) if counts else out
+
+    def layout(self):
+        """dict(cells per axis, cell size, faces in the grid, faces on the large list, faces skipped) of the built index (host
+        copies; a synchronisation -- for measurements, not for the query path).  Reads csrc/mesh_closest.hip's struct Grid at the head
+        of the index buffer and the start array 256 bytes in; a static_assert there holds the offsets used here."""
+        head = self.buf[:64].cpu().numpy()
+        h = head[12:24].view(np.float32)
+        R = head[36:48].view(np.uint32).astype(np.int64)
+        ncells = int(head[48:52].view(np.uint32)[0])
+        st = self.buf[256 + 4 * ncells:256 + 4 * (ncells + 3)].view(torch.int32).cpu().numpy()
+        return {"cells": R.tolist(), "cell size": h.tolist(), "grid faces": int(st[0]), "large faces": int(st[1] - st[0]),
+                "skipped faces": int(st[2] - st[1])}
+
+
+def _mesh_tensors(mesh, device=None):
+    v, f = mesh["verts"], mesh["faces"]
+    if torch.is_tensor(v) and v.is_cuda and torch.is_tensor(f) and f.is_cuda:
+        return v, f
+    return _as_cuda_mesh(mesh, device if device is not None else "cuda")
+
+
+@torch.no_grad()
+def closest_point(mesh, points):
+    """(closest [m, 3] fp32, dist [m] float64, face [m] int64) -- the order of trimesh.proximity.closest_point -- of ``points``
+    (CUDA tensor or array [m, 3]) on ``mesh`` (dict with ``verts`` and ``faces``, or a TriIndex)."""
+    if isinstance(mesh, TriIndex):
+        index = mesh
+    else:
+        index = TriIndex(*_mesh_tensors(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(np.asarray(points), dtype=torch.float32).reshape(-1, 3)
+    dist, face, closest = index.query(points.to(index.device))
+    return closest, dist, face
+
+
+@torch.no_grad()
+def distance_p2m(points, mesh):
+    """eval_rec.py:120-129: the distance of each point to the mesh [m] float64."""
+    return closest_point(mesh, points)[1]
+
+
 def _transform(p, T):
     """p [n, 3] float64 -> R p + t, as ((R0 x + R1 y) + R2 z) + t with every operation rounded on its own."""
     R, t = T[:3, :3], T[:3, 3]
@@ -208,7 +314,7 @@ def _as_cuda_mesh(m, device):
 
 @torch.no_grad()
 def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda", pre_transform=None, clean=None,
-                 region=None, adjust_scale=False, cull=None):
+                 region=None, adjust_scale=False, cull=None, surface="samples"):
     """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
     ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
     reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
@@ -226,7 +332,14 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     the reconstruction that some of these cameras saw (mesh_render.cull_mesh), after ``pre_transform`` and ``clean`` and
     before the ICP, and adds "culled face fraction" to the result.  The cameras look at the reconstruction AS IT IS AT THAT POINT: the
     poses (and the default near of 0.01) are in the frame and units the vertices have after the division by ``scale`` and after
-    ``pre_transform`` -- with ``scale`` other than 1, poses in the mesh file's own units would look at a mesh of another size."""
+    ``pre_transform`` -- with ``scale`` other than 1, poses in the mesh file's own units would look at a mesh of another size.
+    ``surface``: "samples" (the default, the reference's numbers) measures each sample against the other surface's SAMPLES; "mesh"
+    (not a step of the reference, which carries distance_p2m unused) measures it against the other MESH: the same samples from
+    the same seeds, accuracy = mean distance of the reconstruction's samples to the ground-truth mesh, completion = mean distance
+    of the ground truth's samples to the reconstruction's mesh, the normals term against the closest face's normal, everything
+    else from those two distance arrays (metrics_from_surfaces); the result then carries "surface": "mesh"."""
+    if surface not in ("samples", "mesh"):
+        raise ValueError(f"mesh_metrics: surface must be 'samples' or 'mesh', got {surface!r}")
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_metrics: needs a GPU")
     rv, rf = _as_cuda_mesh(rec, device)
@@ -261,7 +374,10 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
         rv = _transform(rv.double(), torch.from_numpy(T).to(rv.device)).float()
     rp, ri = sample_surface(rv, rf, n_points, seed)
     gp, gi = sample_surface(gv, gf, n_points, seed + 1)
-    out = metrics_from_samples(rp, _face_normals(rv, rf)[ri], gp, _face_normals(gv, gf)[gi])
+    if surface == "mesh":
+        out = metrics_from_surfaces(rp, _face_normals(rv, rf)[ri], (rv, rf), gp, _face_normals(gv, gf)[gi], (gv, gf))
+    else:
+        out = metrics_from_samples(rp, _face_normals(rv, rf)[ri], gp, _face_normals(gv, gf)[gi])
     out.update({"transformation": T, "icp fitness": fit, "icp rmse": rmse})
     out.update(extra)
     return out
@@ -286,6 +402,37 @@ def metrics_from_samples(rec_pts, rec_normals, gt_pts, gt_normals):
     return out
 
 
+def surface_metrics(d_acc, d_com, dot_acc, dot_com):
+    """The surface="mesh" arithmetic on float64 tensors (any device): ``d_acc`` the distances of the reconstruction's samples to
+    the ground-truth mesh, ``d_com`` those of the ground truth's samples to the reconstruction's mesh, ``dot_*`` the products
+    n_sample . n_closest_face of the same pairs.  Thresholds and comparisons are those of metrics_from_samples."""
+    acc, com = d_acc.double(), d_com.double()
+    out = {"accuracy": float(acc.mean()), "completion": float(com.mean()),
+           "completion ratio": float((com < COMPLETION_RATIO_THRESHOLD).double().mean()),
+           "normals": float(0.5 * dot_com.double().abs().mean() + 0.5 * dot_acc.double().abs().mean()),
+           "chamfer-L1": float(0.5 * (com.mean() + acc.mean())),
+           "chamfer-L2": float(0.5 * ((com * com).mean() + (acc * acc).mean()))}
+    for key, th in zip(("f-score", "f-score-15", "f-score-20"), F_THRESHOLDS):
+        p, r = float((acc <= th).double().mean()), float((com <= th).double().mean())
+        out[key] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    out["surface"] = "mesh"
+    return out
+
+
+@torch.no_grad()
+def metrics_from_surfaces(rec_pts, rec_normals, rec_mesh, gt_pts, gt_normals, gt_mesh, acc=None, com=None):
+    """The metrics of mesh_metrics(surface="mesh") on given samples (fp32 points, float64 unit normals) and meshes ((verts, faces)
+    CUDA tensors): accuracy from rec_pts against gt_mesh, completion from gt_pts against rec_mesh, the normals term
+    |n_sample . n_face| with n_face the unit normal of the closest face.  ``acc`` / ``com``: (dist, face) to use in place of the
+    two queries (a test feeds an oracle's)."""
+    d_acc, f_acc = acc if acc is not None else TriIndex(*gt_mesh).query(rec_pts)[:2]
+    d_com, f_com = com if com is not None else TriIndex(*rec_mesh).query(gt_pts)[:2]
+    if bool((f_acc < 0).any()) or bool((f_com < 0).any()):
+        raise ValueError("metrics_from_surfaces: a sample has no closest face (non-finite sample, or a mesh without a usable face)")
+    gn, rn = _face_normals(gt_mesh[0], gt_mesh[1].long()), _face_normals(rec_mesh[0], rec_mesh[1].long())
+    return surface_metrics(d_acc, d_com, (gn[f_acc] * rec_normals).sum(-1), (rn[f_com] * gt_normals).sum(-1))
+
+
 def main(argv=None):
     from .inference import read_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_eval", description=__doc__.splitlines()[0])
@@ -304,6 +451,8 @@ def main(argv=None):
     ap.add_argument("--cull-intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"))
     ap.add_argument("--cull-size", type=int, nargs=2, metavar=("H", "W"))
     ap.add_argument("--cull-mode", choices=("any", "all", "frustum"), default="any")
+    ap.add_argument("--surface", choices=("samples", "mesh"), default="samples",
+                    help="measure each sample against the other surface's samples (the reference) or against the other mesh itself")
     a = ap.parse_args(argv)
     if a.cull_poses and not (a.cull_intrinsics and a.cull_size):
         ap.error("--cull-poses needs --cull-intrinsics and --cull-size")
@@ -317,7 +466,10 @@ def main(argv=None):
         ap.error("--region goes with --clean touching or not_touching, and they need it")
     m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,
                      pre_transform=np.load(a.sim3) if a.sim3 else None, clean=a.clean,
-                     region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale, cull=cull)
+                     region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale, cull=cull,
+                     surface=a.surface)
+    if a.surface == "mesh":
+        print("surface: mesh (each sample against the other mesh's surface)")
     print("accuracy: ", m["accuracy"] * 100, "cm")
     print("completion: ", m["completion"] * 100, "cm")
     print("completion ratio: ", m["completion ratio"] * 100, "%")

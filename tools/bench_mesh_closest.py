@@ -1,0 +1,101 @@
+"""Time the closest-point-on-mesh path: TriIndex build and query for 200k surface samples against the 512^3 mesh of
+tools/bench_mesh.py's model (queries: samples of the mesh itself, the same samples pushed off the surface by N(0, 0.01), and uniform
+points of the bounding cube), the faces fully evaluated per query (the kernel's own count), the share of faces on the large list,
+and mesh_metrics end to end in both modes.  Device events, warm-up first, medians; per-kernel times come from a separate
+`rocprofv3 --kernel-trace --stats` run of this script.  Baseline: a chunked torch float64 brute force on the same GPU at a size it
+finishes in a few seconds (queries x faces given below), compared against the index on the same inputs.
+usage: python tools/bench_mesh_closest.py [reps=5] [resolution=512] [out=profiles/mesh_closest_bench.json]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+
+from nicer_slam_amd import inference, mesh_eval as M
+
+REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "mesh_closest_bench.json")
+
+
+def timed(fn, reps=REPS):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        torch.cuda.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return float(np.median(ms))
+
+
+def query_case(name, ix, q, out):
+    out[name + " query ms"] = timed(lambda: ix.query(q))
+    dist, _, _, n = ix.query(q, counts=True)
+    n = n.double()
+    out[name + " faces evaluated/query"] = {"mean": float(n.mean()), "median": float(n.median()), "max": int(n.max())}
+    out[name + " mean distance"] = float(dist.mean())
+
+
+def main():
+    out = {"reps": REPS}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    from bench_mesh import model
+    mesh = inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False)
+    v, f = mesh["verts"], mesh["faces"]
+    out["mesh V"], out["mesh F"] = int(v.shape[0]), int(f.shape[0])
+    out["index bytes"] = int(M.lib.nsa_tri_workspace(f.shape[0]))
+    ix = M.TriIndex(v, f)
+    out["build ms"] = timed(lambda: M.TriIndex(v, f))
+    lay = ix.layout()
+    out["layout"] = lay
+    out["large-list share"] = lay["large faces"] / f.shape[0]
+    out["skipped (index, non-finite, zero area)"] = list(ix.skipped)
+    surf, _ = M.sample_surface(v, f, 200000, 0)
+    query_case("on surface 200k", ix, surf, out)
+    near = surf + 0.01 * torch.randn(surf.shape, device="cuda", generator=g)
+    query_case("near surface (sigma 0.01) 200k", ix, near, out)
+    cube = torch.rand(200000, 3, device="cuda", generator=g) * 2 - 1
+    query_case("uniform in the cube 200k", ix, cube, out)
+
+    # the torch float64 brute force of the tests, at a size it finishes in a few seconds; the index on the same inputs beside it
+    from test_mesh_closest_gpu import _brute_torch
+    small = inference.extract_mesh(model(), 128, (-1.0, 1.0), color=False)
+    sv, sf = small["verts"], small["faces"]
+    sq = near[:16384].contiguous()
+    out["brute force size"] = [int(sq.shape[0]), int(sf.shape[0])]
+    res = {}
+    out["torch float64 brute force ms"] = timed(lambda: res.update(b=_brute_torch(sq, sv, sf)), reps=1)
+    six = M.TriIndex(sv, sf)
+    out["index at the brute-force size: build ms"] = timed(lambda: M.TriIndex(sv, sf))
+    out["index at the brute-force size: query ms"] = timed(lambda: six.query(sq))
+    d2, face, _ = six.query(sq, squared=True)
+    out["index equals the brute force"] = bool(np.array_equal(face.cpu().numpy(), res["b"][0])
+                                               and np.array_equal(d2.cpu().numpy(), res["b"][1]))
+
+    import eval_ref as E
+    T = E.rigid([0.2, 1.0, -0.4], 2.0, [0.01, -0.005, 0.008])
+    src = torch.from_numpy(E.transform(v.cpu().numpy().astype(np.float64), T).astype(np.float32)).cuda()
+    moved = {"verts": src, "faces": f}
+    for mode in ("samples", "mesh"):
+        met = {}
+        out[f"mesh_metrics surface={mode} ms"] = timed(lambda: met.update(M.mesh_metrics(moved, mesh, surface=mode)),
+                                                       reps=max(1, REPS // 2))
+        out[f"mesh_metrics surface={mode} accuracy, completion"] = [met["accuracy"], met["completion"]]
+    text = json.dumps(out, indent=1)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
+    with open(OUT, "w") as fh:
+        fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
