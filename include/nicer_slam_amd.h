@@ -1001,6 +1001,76 @@ int nsa_tri_query_counted(const void *index, const float *verts, uint32_t n_vert
                           const float *queries, uint32_t n_queries, int32_t *face_idx, double *d2, float *closest,
                           uint32_t *evaluated, nsa_stream_t stream);
 
+/* ---- Section 15: signed distance to a triangle mesh and range-limited queries (csrc/mesh_sdf.hip) ---- */
+
+/* Section 14's query with a sign and with a bound.  tests/sdf_ref.py restates this statement in numpy float64.
+ *
+ * Winner.  Everything about the winner is Section 14's, unchanged: the usable faces and the three skip causes, float64 with every
+ * operation rounded on its own, the order of the region tests, the smallest d2 with ties to the lowest face index, p rounded once to
+ * fp32 on the store.  face_idx, d2 and closest equal nsa_tri_query's bit for bit (where the bound lets them through).
+ *
+ * Feature.  The line of Section 14's classification that gave the winner's (s, t):
+ *   0 interior   1 vertex a   2 vertex b   3 edge ab   4 vertex c   5 edge ac   6 edge bc   -1 no winner
+ *
+ * Adjacency is by vertex index over a second int32 array adjacency_faces[n_faces, 3], with the numbering of `faces`, in which
+ * coincident vertices share an index (TriIndex fills it with `faces` after welding vertices whose fp32 coordinates are equal,
+ * -0 = +0).  A face CONTRIBUTES when it is usable under Section 14 and its three adjacency indices lie in [0, n_verts); an adjacency
+ * index outside that range is never dereferenced.
+ *
+ * Unit face normal, float64, divisions and the square root IEEE:
+ *   n_g = (ab x ac) / sqrt((x * x + y * y) + z * z),  (x, y, z) = ab x ac in Section 14's component order.
+ * Pseudo-normal N and weight W of the winner f's feature (Baerentzen & Aanaes 2005), sums from 0 in ascending g, N component by
+ * component as N + alpha_g * n_g (N + n_g on an edge):
+ *   interior      N = n_f, W = 1 (whether f contributes or not)
+ *   edge {i, j}   N = the sum of n_g over the contributing faces g that list both i and j (each once), W = their count: one on a
+ *                 boundary edge, all of them on a non-manifold edge
+ *   vertex i      N = the sum of alpha_g * n_g over the contributing corners at i, W = the sum of alpha_g,
+ *                 alpha_g = atan2(|u x w|, dot(u, w)), u and w the float64 edges from that corner to the next and to the previous
+ *                 corner of g (a -> b, c ; b -> c, a ; c -> a, b)
+ * with i, j the adjacency indices of f's corners.  Sign: e = q - p with p in float64 (before the store);  sign = -1 when
+ * dot(e, N) < 0, else +1 -- so d2 = 0, dot(e, N) = 0 and N = 0 all give +1 -- and a non-zero `flip` negates it.  Positive is the side
+ * ab x ac points to.  For a closed manifold mesh this is outside / inside exactly; for an open mesh it is the side of the nearest
+ * surface element.  Two coincident faces of opposite winding give N = 0 on their interior: +1.
+ *
+ * Bound.  max_d2 in float64; +inf = unbounded; NaN or negative is NSA_EBADARG.  The answer is the unbounded answer when its
+ * d2 <= max_d2 (equality included), otherwise (face -1, d2 +inf, closest NaN, feature -1, sign +1 before flip).  A non-finite query
+ * gives (-1, NaN, NaN, -1, +1 before flip).  The walk starts from the float64 after max_d2 as the distance to beat, so every skip
+ * rule of Section 14 prunes against the bound from the first cell on: the cost is set by the bound, not by the distance to the surface.
+ *
+ * What is bit-exact: face_idx, d2, closest, feature.  N and W are not (atan2 is not the same function in every maths library); the
+ * tests hold |N - N_ref| to 2^-40 W per component and the sign wherever |dot(e, N)| > 2^-36 |e| W.  The results are a function of the
+ * inputs alone: the adjacency is a stable sort, no atomic takes part.
+ *
+ * Adjacency workspace, a function of (n_verts, n_faces) alone, every array rounded up to 256 bytes:
+ *   4 (V + 2) + 5 * 12 F + 2^18   bytes   (<= 4 * n_verts + 60 * n_faces + 2^18 + 2048);   n_faces <= (2^31 - 1) / 3.
+ * A query whose winner's feature is a vertex of k contributing corners walks k of them; an edge walks the shorter of its two
+ * endpoints' lists.  Slow at a vertex of very high valence and never wrong.  nsa_tri_workspace and the index are unchanged. */
+
+/* bytes of the adjacency buffer; 0 for an invalid count */
+uint64_t nsa_tri_adjacency_workspace(uint32_t n_verts, uint32_t n_faces);
+
+/* Build the vertex -> face lists into `adjacency` (device, 256-byte aligned) from the mesh the index was built on and adjacency_faces. */
+int nsa_tri_adjacency_build(const float *verts, uint32_t n_verts, const int32_t *faces, const int32_t *adjacency_faces,
+                            uint32_t n_faces, void *adjacency, nsa_stream_t stream);
+
+/* face_idx[n_queries] int32, d2[n_queries] float64, closest[n_queries, 3] fp32 or NULL, feature[n_queries] int8, sign[n_queries] int8.
+ * n_queries = 0 returns 0 without a launch. */
+int nsa_tri_signed_query(const void *index, const void *adjacency, const float *verts, uint32_t n_verts, const int32_t *faces,
+                         const int32_t *adjacency_faces, uint32_t n_faces, const float *queries, uint32_t n_queries, double max_d2,
+                         int flip, int32_t *face_idx, double *d2, float *closest, int8_t *feature, int8_t *sign, nsa_stream_t stream);
+
+/* The same query; each may be NULL: normal[n_queries, 3] and weight[n_queries] float64 receive N and W (for the tests),
+ * evaluated[n_queries] and cells[n_queries] uint32 the faces fully evaluated and the grid cells looked at (empty ones included). */
+int nsa_tri_signed_query_counted(const void *index, const void *adjacency, const float *verts, uint32_t n_verts, const int32_t *faces,
+                                 const int32_t *adjacency_faces, uint32_t n_faces, const float *queries, uint32_t n_queries,
+                                 double max_d2, int flip, int32_t *face_idx, double *d2, float *closest, int8_t *feature, int8_t *sign,
+                                 double *normal, double *weight, uint32_t *evaluated, uint32_t *cells, nsa_stream_t stream);
+
+/* nsa_tri_query_counted under the bound (no sign, no adjacency); evaluated and cells as above, each may be NULL. */
+int nsa_tri_query_bounded(const void *index, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                          const float *queries, uint32_t n_queries, double max_d2, int32_t *face_idx, double *d2, float *closest,
+                          uint32_t *evaluated, uint32_t *cells, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

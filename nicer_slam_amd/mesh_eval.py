@@ -10,6 +10,8 @@ trimesh's surface sampling.
   nicer_slam_amd/mesh_clean.py).
 * ``TriIndex`` / ``closest_point`` / ``distance_p2m``: the exact closest point of a triangle mesh for each query point, in float64
   (C ABI Section 14, csrc/mesh_closest.hip; trimesh.proximity.closest_point of eval_rec.py:120-129).
+  ``TriIndex.signed_query`` and ``query(max_dist=)``: the signed and the range-limited form (C ABI Section 15, csrc/mesh_sdf.hip,
+  DESIGN 4n; nicer_slam_amd/mesh_sdf.py builds SDF grids and field metrics on them).
 * ``mesh_metrics(..., surface="mesh")``: the same metrics from the distance of each sample to the other mesh's SURFACE, which a
   perfect reconstruction scores 0 on; the default ``surface="samples"`` is the reference's sample-to-sample form.
 * ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale] [--surface mesh]``: the
@@ -129,6 +131,16 @@ def _faces(faces, name):
     return faces.to(torch.int32).contiguous()
 
 
+def _max_d2(max_dist, name):
+    """the float64 bound of header Section 15 for ``max_dist`` (None: +inf)"""
+    if max_dist is None:
+        return math.inf
+    d = float(max_dist)
+    if not d >= 0:
+        raise ValueError(f"{name}: max_dist must be >= 0 or None, got {max_dist!r}")
+    return d * d
+
+
 class TriIndex:
     """Exact closest-point index over a triangle mesh (fp32 verts [V, 3], integer faces [F, 3]) on the device, built once and
     queried any number of times (include/nicer_slam_amd.h Section 14).  The index refers to the mesh by face number, so it keeps
@@ -151,6 +163,7 @@ class TriIndex:
         self._totals = torch.zeros(3, dtype=torch.int32, device=v.device)
         check(lib.nsa_tri_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, self.buf.data_ptr(),
                                 self._totals.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
+        self._adjacency = {}                       # weld setting -> (adjacency faces, adjacency buffer), built on first use
 
     @property
     def skipped(self):
@@ -158,12 +171,14 @@ class TriIndex:
         return tuple(int(x) for x in self._totals.cpu())
 
     @torch.no_grad()
-    def query(self, points, counts=False, squared=False):
+    def query(self, points, counts=False, squared=False, max_dist=None):
         """(dist [m] float64, face [m] int64, closest [m, 3] fp32): the closest point of the mesh for each query, the distance
         to it (the square root, in torch float64, of the kernel's float64 d2) and the face it lies on, ties to the lowest face
         index.  A non-finite query gives (NaN, -1, NaN); a mesh without a usable face (+inf, -1, NaN).  ``squared=True`` returns the
         kernel's d2 itself in place of dist; ``counts=True`` appends the number of faces fully evaluated per query [m] int64 (a
-        measurement of the index)."""
+        measurement of the index).  ``max_dist`` (None: unbounded, the path of every call without it): only a closest point with
+        d2 <= max_dist^2 counts, any other query gives (+inf, -1, NaN), and the walk stops once nothing within max_dist is left
+        (header Section 15); ``counts=True`` then appends the cells visited per query as well."""
         q = _points(points, "TriIndex.query")
         if q.device != self.device:
             raise ValueError("TriIndex.query: points on another device than the index")
@@ -172,6 +187,18 @@ class TriIndex:
         d2 = torch.empty(m, dtype=torch.float64, device=q.device)
         closest = torch.empty(m, 3, dtype=torch.float32, device=q.device)
         n_eval = torch.zeros(m, dtype=torch.int32, device=q.device) if counts else None
+        if max_dist is not None:
+            n_cells = torch.zeros(m, dtype=torch.int32, device=q.device) if counts else None
+            if m:
+                check(lib.nsa_tri_query_bounded(self.buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F,
+                                                q.data_ptr(), m, _max_d2(max_dist, "TriIndex.query"), face.data_ptr(), d2.data_ptr(),
+                                                closest.data_ptr(), n_eval.data_ptr() if counts else None,
+                                                n_cells.data_ptr() if counts else None,
+                                                torch.cuda.current_stream(q.device).cuda_stream))
+            else:
+                _max_d2(max_dist, "TriIndex.query")
+            out = (d2 if squared else torch.sqrt(d2), face.long(), closest)
+            return out + (n_eval.long(), n_cells.long()) if counts else out
         if m:
             check(lib.nsa_tri_query_counted(self.buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F,
                                             q.data_ptr(), m, face.data_ptr(), d2.data_ptr(), closest.data_ptr(),
@@ -179,6 +206,72 @@ class TriIndex:
                                             torch.cuda.current_stream(q.device).cuda_stream))
         out = (d2 if squared else torch.sqrt(d2), face.long(), closest)
         return out + (n_eval.long(),) if counts else out
+
+    def adjacency(self, weld=True):
+        """(adjacency faces [F, 3] int32, adjacency buffer) of header Section 15, built on first use and kept, once per ``weld``
+        setting.  ``weld=True`` names every vertex by the rank of its fp32 coordinates among the distinct ones (-0 = +0; a face
+        with a non-finite vertex is skipped whatever its names are) -- ``torch.unique`` of the coordinates on the device
+        -- so that a mesh whose seams repeat vertices is connected across them; ``weld=False`` takes the faces as they are."""
+        weld = bool(weld)
+        if weld not in self._adjacency:
+            adj = self.faces
+            if weld:
+                # + 0.0: -0 becomes +0.  A non-finite vertex is named as (0, 0, 0): NaN rows break the sort inside torch.unique,
+                # and what they share a name with does not matter, as no face with such a vertex contributes
+                finite = torch.isfinite(self.verts).all(1, keepdim=True)
+                _, inverse = torch.unique(torch.where(finite, self.verts + 0.0, torch.zeros_like(self.verts)), dim=0,
+                                          return_inverse=True)
+                ok = ((self.faces >= 0) & (self.faces < self.V)).all(1, keepdim=True)
+                safe = torch.where(ok, self.faces, torch.zeros_like(self.faces)).long()
+                adj = torch.where(ok, inverse[safe].to(torch.int32), self.faces).contiguous()
+            nbytes = lib.nsa_tri_adjacency_workspace(self.V, self.F)
+            if nbytes == 0:
+                raise ValueError("TriIndex.adjacency: more than (2^31 - 1) / 3 faces")
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            check(lib.nsa_tri_adjacency_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), adj.data_ptr(), self.F,
+                                              buf.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            self._adjacency[weld] = (adj, buf)
+        return self._adjacency[weld]
+
+    @torch.no_grad()
+    def signed_query(self, points, max_dist=None, flip=False, weld=True, counts=False, normals=False):
+        """(signed dist [m] float64, face [m] int64, closest [m, 3] fp32, feature [m] int8): ``query``'s answer with the sign of the
+        angle-weighted pseudo-normal of the closest feature (header Section 15; Baerentzen & Aanaes 2005): positive on the side the
+        faces' ab x ac points to, negative on the other, ``flip`` the opposite.  Exact inside / outside for a closed manifold mesh;
+        for an open one the side of the nearest surface element.  ``feature``: 0 interior, 1 / 2 / 4 vertex a / b / c, 3 / 5 / 6
+        edge ab / ac / bc of ``face``, -1 without one.  A non-finite query gives (NaN, -1, NaN, -1); a query with nothing within
+        ``max_dist`` (None: unbounded), or a mesh without a usable face, (+inf, -1, NaN, -1) -- -inf with ``flip``.
+        ``normals=True`` appends N [m, 3] and W [m] float64; ``counts=True`` then the faces evaluated and the cells visited [m] int64."""
+        q = _points(points, "TriIndex.signed_query")
+        if q.device != self.device:
+            raise ValueError("TriIndex.signed_query: points on another device than the index")
+        max_d2 = _max_d2(max_dist, "TriIndex.signed_query")
+        m = q.shape[0]
+        dev = q.device
+        face = torch.empty(m, dtype=torch.int32, device=dev)
+        d2 = torch.empty(m, dtype=torch.float64, device=dev)
+        closest = torch.empty(m, 3, dtype=torch.float32, device=dev)
+        feature = torch.empty(m, dtype=torch.int8, device=dev)
+        sign = torch.empty(m, dtype=torch.int8, device=dev)
+        N = torch.zeros(m, 3, dtype=torch.float64, device=dev) if normals else None
+        W = torch.zeros(m, dtype=torch.float64, device=dev) if normals else None
+        n_eval = torch.zeros(m, dtype=torch.int32, device=dev) if counts else None
+        n_cells = torch.zeros(m, dtype=torch.int32, device=dev) if counts else None
+        if m:
+            adj, buf = self.adjacency(weld)
+            check(lib.nsa_tri_signed_query_counted(self.buf.data_ptr(), buf.data_ptr(), self.verts.data_ptr(), self.V,
+                                                   self.faces.data_ptr(), adj.data_ptr(), self.F, q.data_ptr(), m, max_d2,
+                                                   1 if flip else 0, face.data_ptr(), d2.data_ptr(), closest.data_ptr(),
+                                                   feature.data_ptr(), sign.data_ptr(), N.data_ptr() if normals else None,
+                                                   W.data_ptr() if normals else None, n_eval.data_ptr() if counts else None,
+                                                   n_cells.data_ptr() if counts else None,
+                                                   torch.cuda.current_stream(dev).cuda_stream))
+        out = (sign.double() * torch.sqrt(d2), face.long(), closest, feature)
+        if normals:
+            out += (N, W)
+        if counts:
+            out += (n_eval.long(), n_cells.long())
+        return out
 
     def layout(self):
         """dict(cells per axis, cell size, faces in the grid, faces on the large list, faces skipped) of the built index (host

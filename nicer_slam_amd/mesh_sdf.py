@@ -1,0 +1,175 @@
+"""The signed distance field of a triangle mesh on the device (C ABI Section 15, csrc/mesh_sdf.hip), on the closest-point
+index of mesh_eval.TriIndex.
+
+* ``signed_distance(mesh, points)``: the exact distance of each point to the mesh with the sign of the angle-weighted pseudo-normal
+  of the closest feature (Baerentzen & Aanaes 2005): positive on the side the faces' normals point to.
+* ``contains(mesh, points)``: whether each point lies inside a CLOSED mesh.
+* ``mesh_sdf_grid(mesh, resolution, ...)``: a narrow-band SDF volume of the mesh, NaN outside the band, in the point order of
+  inference.get_grid_uniform; inference.marching_cubes meshes it as it is.
+* ``sdf_field_metrics(sdf, mesh, ...)``: the learned SDF field (a model, through inference.sdf_values, or any callable) against the
+  mesh's signed distance at points scattered about its surface -- the field itself, not its marching-cubes level set.
+* ``python -m nicer_slam_amd.mesh_sdf MESH.ply --resolution R --bounds LO HI --band B --out SDF.npy [--flip] [--points P.npy
+  --out-dist D.npy]``.
+
+For an open mesh the sign is that of the nearest surface element, not an inside / outside test.  There is no CPU path: a missing GPU
+is an error.
+"""
+import argparse
+import math
+
+import numpy as np
+import torch
+
+from .mesh_eval import TriIndex, _mesh_tensors, sample_surface
+
+
+def _index(mesh, points=None):
+    if isinstance(mesh, TriIndex):
+        return mesh
+    return TriIndex(*_mesh_tensors(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
+
+
+def _on_device(points, index):
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(np.asarray(points), dtype=torch.float32).reshape(-1, 3)
+    return points.to(index.device)
+
+
+@torch.no_grad()
+def signed_distance(mesh, points, max_dist=None, flip=False, weld=True):
+    """[m] float64: the signed distance of ``points`` (CUDA tensor or array [m, 3]) to ``mesh`` (dict with ``verts`` and ``faces``, or
+    a TriIndex): ``TriIndex.signed_query(...)[0]``.  +inf (-inf with ``flip``) where nothing lies within ``max_dist``."""
+    index = _index(mesh, points)
+    return index.signed_query(_on_device(points, index), max_dist=max_dist, flip=flip, weld=weld)[0]
+
+
+@torch.no_grad()
+def contains(mesh, points, flip=False, weld=True):
+    """[m] bool: whether each point lies strictly inside ``mesh`` -- a CLOSED manifold mesh with outward normals (``flip`` for inward
+    ones).  A point on the surface, and a non-finite point, is not inside.  On an open mesh the answer is the side of the nearest
+    surface element and says nothing about an inside."""
+    return signed_distance(mesh, points, flip=flip, weld=weld) < 0
+
+
+def grid_axis(resolution, grid_boundary, device):
+    """the fp32 axis values of inference.get_grid_uniform / sdf_grid"""
+    return torch.linspace(grid_boundary[0], grid_boundary[1], resolution, dtype=torch.float64, device=device).float()
+
+
+def grid_points(ax, lo, hi):
+    """points lo .. hi - 1 of inference.get_grid_uniform's list over the axis values ``ax``: the flat index runs over (y, x, z)"""
+    R = ax.shape[0]
+    flat = torch.arange(lo, hi, device=ax.device)
+    iy = flat // (R * R)
+    ix = (flat // R) % R
+    iz = flat % R
+    return torch.stack([ax[ix], ax[iy], ax[iz]], -1)
+
+
+@torch.no_grad()
+def mesh_sdf_grid(mesh, resolution, grid_boundary=(-1, 1), band=None, flip=False, chunk=1 << 22, weld=True):
+    """fp32 [R, R, R]: the signed distance to ``mesh`` at the points of ``inference.get_grid_uniform(R, grid_boundary)``, in that
+    list's order (the flat index runs over (y, x, z); ``.permute(1, 0, 2)`` is the (x, y, z) volume inference.marching_cubes takes,
+    as in inference.sdf_grid).  ``band`` (a distance; None: none): points farther than it from the mesh are NaN, and their queries
+    stop after the few rings the band reaches -- without it a grid over the whole cube is the slow case of DESIGN 4m.
+    inference.marching_cubes emits no face for a cell with a non-finite corner, so the volume can be meshed as it is."""
+    resolution = int(resolution)
+    if resolution < 2 or resolution ** 3 >= 1 << 40:
+        raise ValueError(f"mesh_sdf_grid: resolution {resolution} out of range")
+    if not float(grid_boundary[1]) > float(grid_boundary[0]):
+        raise ValueError("mesh_sdf_grid: grid_boundary must be (lo, hi) with hi > lo")
+    if band is not None and not float(band) >= 0:
+        raise ValueError("mesh_sdf_grid: band must be >= 0 or None")
+    if chunk < 1:
+        raise ValueError("mesh_sdf_grid: chunk must be >= 1")
+    index = _index(mesh)
+    ax = grid_axis(resolution, grid_boundary, index.device)
+    n = resolution ** 3
+    out = torch.empty(n, dtype=torch.float32, device=index.device)
+    for lo in range(0, n, chunk):
+        hi = min(lo + chunk, n)
+        d = index.signed_query(grid_points(ax, lo, hi), max_dist=band, flip=flip, weld=weld)[0]
+        out[lo:hi] = torch.where(torch.isfinite(d), d, torch.full_like(d, math.nan)).float()
+    return out.view(resolution, resolution, resolution)
+
+
+def field_metrics(f, d, band):
+    """The arithmetic of sdf_field_metrics on tensors of any device: ``f`` the field's values and ``d`` the mesh's signed distances at
+    the same points.  Only points with |d| <= band count (a non-finite d does not)."""
+    f, d = f.double().reshape(-1), d.double().reshape(-1)
+    use = torch.isfinite(d) & (d.abs() <= band)
+    k = int(use.sum())
+    if k == 0:
+        return {"mean abs error": math.nan, "rms error": math.nan, "sign agreement": math.nan, "points": 0}
+    err = (f[use] - d[use]).abs()
+    same = (f[use] < 0) == (d[use] < 0)
+    return {"mean abs error": float(err.mean()), "rms error": math.sqrt(float((err * err).mean())),
+            "sign agreement": float(same.double().mean()), "points": k}
+
+
+@torch.no_grad()
+def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0, flip=False, weld=True):
+    """The SDF field ``sdf`` against the signed distance to ``mesh`` (the ground truth, or any surface the field should be the SDF
+    of).  ``sdf``: a model (evaluated through inference.sdf_values) or a callable taking CUDA points [n, 3] fp32 and returning [n]
+    values.  The points are ``mesh_eval.sample_surface(mesh, n_points, seed)`` each moved by a draw of N(0, sigma^2) per coordinate
+    from a torch generator seeded with ``seed``, so they lie on both sides of the surface and on it.  Of the points within ``band``
+    of the mesh: "mean abs error" and "rms error" of |f - d|, "sign agreement" (the share with (f < 0) == (d < 0)) and "points" (how
+    many counted).  ``flip``: the mesh's normals point inwards."""
+    if not (n_points > 0 and sigma >= 0 and band >= 0):
+        raise ValueError("sdf_field_metrics: needs n_points > 0, sigma >= 0 and band >= 0")
+    index = _index(mesh)
+    pts, _ = sample_surface(index.verts, index.faces, int(n_points), seed)
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    noise = torch.randn(pts.shape, generator=gen, dtype=torch.float64) * float(sigma)
+    pts = (pts.double() + noise.to(pts.device)).float()
+    d = index.signed_query(pts, max_dist=band, flip=flip, weld=weld)[0]
+    if callable(sdf) and not isinstance(sdf, torch.nn.Module):
+        f = sdf(pts)
+    else:
+        from . import inference
+        f = inference.sdf_values(sdf, pts)
+    if not (torch.is_tensor(f) and f.numel() == pts.shape[0]):
+        raise ValueError("sdf_field_metrics: the field must return one value per point")
+    return field_metrics(f.to(d.device), d, float(band))
+
+
+def main(argv=None):
+    from .inference import read_ply
+    ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_sdf", description=__doc__.splitlines()[0])
+    ap.add_argument("mesh")
+    ap.add_argument("--resolution", type=int, help="write the [R, R, R] narrow-band SDF grid to --out")
+    ap.add_argument("--bounds", type=float, nargs=2, default=(-1.0, 1.0), metavar=("LO", "HI"))
+    ap.add_argument("--band", type=float, help="distance beyond which the grid (and --out-dist) is NaN")
+    ap.add_argument("--out", metavar="SDF.npy")
+    ap.add_argument("--flip", action="store_true", help="the mesh's normals point inwards")
+    ap.add_argument("--points", metavar="P.npy", help="[m, 3] points to measure as well")
+    ap.add_argument("--out-dist", metavar="D.npy", help="their signed distances, float64")
+    a = ap.parse_args(argv)
+    if (a.resolution is None) != (a.out is None):
+        ap.error("--resolution and --out go together")
+    if (a.points is None) != (a.out_dist is None):
+        ap.error("--points and --out-dist go together")
+    if a.resolution is None and a.points is None:
+        ap.error("nothing to do: give --resolution and --out, or --points and --out-dist")
+    if not torch.cuda.is_available():
+        raise RuntimeError("mesh_sdf: needs a GPU")
+    index = _index(read_ply(a.mesh))
+    result = {}
+    if a.resolution is not None:
+        grid = mesh_sdf_grid(index, a.resolution, tuple(a.bounds), a.band, a.flip)
+        np.save(a.out, grid.cpu().numpy())
+        inside = int(torch.isfinite(grid).sum())
+        print(f"grid: {a.resolution}^3 over [{a.bounds[0]}, {a.bounds[1]}], {inside} points within the band -> {a.out}")
+        result["grid"] = grid
+    if a.points is not None:
+        pts = np.load(a.points).reshape(-1, 3)
+        d = signed_distance(index, pts, a.band, a.flip)
+        d = torch.where(torch.isfinite(d), d, torch.full_like(d, math.nan))
+        np.save(a.out_dist, d.cpu().numpy())
+        print(f"points: {pts.shape[0]}, {int(torch.isfinite(d).sum())} within the band -> {a.out_dist}")
+        result["dist"] = d
+    return result
+
+
+if __name__ == "__main__":
+    main()

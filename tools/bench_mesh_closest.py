@@ -1,7 +1,9 @@
 """Time the closest-point-on-mesh path: TriIndex build and query for 200k surface samples against the 512^3 mesh of
 tools/bench_mesh.py's model (queries: samples of the mesh itself, the same samples pushed off the surface by N(0, 0.01), and uniform
 points of the bounding cube), the faces fully evaluated per query (the kernel's own count), the share of faces on the large list,
-and mesh_metrics end to end in both modes.  Device events, warm-up first, medians; per-kernel times come from a separate
+and mesh_metrics end to end in both modes; then the signed and the range-limited queries of DESIGN 4n on the same mesh and queries:
+signed against unsigned, the uniform points under a band of 2, 5 and 20 cells, the adjacency build and its bytes, the incident faces
+walked per query, and mesh_sdf_grid at 256^3 with a band of 4 voxels.  Device events, warm-up first, medians; per-kernel times come from a separate
 `rocprofv3 --kernel-trace --stats` run of this script.  Baseline: a chunked torch float64 brute force on the same GPU at a size it
 finishes in a few seconds (queries x faces given below), compared against the index on the same inputs.
 usage: python tools/bench_mesh_closest.py [reps=5] [resolution=512] [out=profiles/mesh_closest_bench.json]"""
@@ -45,6 +47,58 @@ def query_case(name, ix, q, out):
     out[name + " mean distance"] = float(dist.mean())
 
 
+def walked(ix, face, feature):
+    """incident corners each query's pseudo-normal walked: the vertex's list, the shorter endpoint list of an edge, 0 inside a face
+    (read from the adjacency buffer: start[V + 2] at its head, csrc/mesh_sdf.hip)"""
+    adj, buf = ix.adjacency(True)
+    start = buf[:4 * (ix.V + 2)].view(torch.int32).long()
+    val = start[1:ix.V + 1] - start[:ix.V]
+    ft = feature.long().clamp_min(0)
+    names = adj.long()[face.clamp_min(0)]                                        # [m, 3]
+    first = torch.tensor([0, 0, 1, 0, 2, 0, 1], device=face.device)[ft]         # per feature code: a corner, and the other end of an edge
+    second = torch.tensor([0, 0, 1, 1, 2, 2, 2], device=face.device)[ft]
+    n = torch.minimum(val[names.gather(1, first[:, None])[:, 0]], val[names.gather(1, second[:, None])[:, 0]])
+    return torch.where((feature > 0) & (face >= 0), n, torch.zeros_like(n)).double()
+
+
+def signed_case(name, ix, q, out):
+    out[name + " signed query ms"] = timed(lambda: ix.signed_query(q))
+    dist, face, _, feature = ix.signed_query(q)
+    n = walked(ix, face, feature)
+    out[name + " incident faces walked/query"] = {"mean": float(n.mean()), "max": int(n.max())}
+    out[name + " share negative"] = float((dist < 0).double().mean())
+    out[name + " features (interior, vertex, edge)"] = [float((feature == 0).double().mean()),
+                                                        float(((feature == 1) | (feature == 2) | (feature == 4)).double().mean()),
+                                                        float(((feature == 3) | (feature == 5) | (feature == 6)).double().mean())]
+
+
+def sdf_rows(ix, surf, near, cube, out):
+    from nicer_slam_amd import mesh_sdf
+    out["adjacency bytes"] = int(M.lib.nsa_tri_adjacency_workspace(ix.V, ix.F))
+
+    def build():
+        ix._adjacency.clear()
+        ix.adjacency(True)
+
+    out["adjacency build ms (weld included)"] = timed(build)
+    signed_case("on surface 200k", ix, surf, out)
+    signed_case("near surface (sigma 0.01) 200k", ix, near, out)
+    h = max(ix.layout()["cell size"])
+    for cells in (2, 5, 20):
+        band = cells * h
+        key = f"uniform in the cube 200k, band {cells} cells"
+        out[key + " query ms"] = timed(lambda: ix.query(cube, max_dist=band))
+        out[key + " signed query ms"] = timed(lambda: ix.signed_query(cube, max_dist=band))
+        _, face, _, n_eval, n_cells = ix.query(cube, counts=True, max_dist=band)
+        out[key + " within"] = float((face >= 0).double().mean())
+        out[key + " faces evaluated/query"] = {"mean": float(n_eval.double().mean()), "max": int(n_eval.max())}
+        out[key + " cells visited/query"] = {"mean": float(n_cells.double().mean()), "max": int(n_cells.max())}
+    res = {}
+    out["mesh_sdf_grid 256^3, band 4 voxels, ms"] = timed(lambda: res.update(g=mesh_sdf.mesh_sdf_grid(ix, 256, (-1.0, 1.0),
+                                                                                                   band=4 * 2.0 / 255)), reps=max(1, REPS // 2))
+    out["mesh_sdf_grid 256^3 share within the band"] = float(torch.isfinite(res["g"]).double().mean())
+
+
 def main():
     out = {"reps": REPS}
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -65,6 +119,7 @@ def main():
     query_case("near surface (sigma 0.01) 200k", ix, near, out)
     cube = torch.rand(200000, 3, device="cuda", generator=g) * 2 - 1
     query_case("uniform in the cube 200k", ix, cube, out)
+    sdf_rows(ix, surf, near, cube, out)
 
     # the torch float64 brute force of the tests, at a size it finishes in a few seconds; the index on the same inputs beside it
     from test_mesh_closest_gpu import _brute_torch
