@@ -1071,6 +1071,73 @@ int nsa_tri_query_bounded(const void *index, const float *verts, uint32_t n_vert
                           const float *queries, uint32_t n_queries, double max_d2, int32_t *face_idx, double *d2, float *closest,
                           uint32_t *evaluated, uint32_t *cells, nsa_stream_t stream);
 
+/* ---- Section 16: generalised winding number of a triangle mesh (csrc/mesh_winding.hip) ---- */
+
+/* w(q) = (1 / 4 pi) * the sum of the signed solid angles under which the faces are seen from q (Jacobson et al. 2013): 1 inside and 0
+ * outside a closed mesh with outward normals, and on an open mesh a smooth field that is 1/2 across a hole's virtual closure -- the
+ * inside / outside test Section 15's sign is not.  Two forms behind one entry point: the exact sum, and the hierarchical first-order
+ * approximation of Barill et al. 2018 whose cost per query does not grow with n_faces.  tests/winding_ref.py restates this statement
+ * in numpy float64.  verts, faces, queries as in Section 14; the tree is independent of Section 14's index.
+ *
+ * Faces and arithmetic.  The usable faces are exactly Section 14's.  Everything is float64 on the fp32 inputs, every operation
+ * rounded on its own (no FMA contraction), dot(u, w) and u x w in Section 14's component order.
+ *
+ * Solid angle of face (a, b, c) from q (Van Oosterom & Strackee 1983):
+ *   A = a - q ; B = b - q ; C = c - q ;  lA = sqrt(dot(A, A)) ; lB, lC alike
+ *   det = dot(A, B x C)
+ *   den = ((lA * lB) * lC + dot(A, B) * lC) + (dot(A, C) * lB + dot(B, C) * lA)
+ *   Omega = 2 * atan2(det, den), and Omega = 0 when det == 0: a query on a vertex or in a face's plane gets a defined value.
+ * A face whose ab x ac points AWAY from q contributes Omega > 0.  The open unit square in z = 0 with normals +z gives
+ * w = +-(1 / pi) atan(1 / (2 h sqrt(4 h^2 + 2))) at (1/2, 1/2, -+h): 1/6 at h = 1/2.
+ *
+ * Tree.  lo_k = the least coordinate k over the vertices of the usable faces (-0 as +0), side = the largest of the three extents,
+ * L = the smallest integer with 8 * 4^L >= F_usable, at most 10.  A usable face has centroid ((a + b) + c) / 3 and lies in the leaf cell
+ *   cell_k = (uint32) min(max((centroid_k - lo_k) * (2^L / side), 0), 2^L - 1)
+ * with the 3 L-bit Morton code of (cell_x, cell_y, cell_z), x the highest bit of each triple, as its key.  The faces are taken in the
+ * order of a stable sort by key (ascending face index within a leaf).  A node exists for every level l in [0, L] and every distinct
+ * prefix key >> 3 (L - l); its faces are contiguous in that order.  Per face n_t = (ab x ac) * 0.5 and
+ * area_t = sqrt((n_x * n_x + n_y * n_y) + n_z * n_z).  Per node, every sum from +0, component by component:
+ *   leaf     N = sum n_t ;  area = sum area_t ;  M = sum area_t * centroid_t   over its faces in sorted order
+ *   parent   the same three sums over its children in ascending key order (a lone child is repeated bit for bit)
+ *   P = M / area ;  r2 = the largest dot(v - P, v - P) over the vertices v of its faces (a maximum: the same bits in any order)
+ * Nodes are numbered in pre-order, children in ascending key order.  No atomic takes part: the order of every sum is fixed by the
+ * sort, and two builds give identical bits.
+ *
+ * Query.  S = +0 and i = 0; while i < node count, with d = P_i - q and d2 = dot(d, d):
+ *   d2 > beta^2 * r2_i    S = S + dot(N_i, d) / (d2 * sqrt(d2)) ; go to the first node behind i's subtree      (accepted += 1)
+ *   else, at a leaf       S = S + Omega for each of its faces in sorted order ; go to i + 1                    (evaluated += faces)
+ *   else                  go to i + 1
+ * w = S / (4 pi) with 4 pi = 0x1.921fb54442d18p+3, negated by a non-zero `flip`.  beta^2 = beta * beta is formed once on the host.
+ * beta = +inf never accepts a node: w is the exact sum over the usable faces in sorted order.  beta < 1 or NaN is NSA_EBADARG; 2 is the
+ * value of Barill et al. and the default of the Python layer.  A query with a non-finite coordinate gives NaN and counts 0; a mesh
+ * without a usable face gives +0 (-0 with flip).
+ *
+ * What is bit-exact between implementations: the tree (keys, order, N, area, M, P, r2), every accept decision whose
+ * |d2 - beta^2 r2| exceeds the rounding of both sides, and hence `accepted` and `evaluated`; w differs only through atan2, which is
+ * not the same function in every maths library.  Worst cases, slow and never wrong: every face in one leaf (coincident centroids); a
+ * query on the surface, which descends to the leaves about it.  A query far from the mesh accepts the root: one node.
+ *
+ * Workspace, a function of n_faces alone, every array rounded up to 256 bytes, with K(F) = the sum over l in [0, L(F)] of
+ * min(8^l, F) (the most nodes a mesh of F faces can have; K(F) < 3.5 F for F >= 8):
+ *   256 + 6 * 4 F + 4 + 100 K(F) + 2^18   bytes.
+ * Nothing is allocated or synchronised; arguments are checked before the device is touched.  n_queries = 0 and n_faces = 0 return 0
+ * without a launch (nothing is written).  The tree refers to the mesh by face number: the verts and faces given to
+ * nsa_tri_winding_query are those given to nsa_tri_winding_build, unchanged. */
+
+/* bytes of the tree buffer for n_faces (>= 1) faces; 0 for an invalid count */
+uint64_t nsa_tri_winding_workspace(uint32_t n_faces);
+
+/* Build the tree into `tree` (nsa_tri_winding_workspace(n_faces) bytes, device, 256-byte aligned).  info[3] (uint32, device; may be
+ * NULL) receives L, the node count and the number of usable faces. */
+int nsa_tri_winding_build(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, void *tree, uint32_t *info,
+                          nsa_stream_t stream);
+
+/* w[n_queries] float64.  accepted[n_queries] and evaluated[n_queries] uint32 (each may be NULL) receive the nodes used through their
+ * dipole and the faces summed exactly -- measurements of the tree, not part of the answer. */
+int nsa_tri_winding_query(const void *tree, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                          const float *queries, uint32_t n_queries, double beta, int flip, double *w, uint32_t *accepted,
+                          uint32_t *evaluated, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -381,3 +381,10 @@ lib.nsa_tri_query_bounded.restype = _i
 lib.nsa_tri_query_bounded.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, ctypes.c_double, _p, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_tri_adjacency_workspace", "nsa_tri_adjacency_build", "nsa_tri_signed_query", "nsa_tri_signed_query_counted",
             "nsa_tri_query_bounded"]
+lib.nsa_tri_winding_workspace.restype = _u64
+lib.nsa_tri_winding_workspace.argtypes = [_u32]
+lib.nsa_tri_winding_build.restype = _i
+lib.nsa_tri_winding_build.argtypes = [_p, _u32, _p, _u32, _p, _p, _p]
+lib.nsa_tri_winding_query.restype = _i
+lib.nsa_tri_winding_query.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, ctypes.c_double, _i, _p, _p, _p, _p]
+EXPORTS += ["nsa_tri_winding_workspace", "nsa_tri_winding_build", "nsa_tri_winding_query"]

@@ -164,6 +164,7 @@ class TriIndex:
         check(lib.nsa_tri_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, self.buf.data_ptr(),
                                 self._totals.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
         self._adjacency = {}                       # weld setting -> (adjacency faces, adjacency buffer), built on first use
+        self._winding = None                       # (tree buffer, info) of Section 16, built on first use
 
     @property
     def skipped(self):
@@ -272,6 +273,49 @@ class TriIndex:
         if counts:
             out += (n_eval.long(), n_cells.long())
         return out
+
+    def _winding_tree(self):
+        """(tree buffer, info [3] int32 on the device: L, node count, usable faces) of header Section 16, built on first use and kept"""
+        if self._winding is None:
+            buf = torch.empty(lib.nsa_tri_winding_workspace(self.F), dtype=torch.uint8, device=self.device)
+            info = torch.zeros(3, dtype=torch.int32, device=self.device)
+            check(lib.nsa_tri_winding_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, buf.data_ptr(),
+                                            info.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            self._winding = (buf, info)
+        return self._winding
+
+    @torch.no_grad()
+    def winding(self, points, beta=2.0, flip=False, counts=False):
+        """[m] float64: the generalised winding number of the mesh at each point (header Section 16; Jacobson et al. 2013) -- the sum
+        of the signed solid angles of the usable faces over 4 pi.  1 inside and 0 outside a closed mesh whose normals point outwards
+        (``flip`` for inward ones: the negated value).  On an open mesh it is a smooth field, 1/2 across a hole's virtual closure, so
+        ``w > 0.5`` is an inside / outside test that a hole does not break.  ``beta`` (>= 1): the accuracy of the hierarchical
+        approximation of Barill et al. 2018 -- a tree node whose faces lie within r of its centre is used through its dipole from
+        farther than beta r; 2 is theirs, ``math.inf`` the exact sum over all faces.  A non-finite point gives NaN; a mesh without a
+        usable face 0.  ``counts=True`` appends the nodes accepted and the faces summed exactly per point [m] int64 (measurements).
+        The tree is independent of the closest-point index and built on first use."""
+        q = _points(points, "TriIndex.winding")
+        if q.device != self.device:
+            raise ValueError("TriIndex.winding: points on another device than the index")
+        beta = float(beta)
+        if not beta >= 1.0:
+            raise ValueError(f"TriIndex.winding: beta must be >= 1, got {beta!r}")
+        m = q.shape[0]
+        w = torch.empty(m, dtype=torch.float64, device=q.device)
+        n_acc = torch.zeros(m, dtype=torch.int32, device=q.device) if counts else None
+        n_eval = torch.zeros(m, dtype=torch.int32, device=q.device) if counts else None
+        if m:
+            buf, _ = self._winding_tree()
+            check(lib.nsa_tri_winding_query(buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, q.data_ptr(),
+                                            m, beta, 1 if flip else 0, w.data_ptr(), n_acc.data_ptr() if counts else None,
+                                            n_eval.data_ptr() if counts else None, torch.cuda.current_stream(q.device).cuda_stream))
+        return (w, n_acc.long(), n_eval.long()) if counts else w
+
+    def winding_layout(self):
+        """dict(L, nodes, usable faces, bytes) of the winding-number tree (a host copy: a synchronisation)"""
+        buf, info = self._winding_tree()
+        L, nodes, usable = (int(x) for x in info.cpu())
+        return {"L": L, "nodes": nodes, "usable faces": usable, "bytes": int(buf.numel())}
 
     def layout(self):
         """dict(cells per axis, cell size, faces in the grid, faces on the large list, faces skipped) of the built index (host

@@ -3,10 +3,12 @@ tools/bench_mesh.py's model (queries: samples of the mesh itself, the same sampl
 points of the bounding cube), the faces fully evaluated per query (the kernel's own count), the share of faces on the large list,
 and mesh_metrics end to end in both modes; then the signed and the range-limited queries of DESIGN 4n on the same mesh and queries:
 signed against unsigned, the uniform points under a band of 2, 5 and 20 cells, the adjacency build and its bytes, the incident faces
-walked per query, and mesh_sdf_grid at 256^3 with a band of 4 voxels.  Device events, warm-up first, medians; per-kernel times come from a separate
+walked per query, and mesh_sdf_grid at 256^3 with a band of 4 voxels; then the winding numbers of DESIGN 4o: the tree build and its
+bytes, the tree query at beta = 2 and 3 on the three query sets with the nodes accepted and the faces summed exactly per query, the
+exact sum on the first 20000 of each, and mesh_sdf_grid(sign="winding") beside the "normal" one.  Device events, warm-up first, medians; per-kernel times come from a separate
 `rocprofv3 --kernel-trace --stats` run of this script.  Baseline: a chunked torch float64 brute force on the same GPU at a size it
 finishes in a few seconds (queries x faces given below), compared against the index on the same inputs.
-usage: python tools/bench_mesh_closest.py [reps=5] [resolution=512] [out=profiles/mesh_closest_bench.json]"""
+usage: python tools/bench_mesh_closest.py [reps=5] [resolution=512] [out=profiles/mesh_closest_bench.json] [legs=all|winding]"""
 import json
 import os
 import sys
@@ -23,6 +25,7 @@ from nicer_slam_amd import inference, mesh_eval as M
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "mesh_closest_bench.json")
+LEGS = sys.argv[4] if len(sys.argv) > 4 else "all"
 
 
 def timed(fn, reps=REPS):
@@ -99,8 +102,40 @@ def sdf_rows(ix, surf, near, cube, out):
     out["mesh_sdf_grid 256^3 share within the band"] = float(torch.isfinite(res["g"]).double().mean())
 
 
+def winding_rows(ix, surf, near, cube, out):
+    import math
+    from nicer_slam_amd import mesh_sdf
+    out["winding tree bytes"] = int(M.lib.nsa_tri_winding_workspace(ix.F))
+
+    def build():
+        ix._winding = None
+        ix._winding_tree()
+
+    out["winding tree build ms"] = timed(build)
+    out["winding tree layout"] = ix.winding_layout()
+    for name, q in (("on surface 200k", surf), ("near surface (sigma 0.01) 200k", near), ("uniform in the cube 200k", cube)):
+        for beta in (2.0, 3.0):
+            key = f"{name} winding beta {beta:g}"
+            out[key + " ms"] = timed(lambda: ix.winding(q, beta=beta))
+            _, acc, ev = ix.winding(q, beta=beta, counts=True)
+            out[key + " nodes accepted/query"] = {"mean": float(acc.double().mean()), "max": int(acc.max())}
+            out[key + " faces summed/query"] = {"mean": float(ev.double().mean()), "max": int(ev.max())}
+        sub = q[:20000].contiguous()
+        out[f"{name[:-5]} 20k winding exact ms"] = timed(lambda: ix.winding(sub, beta=math.inf), reps=max(1, REPS // 2))
+        exact = ix.winding(sub, beta=math.inf)
+        for beta in (2.0, 3.0):
+            out[f"{name[:-5]} 20k max |w(beta {beta:g}) - w exact|"] = float((ix.winding(sub, beta=beta) - exact).abs().max())
+    res = {}
+    for sign in ("normal", "winding"):
+        out[f"mesh_sdf_grid 256^3, band 4 voxels, sign {sign}, ms"] = timed(
+            lambda: res.update({sign: mesh_sdf.mesh_sdf_grid(ix, 256, (-1.0, 1.0), band=4 * 2.0 / 255, sign=sign)}), reps=max(1, REPS // 2))
+    both = torch.isfinite(res["normal"])
+    out["mesh_sdf_grid 256^3 share of band points where the two signs differ"] = float(
+        ((res["normal"] < 0) != (res["winding"] < 0))[both].double().mean())
+
+
 def main():
-    out = {"reps": REPS}
+    out = {"reps": REPS, "legs": LEGS}
     g = torch.Generator(device="cuda").manual_seed(0)
     from bench_mesh import model
     mesh = inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False)
@@ -108,18 +143,22 @@ def main():
     out["mesh V"], out["mesh F"] = int(v.shape[0]), int(f.shape[0])
     out["index bytes"] = int(M.lib.nsa_tri_workspace(f.shape[0]))
     ix = M.TriIndex(v, f)
+    surf, _ = M.sample_surface(v, f, 200000, 0)
+    near = surf + 0.01 * torch.randn(surf.shape, device="cuda", generator=g)
+    cube = torch.rand(200000, 3, device="cuda", generator=g) * 2 - 1
+    if LEGS == "winding":
+        winding_rows(ix, surf, near, cube, out)
+        return finish(out)
     out["build ms"] = timed(lambda: M.TriIndex(v, f))
     lay = ix.layout()
     out["layout"] = lay
     out["large-list share"] = lay["large faces"] / f.shape[0]
     out["skipped (index, non-finite, zero area)"] = list(ix.skipped)
-    surf, _ = M.sample_surface(v, f, 200000, 0)
     query_case("on surface 200k", ix, surf, out)
-    near = surf + 0.01 * torch.randn(surf.shape, device="cuda", generator=g)
     query_case("near surface (sigma 0.01) 200k", ix, near, out)
-    cube = torch.rand(200000, 3, device="cuda", generator=g) * 2 - 1
     query_case("uniform in the cube 200k", ix, cube, out)
     sdf_rows(ix, surf, near, cube, out)
+    winding_rows(ix, surf, near, cube, out)
 
     # the torch float64 brute force of the tests, at a size it finishes in a few seconds; the index on the same inputs beside it
     from test_mesh_closest_gpu import _brute_torch
@@ -145,6 +184,10 @@ def main():
         out[f"mesh_metrics surface={mode} ms"] = timed(lambda: met.update(M.mesh_metrics(moved, mesh, surface=mode)),
                                                        reps=max(1, REPS // 2))
         out[f"mesh_metrics surface={mode} accuracy, completion"] = [met["accuracy"], met["completion"]]
+    finish(out)
+
+
+def finish(out):
     text = json.dumps(out, indent=1)
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
