@@ -1138,6 +1138,92 @@ int nsa_tri_winding_query(const void *tree, const float *verts, uint32_t n_verts
                           const float *queries, uint32_t n_queries, double beta, int flip, double *w, uint32_t *accepted,
                           uint32_t *evaluated, nsa_stream_t stream);
 
+/* ---- Section 17: rays against a triangle mesh (csrc/mesh_raycast.hip) ---- */
+
+/* Where does a ray o + t d hit the mesh: the smallest t in [tmin, tmax], the face and the barycentric coordinates of the hit -- or,
+ * in any-hit mode, whether there is a hit at all.  Nothing in the reference casts rays against a mesh: this statement is the
+ * contract, tests/raycast_ref.py restates it in numpy float64, and the kernels agree with that restatement BIT FOR BIT on t, the
+ * face and the barycentrics; no tolerance is involved.  verts and faces as in Section 14; the tree is a buffer of its own.
+ *
+ * Inputs and arithmetic.  origins[n_rays][3] and dirs[n_rays][3] are fp32; a direction is not normalised, t is in units of |d|.
+ * tmin and tmax are float64 (NaN: NSA_EBADARG; tmin > tmax: every ray misses).  The usable faces are exactly Section 14's.
+ * Everything is float64 on the fp32 inputs, every operation rounded on its own (no FMA contraction); there is no transcendental
+ * function anywhere, so +, -, *, / alone decide the bits.
+ *
+ * Face test (Woop, Benthin & Wald, "Watertight Ray/Triangle Intersection", JCGT 2013, in float64).  Per ray:
+ *   kz = the index of the largest |d_k| (the lowest k on a tie) ; kx = kz + 1 mod 3 ; ky = kx + 1 mod 3 ; if d_kz < 0 swap kx, ky
+ *   Sx = d_kx / d_kz ; Sy = d_ky / d_kz ; Sz = 1 / d_kz ; inv_k = 1 / d_k
+ * Per face (a, b, c), with A = a - o, B = b - o, C = c - o:
+ *   Ax = A_kx - Sx * A_kz ; Ay = A_ky - Sy * A_kz   (B, C alike)
+ *   U = Cx * By - Cy * Bx ; V = Ax * Cy - Ay * Cx ; W = Bx * Ay - By * Ax
+ *   miss if (U < 0 or V < 0 or W < 0) and (U > 0 or V > 0 or W > 0)
+ *   det = (U + V) + W ; miss if det == 0
+ *   NSA_RAY_CULL_BACK: miss if det < 0 (ab x ac points along d: the ray meets the face from behind) ; NSA_RAY_CULL_FRONT: if det > 0
+ *   T = (U * (Sz * A_kz) + V * (Sz * B_kz)) + W * (Sz * C_kz) ; t = T / det ; barycentrics (U / det, V / det, W / det) for (a, b, c)
+ *   miss unless enter <= t <= exit for the face's own box (below)
+ * Two faces that share an edge with the same fp32 coordinates form that edge's function from the same products with the opposite
+ * sign, exactly: no ray passes between them, and a ray through a shared edge or vertex hits at least one of the faces about it.
+ *
+ * Boxes.  A usable face has the fp32 box  s = the largest |coordinate| of its nine ; pad = fp32(s * 2^-20) ;
+ *   lo_k = the next fp32 below fp32(min(a_k, b_k, c_k) - pad) ; hi_k = the next fp32 above fp32(max(a_k, b_k, c_k) + pad).
+ * The slab interval of a ray against a box (lo, hi): per axis with d_k != 0, near_k and far_k = the min and max of
+ * (lo_k - o_k) * inv_k and (hi_k - o_k) * inv_k; an axis with d_k == 0 passes iff lo_k <= o_k <= hi_k;
+ *   enter = max(near_k, tmin) ; exit = min(far_k, tmax) ; the interval is empty when an axis fails or enter > exit.
+ * The box clause is PART OF THE FACE TEST, and that is what makes pruning exact without an error analysis: a node's box is the fp32
+ * min / max of the boxes below it, rounding is monotone, so a node's interval contains the interval of every face below it.  A node
+ * with an empty interval cannot contain a hit; a node with enter > the best t so far cannot contain one that wins or ties.  The tree
+ * and the brute force over all usable faces are equal by construction, in any traversal order.
+ * The price: the pad must be wide enough that the clause never rejects what the edge functions accept.  The computed t places the hit
+ * within about 2^-50 * D * (D / e) of the face, D = the distance of the face from o and e its shortest height (a ray grazing the
+ * face's plane divides a small T by a small det); the pad is at least 2^-20 * s.  So the clause is idle while
+ *   D^2 / e <= 2^30 * s,
+ * which a mesh of 1 mm faces seen from a kilometre still meets.  tests/raycast_ref.py carries the test with and without the clause
+ * and tests/test_mesh_raycast_cpu.py asserts that they agree on every ray of every case of the suite.
+ *
+ * Answer.  The hit with the smallest t, ties to the lowest face index: (t, face, barycentrics).  No hit: (+inf, -1, NaN).  A ray with
+ * a non-finite component or d == 0: (NaN, -1, NaN), counts 0.  A mesh without a usable face: (+inf, -1, NaN).  A hit whose t
+ * overflows to +inf is no hit.  NSA_RAY_ANY_HIT: the walk stops at the first hit it finds; face >= 0 iff some face is hit in
+ * [tmin, tmax] -- that flag is the contract, t, face and the barycentrics are those of whichever hit was found.
+ *
+ * Tree.  Section 16's, rebuilt here into a buffer of its own: lo, side, L, the Morton key of each usable face's centroid, the stable
+ * sort, a node for every level l in [0, L] and distinct prefix, numbered in pre-order.  Each node carries the box of its faces and,
+ * per octant o = the 3 key bits of its level, the child of that octant.  No atomic takes part; two builds give identical bits.
+ *
+ * Walk of one ray, m = 4 * [d_x < 0] + 2 * [d_y < 0] + [d_z < 0], starting with visit(root):
+ *   visit(i): n_nodes += 1 ; return if the node's interval is empty ; return if closest-hit and enter > best t
+ *     at a leaf (level L): for each of its faces in sorted order: skip it if its own interval is empty, or if closest-hit and
+ *        enter > best t ; else n_tested += 1 and the face test runs ; a hit replaces the best when t < best t, or t == best t and its
+ *        face index is lower ; in any-hit mode the first hit ends the walk
+ *     else: for r = 0 .. 7: visit(the child of octant r xor m) when the node has one
+ * so the children nearer along the ray come first.  n_nodes and n_tested are functions of the inputs alone and the oracle
+ * reproduces them exactly.  NSA_RAY_BRUTE tests every usable face in sorted order under the same skip rules (n_nodes = 0): the
+ * on-device cross-check.  Worst cases, slow and never wrong: every centroid in one leaf; faces as large as the mesh.
+ *
+ * Workspace, a function of n_faces alone, every array rounded up to 256 bytes, K(F) as in Section 16:
+ *   256 + 6 * 4 F + 4 + 24 F + 68 K(F) + 2^18   bytes.
+ * Nothing is allocated or synchronised; arguments are checked before the device is touched.  n_rays = 0 and n_faces = 0 return 0
+ * without a launch (nothing is written).  The verts and faces given to nsa_tri_ray_cast are those given to nsa_tri_ray_build. */
+
+#define NSA_RAY_ANY_HIT 1u
+#define NSA_RAY_CULL_BACK 2u
+#define NSA_RAY_CULL_FRONT 4u
+#define NSA_RAY_BRUTE 8u
+
+/* bytes of the tree buffer for n_faces (>= 1) faces; 0 for an invalid count */
+uint64_t nsa_tri_ray_workspace(uint32_t n_faces);
+
+/* Build the tree into `tree` (nsa_tri_ray_workspace(n_faces) bytes, device, 256-byte aligned).  info[3] (uint32, device; may be NULL)
+ * receives L, the node count and the number of usable faces. */
+int nsa_tri_ray_build(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, void *tree, uint32_t *info,
+                      nsa_stream_t stream);
+
+/* t[n_rays] float64, face[n_rays] int32, bary[n_rays][3] float64 (may be NULL); n_nodes[n_rays] and n_tested[n_rays] uint32 (each may
+ * be NULL) receive the nodes visited and the faces that went through the face test.  flags: a combination of NSA_RAY_*; both cull
+ * bits at once, or an unknown bit, is NSA_EBADARG. */
+int nsa_tri_ray_cast(const void *tree, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                     const float *origins, const float *dirs, uint32_t n_rays, double tmin, double tmax, uint32_t flags, double *t,
+                     int32_t *face, double *bary, uint32_t *n_nodes, uint32_t *n_tested, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -388,3 +388,11 @@ lib.nsa_tri_winding_build.argtypes = [_p, _u32, _p, _u32, _p, _p, _p]
 lib.nsa_tri_winding_query.restype = _i
 lib.nsa_tri_winding_query.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, ctypes.c_double, _i, _p, _p, _p, _p]
 EXPORTS += ["nsa_tri_winding_workspace", "nsa_tri_winding_build", "nsa_tri_winding_query"]
+lib.nsa_tri_ray_workspace.restype = _u64
+lib.nsa_tri_ray_workspace.argtypes = [_u32]
+lib.nsa_tri_ray_build.restype = _i
+lib.nsa_tri_ray_build.argtypes = [_p, _u32, _p, _u32, _p, _p, _p]
+lib.nsa_tri_ray_cast.restype = _i
+lib.nsa_tri_ray_cast.argtypes = [_p, _p, _u32, _p, _u32, _p, _p, _u32, ctypes.c_double, ctypes.c_double, _u32, _p, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_tri_ray_workspace", "nsa_tri_ray_build", "nsa_tri_ray_cast"]
+RAY_ANY_HIT, RAY_CULL_BACK, RAY_CULL_FRONT, RAY_BRUTE = 1, 2, 4, 8          # NSA_RAY_* of header Section 17

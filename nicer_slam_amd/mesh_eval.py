@@ -11,7 +11,8 @@ trimesh's surface sampling.
 * ``TriIndex`` / ``closest_point`` / ``distance_p2m``: the exact closest point of a triangle mesh for each query point, in float64
   (C ABI Section 14, csrc/mesh_closest.hip; trimesh.proximity.closest_point of eval_rec.py:120-129).
   ``TriIndex.signed_query`` and ``query(max_dist=)``: the signed and the range-limited form (C ABI Section 15, csrc/mesh_sdf.hip,
-  DESIGN 4n; nicer_slam_amd/mesh_sdf.py builds SDF grids and field metrics on them).
+  DESIGN 4n; nicer_slam_amd/mesh_sdf.py builds SDF grids and field metrics on them).  ``TriIndex.raycast``: the exact first hit of
+  rays against the mesh (C ABI Section 17, csrc/mesh_raycast.hip; nicer_slam_amd/mesh_raycast.py renders depth with it).
 * ``mesh_metrics(..., surface="mesh")``: the same metrics from the distance of each sample to the other mesh's SURFACE, which a
   perfect reconstruction scores 0 on; the default ``surface="samples"`` is the reference's sample-to-sample form.
 * ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale] [--surface mesh]``: the
@@ -26,7 +27,7 @@ import math
 import numpy as np
 import torch
 
-from ._native import lib, check
+from ._native import RAY_ANY_HIT, RAY_BRUTE, RAY_CULL_BACK, RAY_CULL_FRONT, check, lib
 
 F_THRESHOLDS = (0.010, 0.015, 0.020)       # np.linspace(1/1000, 1, 1000)[[9, 14, 19]] of eval_pointcloud
 COMPLETION_RATIO_THRESHOLD = 0.05          # completion_ratio's dist_th (eval_rec.py:168)
@@ -165,6 +166,7 @@ class TriIndex:
                                 self._totals.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
         self._adjacency = {}                       # weld setting -> (adjacency faces, adjacency buffer), built on first use
         self._winding = None                       # (tree buffer, info) of Section 16, built on first use
+        self._ray = None                           # (tree buffer, info) of Section 17, built on first use
 
     @property
     def skipped(self):
@@ -317,6 +319,61 @@ class TriIndex:
         L, nodes, usable = (int(x) for x in info.cpu())
         return {"L": L, "nodes": nodes, "usable faces": usable, "bytes": int(buf.numel())}
 
+    def _ray_tree(self):
+        """(tree buffer, info [3] int32 on the device: L, node count, usable faces) of header Section 17, built on first use and kept"""
+        if self._ray is None:
+            buf = torch.empty(lib.nsa_tri_ray_workspace(self.F), dtype=torch.uint8, device=self.device)
+            info = torch.zeros(3, dtype=torch.int32, device=self.device)
+            check(lib.nsa_tri_ray_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, buf.data_ptr(),
+                                        info.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            self._ray = (buf, info)
+        return self._ray
+
+    @torch.no_grad()
+    def raycast(self, origins, dirs, tmin=0.0, tmax=math.inf, any_hit=False, cull=None, counts=False, brute=False):
+        """(t [m] float64, face [m] int64, bary [m, 3] float64): where each ray ``origins + t * dirs`` (CUDA tensors [m, 3]; a
+        direction is not normalised, t is in units of its length) first hits the mesh within [tmin, tmax], ties to the lowest face
+        index, with the barycentric coordinates of the hit for the face's three vertices (header Section 17: the watertight test of
+        Woop et al. 2013 in float64 -- no ray slips between two faces that share an edge).  A miss gives (+inf, -1, NaN); a ray with a
+        non-finite component or a zero direction (NaN, -1, NaN).  ``cull``: None, "back" (faces whose ab x ac points along the ray are
+        not hit) or "front".  ``any_hit=True`` returns bool [m] instead -- whether anything is hit -- and stops each ray at the first
+        hit found.  ``brute=True`` tests every usable face (the on-device cross-check).  ``counts=True`` appends the tree nodes
+        visited and the faces tested per ray [m] int64 (measurements).  The tree is built on first use."""
+        o, d = _points(origins, "TriIndex.raycast"), _points(dirs, "TriIndex.raycast")
+        if o.device != self.device or d.device != self.device:
+            raise ValueError("TriIndex.raycast: rays on another device than the index")
+        if o.shape != d.shape:
+            raise ValueError(f"TriIndex.raycast: {o.shape[0]} origins for {d.shape[0]} directions")
+        tmin, tmax = float(tmin), float(tmax)
+        if math.isnan(tmin) or math.isnan(tmax):
+            raise ValueError("TriIndex.raycast: tmin and tmax must not be NaN")
+        if cull not in (None, "back", "front"):
+            raise ValueError(f"TriIndex.raycast: cull must be None, 'back' or 'front', got {cull!r}")
+        flags = ((RAY_ANY_HIT if any_hit else 0) | (RAY_BRUTE if brute else 0)
+                 | {None: 0, "back": RAY_CULL_BACK, "front": RAY_CULL_FRONT}[cull])
+        m, dev = o.shape[0], o.device
+        t = torch.empty(m, dtype=torch.float64, device=dev)
+        face = torch.empty(m, dtype=torch.int32, device=dev)
+        bary = None if any_hit else torch.empty(m, 3, dtype=torch.float64, device=dev)
+        n_nodes = torch.zeros(m, dtype=torch.int32, device=dev) if counts else None
+        n_tested = torch.zeros(m, dtype=torch.int32, device=dev) if counts else None
+        if m:
+            buf, _ = self._ray_tree()
+            check(lib.nsa_tri_ray_cast(buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, o.data_ptr(),
+                                       d.data_ptr(), m, tmin, tmax, flags, t.data_ptr(), face.data_ptr(),
+                                       bary.data_ptr() if bary is not None else None, n_nodes.data_ptr() if counts else None,
+                                       n_tested.data_ptr() if counts else None, torch.cuda.current_stream(dev).cuda_stream))
+        out = (face >= 0,) if any_hit else (t, face.long(), bary)
+        if counts:
+            return out + (n_nodes.long(), n_tested.long())
+        return out[0] if any_hit else out
+
+    def ray_layout(self):
+        """dict(L, nodes, usable faces, bytes) of the ray-cast tree (a host copy: a synchronisation)"""
+        buf, info = self._ray_tree()
+        L, nodes, usable = (int(x) for x in info.cpu())
+        return {"L": L, "nodes": nodes, "usable faces": usable, "bytes": int(buf.numel())}
+
     def layout(self):
         """dict(cells per axis, cell size, faces in the grid, faces on the large list, faces skipped) of the built index (host
         copies; a synchronisation -- for measurements, not for the query path).  Reads csrc/mesh_closest.hip's struct Grid at the head
@@ -465,7 +522,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     (mesh_clean.keep_components) and adds "components" (count before cleaning) and "kept area fraction" to the result;
     ``adjust_scale`` lets the ICP estimate a scale as well.  Departure: that one ICP does what CloudCompare's
     -ICP -ADJUST_SCALE and open3d's registration_icp do one after the other in the reference.
-    ``cull`` (off by default; not a step of the reference): dict(c2w=, intrinsics=, size=(H, W) [, mode=, rel=, near=]) keeps the faces of
+    ``cull`` (off by default; not a step of the reference): dict(c2w=, intrinsics=, size=(H, W) [, mode=, rel=, near=, method=]) keeps the faces of
     the reconstruction that some of these cameras saw (mesh_render.cull_mesh), after ``pre_transform`` and ``clean`` and
     before the ICP, and adds "culled face fraction" to the result.  The cameras look at the reconstruction AS IT IS AT THAT POINT: the
     poses (and the default near of 0.01) are in the frame and units the vertices have after the division by ``scale`` and after
@@ -588,6 +645,7 @@ def main(argv=None):
     ap.add_argument("--cull-intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"))
     ap.add_argument("--cull-size", type=int, nargs=2, metavar=("H", "W"))
     ap.add_argument("--cull-mode", choices=("any", "all", "frustum"), default="any")
+    ap.add_argument("--cull-raycast", action="store_true", help="decide visibility by casting rays (mesh_render method='raycast')")
     ap.add_argument("--surface", choices=("samples", "mesh"), default="samples",
                     help="measure each sample against the other surface's samples (the reference) or against the other mesh itself")
     a = ap.parse_args(argv)
@@ -599,6 +657,8 @@ def main(argv=None):
     if a.cull_poses:
         from .mesh_render import read_poses
         cull = dict(c2w=read_poses(a.cull_poses), intrinsics=a.cull_intrinsics, size=tuple(a.cull_size), mode=a.cull_mode)
+        if a.cull_raycast:
+            cull["method"] = "raycast"
     if (a.clean in ("touching", "not_touching")) != (a.region is not None):
         ap.error("--region goes with --clean touching or not_touching, and they need it")
     m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,

@@ -7,7 +7,7 @@
 * ``depth_l1``: mean absolute difference of the mesh's depth images and sensor depth frames.
 * ``camera_actor`` / ``trajectory_points`` / ``fly_through``: viz.py's point sets and its saved renderings, one PNG per frame.
 * ``python -m nicer_slam_amd.mesh_render MESH.ply --poses P --intrinsics fx fy cx cy --size H W --out DIR [--sim3 T.npy]
-  [--gt-poses P] [--cull OUT.ply --mode any --rel R] [--depth-l1 DEPTH_DIR] [--follow]``
+  [--gt-poses P] [--cull OUT.ply --mode any --rel R] [--depth-l1 DEPTH_DIR] [--raycast] [--follow]``
 
 Rasterisation and visibility have no CPU path: a missing GPU is an error.
 """
@@ -30,6 +30,7 @@ N_TOTALS = 12
 TOTALS = ("drawn", "bad_index", "depth", "guard", "degenerate", "backface", "atomics", "large_pairs", "items", "points_drawn",
           "points_skipped")
 DEFAULT_NEAR = 0.01
+METHODS = ("raster", "raycast")
 DEFAULT_REL = 2.0 ** -6          # the smallest power of two for which "any" equals "frustum" on the closed room
 LARGE_THRESHOLD = 256            # candidate pixel centres above which a face goes through the tile queue
 QUEUE_CAPACITY = 1 << 20
@@ -123,6 +124,11 @@ class _Scene:
                                    flags.data_ptr() if F else None, torch.cuda.current_stream(self.dev).cuda_stream))
 
 
+def _ray_index(sc):
+    from .mesh_eval import TriIndex
+    return TriIndex(sc.verts, sc.faces)
+
+
 def _points_arg(points, dev):
     """None, an array [P, 3] (colour index 0) or (array [P, 3], colour index [P]) -> (points fp32, colour int32) on the device"""
     if points is None:
@@ -174,17 +180,62 @@ def render_mesh(mesh, c2w, intrinsics, size, near=DEFAULT_NEAR, channels=CHANNEL
     return out
 
 
+def _method(method):
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    return method
+
+
+def _visible_by_rays(sc, c2w, mode, rel):
+    """bool [F]: ``visible_faces`` with the occlusion test itself in place of the depth images.  Per view, the vertices in front of
+    ``near`` that project inside the image are found by the frustum test of ``"frustum"`` (the same kernel, run on one degenerate
+    face per vertex); of those, a vertex is seen when nothing is hit on the way from the camera centre to it, up to 1 - rel of the way
+    (``mesh_raycast.occluded``)."""
+    from .mesh_eval import TriIndex
+    from .mesh_raycast import occluded
+    F, V = sc.faces.shape[0], sc.verts.shape[0]
+    flags = torch.zeros(F, dtype=torch.bool, device=sc.dev)
+    if F == 0 or V == 0:
+        return flags
+    ok = ((sc.faces >= 0) & (sc.faces < V)).all(1)
+    f = torch.where(ok[:, None], sc.faces, torch.zeros_like(sc.faces)).long()
+    ix = TriIndex(sc.verts, sc.faces) if mode != "frustum" else None
+    each = torch.arange(V, dtype=torch.int32, device=sc.dev)[:, None].expand(V, 3).contiguous()
+    centres = torch.from_numpy(np.ascontiguousarray(_as_numpy(c2w, np.float64).reshape(-1, 4, 4)[:, :3, 3])).float().to(sc.dev)
+    for i in range(sc.n):
+        inside = torch.zeros(V, dtype=torch.uint8, device=sc.dev)
+        v = sc.views(i, 1)
+        check(lib.nsa_mesh_visible(sc.verts.data_ptr(), V, each.data_ptr(), V, ctypes.byref(v), None, MODES["frustum"], 0.0,
+                                   inside.data_ptr(), torch.cuda.current_stream(sc.dev).cuda_stream))
+        seen = inside.bool()
+        if ix is not None:
+            idx = torch.nonzero(seen)[:, 0]
+            hidden = occluded(ix, centres[i], sc.verts[idx], rel)
+            seen[idx[hidden]] = False
+        per_face = seen[f]
+        flags |= ok & (per_face.all(1) if mode == "all" else per_face.any(1))
+    return flags
+
+
 @torch.no_grad()
-def visible_faces(mesh, c2w, intrinsics, size, mode="any", rel=DEFAULT_REL, near=DEFAULT_NEAR, batch=32, device="cuda"):
+def visible_faces(mesh, c2w, intrinsics, size, mode="any", rel=DEFAULT_REL, near=DEFAULT_NEAR, batch=32, device="cuda",
+                  method="raster"):
     """bool [F]: the faces of ``mesh`` that some view sees.  A vertex is seen in a view when it lies in front of ``near``, projects
     inside the image and is not farther than (1 + rel) times the largest depth of the mesh's own depth image at the four pixel
     centres around it; a face is visible in a view when any (``"any"``) or all (``"all"``) of its vertices are seen there.
-    ``"frustum"`` skips the depth comparison (and the rasterisation).  numpy in, numpy out; torch in, torch out."""
+    ``"frustum"`` skips the depth comparison (and the rasterisation).  numpy in, numpy out; torch in, torch out.
+    ``method="raycast"`` replaces the comparison with depth images by the occlusion test itself: a ray from the camera centre to the
+    vertex, any hit within 1 - rel of the way hides it (``mesh_raycast.occluded``) -- independent of the image resolution, and of
+    ``render_mesh``'s missing near-plane clipping."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {tuple(MODES)}, got {mode!r}")
     if not (0.0 <= float(rel) <= 1.0):
         raise ValueError("rel must lie in [0, 1]")
+    _method(method)
     sc = _Scene(mesh, c2w, intrinsics, size, near, device)
+    if method == "raycast":
+        out = _visible_by_rays(sc, c2w, mode, min(float(rel), 0.5))
+        return out.cpu().numpy() if sc.was_numpy else out.to(sc.orig)
     flags = torch.zeros(sc.faces.shape[0], dtype=torch.uint8, device=sc.dev)
     batch = max(1, int(batch))
     for lo in range(0, sc.n, batch):
@@ -195,17 +246,19 @@ def visible_faces(mesh, c2w, intrinsics, size, mode="any", rel=DEFAULT_REL, near
     return out.cpu().numpy() if sc.was_numpy else out.to(sc.orig)
 
 
-def cull_mesh(mesh, c2w, intrinsics, size, mode="any", rel=DEFAULT_REL, near=DEFAULT_NEAR, batch=32, device="cuda"):
+def cull_mesh(mesh, c2w, intrinsics, size, mode="any", rel=DEFAULT_REL, near=DEFAULT_NEAR, batch=32, device="cuda", method="raster"):
     """``mesh`` without the faces no view sees (``visible_faces``), compacted by ``mesh_clean.select_faces``: face and vertex order
     are kept."""
-    return select_faces(mesh, visible_faces(mesh, c2w, intrinsics, size, mode, rel, near, batch, device))
+    return select_faces(mesh, visible_faces(mesh, c2w, intrinsics, size, mode, rel, near, batch, device, method))
 
 
 @torch.no_grad()
-def depth_l1(mesh, depth_frames, c2w, intrinsics, near=DEFAULT_NEAR, batch=8, device="cuda"):
+def depth_l1(mesh, depth_frames, c2w, intrinsics, near=DEFAULT_NEAR, batch=8, device="cuda", method="raster"):
     """(mean |mesh depth - frame depth| over the pixels valid in both, their count): ``depth_frames`` [n, H, W] (or [H, W]) with the
     hole convention of ``TSDFVolume.integrate`` (valid: finite and > 0).  The differences are formed and summed in float64.
-    (nan, 0) when no pixel is valid in both."""
+    (nan, 0) when no pixel is valid in both.  ``method="raycast"`` takes the mesh depth from ``mesh_raycast.render_depth``: faces that
+    straddle the camera count."""
+    _method(method)
     d = torch.as_tensor(depth_frames)
     if d.dim() == 2:
         d = d[None]
@@ -217,10 +270,19 @@ def depth_l1(mesh, depth_frames, c2w, intrinsics, near=DEFAULT_NEAR, batch=8, de
     total = torch.zeros((), dtype=torch.float64, device=sc.dev)
     count = 0
     batch = max(1, int(batch))
+    ix = None
     for lo in range(0, sc.n, batch):
         m = min(batch, sc.n - lo)
-        zbuf, _ = sc.raster(lo, m)
-        r = sc.resolve(lo, m, zbuf, ("depth",))["depth"].double()
+        if method == "raycast":
+            from .mesh_raycast import render_depth
+            if ix is None:
+                ix = _ray_index(sc)
+                c2w_all, K_all = _as_numpy(c2w, np.float64).reshape(-1, 4, 4), _intrinsics4(intrinsics, sc.n)
+            r = render_depth(ix, c2w_all[lo:lo + m], K_all[lo:lo + m] if K_all.shape[0] > 1 else K_all, (sc.H, sc.W), near,
+                             ("depth",))["depth"].to(sc.dev)
+        else:
+            zbuf, _ = sc.raster(lo, m)
+            r = sc.resolve(lo, m, zbuf, ("depth",))["depth"].double()
         g = d[lo:lo + m].to(sc.dev).double()
         ok = (r > 0) & torch.isfinite(g) & (g > 0)
         total += (r - g).abs()[ok].sum()
@@ -399,6 +461,7 @@ def parse_args(argv=None):
     ap.add_argument("--rel", type=float, default=DEFAULT_REL)
     ap.add_argument("--near", type=float, default=DEFAULT_NEAR)
     ap.add_argument("--depth-l1", metavar="DEPTH_DIR", help="print the depth L1 against the frames of this directory")
+    ap.add_argument("--raycast", action="store_true", help="--cull and --depth-l1 by casting rays (method='raycast')")
     ap.add_argument("--follow", action="store_true", help="the viewer follows the current pose")
     ap.add_argument("--viewer-size", type=int, nargs=2, metavar=("H", "W"), default=list(VIZ_SIZE))
     a = ap.parse_args(argv)
@@ -426,10 +489,10 @@ def main(argv=None):
             frames = read_depth_dir(a.depth_l1, len(poses))
             if tuple(frames.shape[1:]) != tuple(a.size):
                 raise ValueError(f"{a.depth_l1}: frames of {frames.shape[1:]} for --size {a.size}")
-            l1, count = depth_l1(mesh, frames, poses, a.intrinsics, a.near)
+            l1, count = depth_l1(mesh, frames, poses, a.intrinsics, a.near, method="raycast" if a.raycast else "raster")
             print(f"depth L1 {l1:.6f} over {count} pixels")
         if a.cull:
-            culled = cull_mesh(mesh, poses, a.intrinsics, a.size, a.mode, a.rel, a.near)
+            culled = cull_mesh(mesh, poses, a.intrinsics, a.size, a.mode, a.rel, a.near, method="raycast" if a.raycast else "raster")
             print(f"{a.cull}: kept {culled['faces'].shape[0]} of {mesh['faces'].shape[0]} faces, "
                   f"{culled['verts'].shape[0]} of {mesh['verts'].shape[0]} vertices")
             out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in culled.items() if k in ("verts", "normals", "colors", "faces")}
