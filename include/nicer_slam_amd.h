@@ -1224,6 +1224,77 @@ int nsa_tri_ray_cast(const void *tree, const float *verts, uint32_t n_verts, con
                      const float *origins, const float *dirs, uint32_t n_rays, double tmin, double tmax, uint32_t flags, double *t,
                      int32_t *face, double *bary, uint32_t *n_nodes, uint32_t *n_tested, nsa_stream_t stream);
 
+/* ---- Section 18: mesh topology (edge table, watertightness, components joined across edges; DESIGN 4q, csrc/mesh_topology.hip) ---- */
+
+/* The undirected edge table of faces[n_faces, 3] int32 over n_verts vertices, by index only, as in Section 11: coordinates play no
+ * part and unwelded duplicates are different vertices.  n_verts < 2^31; H = 3 * n_faces < 2^31.  tests/topology_ref.py restates
+ * this statement in numpy.  All of it is integer work: no floating point, no tolerance.
+ *
+ * Contributing faces.  A face CONTRIBUTES when its three indices lie in [0, n_verts), they are pairwise distinct, and face_mask
+ * (uint8 [n_faces]; NULL = every face set) is non-zero for it.  F_c is their number, H_c = 3 F_c.  An index outside the range is
+ * never dereferenced.  (Section 11's VALID face may be degenerate; here (a, a, b) does not contribute: it has no three edges.)
+ *
+ * Half-edges.  Half-edge h = 3 f + k (k = 0, 1, 2) of a contributing face f runs from faces[f][k] to faces[f][(k + 1) % 3].  Its EDGE
+ * is the unordered pair (lo, hi), lo < hi, of the two; the half-edge is FORWARD when it runs lo -> hi.
+ *
+ * Edge table.  The E distinct edges are numbered in ascending (lo, hi) order, which is the ascending order of the 64-bit key
+ * lo << 32 | hi.  Arrays sized by H, the first E entries valid (the rest are not written):
+ *   edges[H, 2] int32         (lo, hi) of edge e
+ *   edge_count[H] int32       the half-edges on it
+ *   edge_forward[H] int32     how many of those are forward
+ *   edge_start[H + 1] int32   CSR offsets into edge_halfedges: edge e owns [edge_start[e], edge_start[e + 1]); edge_start[E] = H_c
+ * and
+ *   edge_halfedges[H] int32   the half-edge ids sorted by edge, ascending id within an edge; the first H_c are valid, the rest -1
+ *   face_edges[n_faces, 3]    int32: the edge id of half-edge 3 f + k; -1 (all three) for a face that does not contribute
+ *
+ * Classes.  edge_count == 1: BOUNDARY.  edge_count == 2: interior; it is INCONSISTENT when edge_forward != 1, that is, when its two
+ * faces traverse it the same way.  edge_count > 2: NON-MANIFOLD; it is never counted as inconsistent.
+ *
+ * Boundary loops.  The connected components of the graph whose edges are the boundary edges, joined at shared vertices (so two
+ * holes that touch in one vertex count once).  Computed with the vertex union-find of Section 11 (csrc/uf_passes.hpp), a boundary
+ * edge uniting its two ends in place of a face uniting its three.
+ *
+ * totals[8] (uint64, device; the caller reads them once):
+ *   {E, F_c, used vertices = distinct indices of contributing faces, boundary edges, non-manifold edges, inconsistent edges,
+ *    boundary loops, status}
+ * status: Section 11's bits (1: walk, 2: hook) from the boundary union-find; 0 unless the implementation is wrong.
+ *
+ * Kernel shape: the key sort is two stable argsorts of Section 4's radix sort, by hi and then by lo, each with only
+ * the 8-bit passes n_verts needs; a half-edge that does not contribute carries n_verts in both and sorts last.  Run heads are found
+ * by comparing neighbours in the sorted order, edge ids and forward counts by one exclusive scan of the head and forward flags, counts
+ * as differences of run starts, and every total as a sum of per-block integer counts.  No atomics are used outside the union-find,
+ * and those decide nothing in the output (parent[x] <= x): every output is a function of (faces, n_verts, face_mask) alone and
+ * bit-reproducible.
+ *
+ * NULL faces, workspace, totals or output array, n_verts >= 2^31 or 3 * n_faces >= 2^31: NSA_EBADARG before anything is launched.
+ * n_faces = 0 launches nothing, writes nothing and returns 0: all eight totals are zero by definition and the caller does not read
+ * them.  n_verts = 0 with faces is legal (no face contributes).  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_faces = 0, 3 * n_faces >= 2^31, n_verts >= 2^31) */
+uint64_t nsa_mesh_edges_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_edges(const int32_t *faces, uint32_t n_faces, uint32_t n_verts, const uint8_t *face_mask, void *workspace,
+                   int32_t *edges, int32_t *edge_count, int32_t *edge_forward, int32_t *edge_start, int32_t *edge_halfedges,
+                   int32_t *face_edges, uint64_t *totals, nsa_stream_t stream);
+
+/* Face components, after nsa_mesh_edges on the same mesh, from its face_edges, edge_start and edge_halfedges.  Two contributing
+ * faces are JOINED when they share an edge of any count >= 2; the closure is transitive.
+ *   face_label[n_faces] int32   the smallest face index of the face's component, -1 for a face that does not contribute
+ *   totals[2] (uint64, device)  {components, status}
+ * A union-find over the faces with Section 11's uf_find / uf_unite unchanged: every half-edge of a run after the first unites its
+ * face with its predecessor's.  The guarantees are Section 11's: parent[x] <= x, so the root is the smallest face index whatever the
+ * interleaving and the atomics decide nothing in the output; step caps (n_faces steps) report through status (1: walk, 2: hook)
+ * instead of spinning.  Input arrays that nsa_mesh_edges did not write give meaningless labels, never an access out of bounds.
+ * Departure from trimesh: its face_adjacency pairs only edges with exactly two faces, so trimesh's split cuts a mesh at a
+ * non-manifold edge; this rule joins across it.  (Python's face_adjacency keeps trimesh's definition.)
+ * n_faces = 0 launches nothing and returns 0; NULL arguments or 3 * n_faces >= 2^31 are NSA_EBADARG before anything is launched. */
+
+/* bytes of workspace; 0 for an invalid count (n_faces = 0 or 3 * n_faces >= 2^31) */
+uint64_t nsa_mesh_face_components_workspace(uint32_t n_faces);
+
+int nsa_mesh_face_components(const int32_t *face_edges, const int32_t *edge_start, const int32_t *edge_halfedges, uint32_t n_faces,
+                             void *workspace, int32_t *face_label, uint64_t *totals, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -396,3 +396,12 @@ lib.nsa_tri_ray_cast.restype = _i
 lib.nsa_tri_ray_cast.argtypes = [_p, _p, _u32, _p, _u32, _p, _p, _u32, ctypes.c_double, ctypes.c_double, _u32, _p, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_tri_ray_workspace", "nsa_tri_ray_build", "nsa_tri_ray_cast"]
 RAY_ANY_HIT, RAY_CULL_BACK, RAY_CULL_FRONT, RAY_BRUTE = 1, 2, 4, 8          # NSA_RAY_* of header Section 17
+lib.nsa_mesh_edges_workspace.restype = _u64
+lib.nsa_mesh_edges_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_edges.restype = _i
+lib.nsa_mesh_edges.argtypes = [_p, _u32, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+lib.nsa_mesh_face_components_workspace.restype = _u64
+lib.nsa_mesh_face_components_workspace.argtypes = [_u32]
+lib.nsa_mesh_face_components.restype = _i
+lib.nsa_mesh_face_components.argtypes = [_p, _p, _p, _u32, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_edges_workspace", "nsa_mesh_edges", "nsa_mesh_face_components_workspace", "nsa_mesh_face_components"]

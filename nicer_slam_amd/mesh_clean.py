@@ -9,7 +9,8 @@ the trajectory evaluation.
 * ``transform_mesh``: a 4x4 similarity applied to vertices and normals (alignment_transformation_sim3.npy, eval_rec.py:259-264).
 * ``python -m nicer_slam_amd.mesh_clean IN.ply --out OUT.ply [--keep ...] [--transform T.npy] [--list]``.
 
-Departure from trimesh's ``split``: faces that share a vertex are joined, not only faces that share an edge.
+Departure from trimesh's ``split``: faces that share a vertex are joined, not only faces that share an edge;
+``keep_components(..., connectivity="edge")`` takes the edge rule from mesh_topology.
 Labelling and statistics have no CPU path: a missing GPU is an error.  ``select_faces`` and ``transform_mesh`` are torch
 plumbing and run wherever their input lives.
 """
@@ -22,6 +23,7 @@ import torch
 from ._native import lib, check
 
 KEEP_MODES = ("largest", "touching", "not_touching")
+CONNECTIVITY = ("vertex", "edge")
 _PER_VERTEX = ("verts", "normals", "colors")
 
 
@@ -156,16 +158,24 @@ def _region(region):
 
 
 @torch.no_grad()
-def keep_components(mesh, keep="largest", region=None, device="cuda"):
+def keep_components(mesh, keep="largest", region=None, device="cuda", connectivity="vertex"):
     """(mesh, stats): the components of ``mesh`` (a dict as marching_cubes / extract_mesh / TSDFVolume.extract_mesh / read_ply
     give, numpy or torch) selected by ``keep``, compacted with ``select_faces``:
       "largest"       the component of greatest area, ties to the smallest label
       "touching"      with region=(lo, hi): the components with at least one vertex inside the closed box
       "not_touching"  the others
     ``stats`` is the ``component_stats`` table of the input plus ``kept`` [C] bool and ``kept_area_fraction``.
+    ``connectivity="edge"``: a component is a set of faces joined across shared EDGES (mesh_topology.face_components; trimesh's
+    ``split``), not at shared vertices.  The table is then that of the mesh in which every vertex has been duplicated once per
+    edge-joined component that uses it (mesh_topology.split_faces), on which the two rules coincide: ``label`` and ``vertex_comp``
+    refer to that mesh's vertices (the original indices when no vertex is shared between components), ``n_verts`` counts a pinch
+    vertex once per component, and a face with a repeated index belongs to no component and is dropped.  The returned mesh is the
+    selection applied to the ORIGINAL mesh: a pinch vertex two kept components share stays one vertex.
     An empty mesh or a selection that keeps nothing raises ValueError."""
     if keep not in KEEP_MODES:
         raise ValueError(f"keep_components: keep must be one of {KEEP_MODES}, got {keep!r}")
+    if connectivity not in CONNECTIVITY:
+        raise ValueError(f"keep_components: connectivity must be one of {CONNECTIVITY}, got {connectivity!r}")
     if keep != "largest":
         lo, hi = _region(region)
     if not torch.cuda.is_available():
@@ -173,7 +183,14 @@ def keep_components(mesh, keep="largest", region=None, device="cuda"):
     m, was_numpy, orig = _mesh_tensors(mesh, device)
     if m["verts"].shape[0] == 0 or m["faces"].shape[0] == 0:
         raise ValueError("keep_components: empty mesh")
-    st = component_stats(m["verts"], m["faces"])
+    sv, sf = m["verts"], m["faces"]                            # the mesh the table is of
+    if connectivity == "edge":
+        from . import mesh_topology
+        f32 = _faces_i32(sf, "keep_components")
+        label, _ = mesh_topology.face_components(f32, sv.shape[0])
+        sf, origin = mesh_topology.split_faces(f32, label, sv.shape[0])
+        sv = sv[origin]
+    st = component_stats(sv, sf)
     C = st["n_components"]
     if C == 0:
         raise ValueError("keep_components: no valid face")
@@ -184,7 +201,7 @@ def keep_components(mesh, keep="largest", region=None, device="cuda"):
         kept = torch.zeros(C, dtype=torch.bool, device=dev)
         kept[best] = True
     else:
-        v = m["verts"].double()
+        v = sv.double()
         inside = ((v >= torch.tensor(lo, device=dev)) & (v <= torch.tensor(hi, device=dev))).all(1)
         vc = st["vertex_comp"].long()
         hit = torch.zeros(C, dtype=torch.bool, device=dev)
@@ -257,6 +274,8 @@ def parse_args(argv=None):
     ap.add_argument("--out")
     ap.add_argument("--keep", choices=KEEP_MODES)
     ap.add_argument("--region", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--connectivity", choices=CONNECTIVITY, default="vertex",
+                    help="with --keep: faces joined at a shared vertex (the default) or only across a shared edge")
     ap.add_argument("--transform", metavar="T.npy", help="4x4 similarity applied before the selection")
     ap.add_argument("--list", action="store_true", help="print the component table and write nothing")
     a = ap.parse_args(argv)
@@ -284,7 +303,7 @@ def main(argv=None):
             return st
         if a.keep:
             region = (a.region[:3], a.region[3:]) if a.region else None
-            mesh, st = keep_components(mesh, a.keep, region)
+            mesh, st = keep_components(mesh, a.keep, region, connectivity=a.connectivity)
             print(f"{st['n_components']} components, kept {int(st['kept'].sum())} "
                   f"({st['kept_area_fraction'] * 100:.2f} % of the area): {mesh['verts'].shape[0]} vertices, "
                   f"{mesh['faces'].shape[0]} faces")

@@ -142,6 +142,19 @@ def _max_d2(max_dist, name):
     return d * d
 
 
+def welded_faces(verts, faces):
+    """``faces`` [F, 3] int32 with every vertex named by the rank of its fp32 coordinates among the distinct ones (-0 = +0), the
+    naming of ``TriIndex.adjacency(weld=True)`` and ``mesh_topology.topology(weld=True)``; a face with an index outside [0, V) is
+    kept as it is.  ``torch.unique`` of the coordinates, wherever ``verts`` lives."""
+    # + 0.0: -0 becomes +0.  A non-finite vertex is named as (0, 0, 0): NaN rows break the sort inside torch.unique,
+    # and what they share a name with does not matter, as no face with such a vertex contributes
+    finite = torch.isfinite(verts).all(1, keepdim=True)
+    _, inverse = torch.unique(torch.where(finite, verts + 0.0, torch.zeros_like(verts)), dim=0, return_inverse=True)
+    ok = ((faces >= 0) & (faces < verts.shape[0])).all(1, keepdim=True)
+    safe = torch.where(ok, faces, torch.zeros_like(faces)).long()
+    return torch.where(ok, inverse[safe].to(torch.int32), faces).contiguous()
+
+
 class TriIndex:
     """Exact closest-point index over a triangle mesh (fp32 verts [V, 3], integer faces [F, 3]) on the device, built once and
     queried any number of times (include/nicer_slam_amd.h Section 14).  The index refers to the mesh by face number, so it keeps
@@ -167,6 +180,7 @@ class TriIndex:
         self._adjacency = {}                       # weld setting -> (adjacency faces, adjacency buffer), built on first use
         self._winding = None                       # (tree buffer, info) of Section 16, built on first use
         self._ray = None                           # (tree buffer, info) of Section 17, built on first use
+        self._topology = {}                        # weld setting -> report of Section 18, computed on first use
 
     @property
     def skipped(self):
@@ -217,16 +231,7 @@ class TriIndex:
         -- so that a mesh whose seams repeat vertices is connected across them; ``weld=False`` takes the faces as they are."""
         weld = bool(weld)
         if weld not in self._adjacency:
-            adj = self.faces
-            if weld:
-                # + 0.0: -0 becomes +0.  A non-finite vertex is named as (0, 0, 0): NaN rows break the sort inside torch.unique,
-                # and what they share a name with does not matter, as no face with such a vertex contributes
-                finite = torch.isfinite(self.verts).all(1, keepdim=True)
-                _, inverse = torch.unique(torch.where(finite, self.verts + 0.0, torch.zeros_like(self.verts)), dim=0,
-                                          return_inverse=True)
-                ok = ((self.faces >= 0) & (self.faces < self.V)).all(1, keepdim=True)
-                safe = torch.where(ok, self.faces, torch.zeros_like(self.faces)).long()
-                adj = torch.where(ok, inverse[safe].to(torch.int32), self.faces).contiguous()
+            adj = welded_faces(self.verts, self.faces) if weld else self.faces
             nbytes = lib.nsa_tri_adjacency_workspace(self.V, self.F)
             if nbytes == 0:
                 raise ValueError("TriIndex.adjacency: more than (2^31 - 1) / 3 faces")
@@ -235,6 +240,15 @@ class TriIndex:
                                               buf.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
             self._adjacency[weld] = (adj, buf)
         return self._adjacency[weld]
+
+    def topology(self, weld=True):
+        """the report of ``mesh_topology.topology`` for the index's mesh (header Section 18), computed on first use and kept, once
+        per ``weld`` setting, like ``adjacency``"""
+        weld = bool(weld)
+        if weld not in self._topology:
+            from .mesh_topology import topology
+            self._topology[weld] = topology({"verts": self.verts, "faces": self.faces}, weld=weld)
+        return dict(self._topology[weld])
 
     @torch.no_grad()
     def signed_query(self, points, max_dist=None, flip=False, weld=True, counts=False, normals=False):
@@ -508,7 +522,7 @@ def _as_cuda_mesh(m, device):
 
 @torch.no_grad()
 def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda", pre_transform=None, clean=None,
-                 region=None, adjust_scale=False, cull=None, surface="samples"):
+                 region=None, adjust_scale=False, cull=None, surface="samples", connectivity="vertex"):
     """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
     ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
     reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
@@ -520,6 +534,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     ``pre_transform`` (4x4 similarity, alignment_transformation_sim3.npy) moves the scaled reconstruction; ``clean``
     ("largest", or "touching" / "not_touching" with ``region`` = (lo, hi)) keeps those components of it
     (mesh_clean.keep_components) and adds "components" (count before cleaning) and "kept area fraction" to the result;
+    ``connectivity`` ("vertex", the default, or "edge") is keep_components' rule for what a component is;
     ``adjust_scale`` lets the ICP estimate a scale as well.  Departure: that one ICP does what CloudCompare's
     -ICP -ADJUST_SCALE and open3d's registration_icp do one after the other in the reference.
     ``cull`` (off by default; not a step of the reference): dict(c2w=, intrinsics=, size=(H, W) [, mode=, rel=, near=, method=]) keeps the faces of
@@ -550,7 +565,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
             _, P = mesh_clean.check_similarity(pre_transform)
             rv = _transform(rv.double(), torch.from_numpy(P).to(rv.device)).float()
         if clean is not None:
-            kept, st = mesh_clean.keep_components({"verts": rv, "faces": rf}, clean, region, device)
+            kept, st = mesh_clean.keep_components({"verts": rv, "faces": rf}, clean, region, device, connectivity=connectivity)
             rv, rf = kept["verts"], kept["faces"]
             extra = {"components": st["n_components"], "kept area fraction": st["kept_area_fraction"]}
     if cull is not None:
@@ -639,6 +654,8 @@ def main(argv=None):
     ap.add_argument("--sim3", metavar="T.npy", help="4x4 similarity applied to REC first (alignment_transformation_sim3.npy)")
     ap.add_argument("--clean", choices=("largest", "touching", "not_touching"), help="keep these components of REC")
     ap.add_argument("--region", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--connectivity", choices=("vertex", "edge"), default="vertex",
+                    help="with --clean: faces joined at a shared vertex (the default) or only across a shared edge")
     ap.add_argument("--adjust-scale", action="store_true", help="the ICP estimates a scale as well")
     ap.add_argument("--cull-poses", metavar="POSES", help="cull REC to what these camera-to-world poses saw (.npy, text or a directory); the poses are in the frame REC has "
                     "after --scale and --sim3 have been applied, not in the file's own units")
@@ -664,7 +681,7 @@ def main(argv=None):
     m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,
                      pre_transform=np.load(a.sim3) if a.sim3 else None, clean=a.clean,
                      region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale, cull=cull,
-                     surface=a.surface)
+                     surface=a.surface, connectivity=a.connectivity)
     if a.surface == "mesh":
         print("surface: mesh (each sample against the other mesh's surface)")
     print("accuracy: ", m["accuracy"] * 100, "cm")

@@ -8,12 +8,14 @@ index of mesh_eval.TriIndex.
   al. 2013, Barill et al. 2018): 1 inside and 0 outside a closed mesh, and on an OPEN mesh a smooth field that is 1/2 across a hole's
   virtual closure.  ``sign="winding"`` (``method="winding"`` for ``contains``) takes the sign of every function here from
   ``w > 0.5`` instead: an inside / outside test for meshes with holes.  The default ``"normal"`` is the pseudo-normal rule, unchanged.
+  ``sign="auto"`` picks between the two: "normal" when the mesh is closed and consistently oriented, which
+  ``mesh_topology.topology`` decides exactly, "winding" otherwise; ``resolve_sign`` returns the rule used.
 * ``mesh_sdf_grid(mesh, resolution, ...)``: a narrow-band SDF volume of the mesh, NaN outside the band, in the point order of
   inference.get_grid_uniform; inference.marching_cubes meshes it as it is.
 * ``sdf_field_metrics(sdf, mesh, ...)``: the learned SDF field (a model, through inference.sdf_values, or any callable) against the
   mesh's signed distance at points scattered about its surface -- the field itself, not its marching-cubes level set.
 * ``python -m nicer_slam_amd.mesh_sdf MESH.ply --resolution R --bounds LO HI --band B --out SDF.npy [--flip]
-  [--sign winding [--beta B | --exact]] [--points P.npy --out-dist D.npy [--out-winding W.npy]]``.
+  [--sign winding|auto [--beta B | --exact]] [--points P.npy --out-dist D.npy [--out-winding W.npy]]``.
 
 For an open mesh the "normal" sign is that of the nearest surface element, not an inside / outside test; the "winding" sign is one.
 There is no CPU path: a missing GPU
@@ -40,7 +42,18 @@ def _on_device(points, index):
     return points.to(index.device)
 
 
-SIGNS = ("normal", "winding")
+SIGNS = ("normal", "winding", "auto")
+
+
+def resolve_sign(mesh, sign, weld=True):
+    """the sign rule a call with ``sign`` uses on ``mesh`` (a dict or a TriIndex): "normal" and "winding" are themselves; "auto"
+    is "normal" when the mesh is closed and consistently oriented -- ``topology(mesh, weld=weld)["is_oriented"]``,
+    cached on a TriIndex -- and "winding" otherwise."""
+    if sign not in SIGNS:
+        raise ValueError(f"resolve_sign: sign must be one of {SIGNS}, got {sign!r}")
+    if sign != "auto":
+        return sign
+    return "normal" if _index(mesh).topology(weld=weld)["is_oriented"] else "winding"
 
 
 def _sign_rule(sign, beta, name):
@@ -84,6 +97,7 @@ def signed_distance(mesh, points, max_dist=None, flip=False, weld=True, sign="no
     ``beta`` as in ``winding_number``; +inf where nothing lies within ``max_dist``, whatever ``flip``."""
     sign, beta = _sign_rule(sign, beta, "signed_distance")
     index = _index(mesh, points)
+    sign = resolve_sign(index, sign, weld)
     if sign == "winding":
         return _winding_signed(index, _on_device(points, index), max_dist, flip, beta)
     return index.signed_query(_on_device(points, index), max_dist=max_dist, flip=flip, weld=weld)[0]
@@ -96,6 +110,9 @@ def contains(mesh, points, flip=False, weld=True, method="normal", beta=2.0):
     surface element and says nothing about an inside.  ``method="winding"``: whether the winding number exceeds 0.5 (a NaN is not
     inside) -- an answer for open meshes too, with every hole closed by the surface on which w = 1/2."""
     method, beta = _sign_rule(method, beta, "contains")
+    if method == "auto":
+        mesh = _index(mesh, points)
+        method = resolve_sign(mesh, method, weld)
     if method == "winding":
         return winding_number(mesh, points, beta=beta, flip=flip) > 0.5
     return signed_distance(mesh, points, flip=flip, weld=weld) < 0
@@ -136,6 +153,7 @@ def mesh_sdf_grid(mesh, resolution, grid_boundary=(-1, 1), band=None, flip=False
     if chunk < 1:
         raise ValueError("mesh_sdf_grid: chunk must be >= 1")
     index = _index(mesh)
+    sign = resolve_sign(index, sign, weld)
     ax = grid_axis(resolution, grid_boundary, index.device)
     n = resolution ** 3
     out = torch.empty(n, dtype=torch.float32, device=index.device)
@@ -176,6 +194,7 @@ def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0,
     if not (n_points > 0 and sigma >= 0 and band >= 0):
         raise ValueError("sdf_field_metrics: needs n_points > 0, sigma >= 0 and band >= 0")
     index = _index(mesh)
+    sign = resolve_sign(index, sign, weld)
     pts, _ = sample_surface(index.verts, index.faces, int(n_points), seed)
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
     noise = torch.randn(pts.shape, generator=gen, dtype=torch.float64) * float(sigma)
@@ -205,7 +224,8 @@ def main(argv=None):
     ap.add_argument("--flip", action="store_true", help="the mesh's normals point inwards")
     ap.add_argument("--points", metavar="P.npy", help="[m, 3] points to measure as well")
     ap.add_argument("--out-dist", metavar="D.npy", help="their signed distances, float64")
-    ap.add_argument("--sign", choices=SIGNS, default="normal", help="the sign rule: pseudo-normal, or winding number > 0.5")
+    ap.add_argument("--sign", choices=SIGNS, default="normal", help="the sign rule: pseudo-normal, winding number > 0.5, or auto: pseudo-normal when the mesh is closed and "
+                    "consistently oriented (mesh_topology), winding otherwise")
     ap.add_argument("--beta", type=float, default=2.0, help="accuracy of the hierarchical winding number (>= 1)")
     ap.add_argument("--exact", action="store_true", help="the exact winding number: beta = +inf")
     ap.add_argument("--out-winding", metavar="W.npy", help="the winding numbers of --points, float64")
@@ -224,16 +244,20 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_sdf: needs a GPU")
     index = _index(read_ply(a.mesh))
+    rule = resolve_sign(index, a.sign)
     result = {}
+    if a.sign == "auto":                                       # (the other two say themselves; their output stays as it was)
+        print(f"sign rule: {rule} (auto)")
+        result["sign"] = rule
     if a.resolution is not None:
-        grid = mesh_sdf_grid(index, a.resolution, tuple(a.bounds), a.band, a.flip, sign=a.sign, beta=beta)
+        grid = mesh_sdf_grid(index, a.resolution, tuple(a.bounds), a.band, a.flip, sign=rule, beta=beta)
         np.save(a.out, grid.cpu().numpy())
         inside = int(torch.isfinite(grid).sum())
         print(f"grid: {a.resolution}^3 over [{a.bounds[0]}, {a.bounds[1]}], {inside} points within the band -> {a.out}")
         result["grid"] = grid
     if a.points is not None:
         pts = np.load(a.points).reshape(-1, 3)
-        d = signed_distance(index, pts, a.band, a.flip, sign=a.sign, beta=beta)
+        d = signed_distance(index, pts, a.band, a.flip, sign=rule, beta=beta)
         d = torch.where(torch.isfinite(d), d, torch.full_like(d, math.nan))
         np.save(a.out_dist, d.cpu().numpy())
         print(f"points: {pts.shape[0]}, {int(torch.isfinite(d).sum())} within the band -> {a.out_dist}")
