@@ -1295,6 +1295,104 @@ uint64_t nsa_mesh_face_components_workspace(uint32_t n_faces);
 int nsa_mesh_face_components(const int32_t *face_edges, const int32_t *edge_start, const int32_t *edge_halfedges, uint32_t n_faces,
                              void *workspace, int32_t *face_label, uint64_t *totals, nsa_stream_t stream);
 
+/* ---- Section 19: mesh simplification by vertex clustering with quadric placement (csrc/mesh_simplify.hip) ---- */
+
+/* Rossignac-Borrel vertex clustering on a uniform grid, the representative of a cell placed by the error quadric of the faces around
+ * it (Lindstrom's out-of-core form).  verts[n_verts, 3] fp32 and faces[n_faces, 3] int32 as in Section 14; optional normals and
+ * colours fp32 [n_verts, 3]; origin[3] and h host float64 (finite, h > 0).  n_verts < 2^31, 3 * n_faces < 2^31.
+ * tests/simplify_ref.py restates this statement in numpy float64.
+ *
+ * Arithmetic.  Float64 on the fp32 inputs, every operation rounded on its own (no FMA contraction), dot(u, w) and u x w in
+ * Section 14's component order.  Everything after the cell of a vertex is integer work until the placement.
+ *
+ * Cells.  Vertex v has cell c_k = floor((double(v_k) - origin_k) / h) on axis k.  It is IN THE GRID when its three coordinates are
+ * finite and 0 <= c_k < n_cells on every axis; n_cells <= 2^21, and the grid of the statement is n_cells = 2^21: a caller who knows
+ * that every cell index is smaller may say so, which changes nothing but the number of sort passes (below).  Its key is
+ * c_x * 2^42 + c_y * 2^21 + c_z.  The cell centre is origin + (c + 0.5) * h, computed as written.  (The quotient is rounded before
+ * the floor, so a vertex within one float64 rounding of a cell face may be assigned across it: an output position lies in the
+ * closed box of its cell up to a few float64 roundings of |v - origin| + h and the float32 rounding of the output.)
+ *
+ * Contributing faces.  A face CONTRIBUTES when its three indices lie in [0, n_verts) and all three vertices are in the grid.  The
+ * indices need not be distinct (a repeated index gives a zero normal below and a face that cannot survive).  An index outside the
+ * range is never dereferenced.  A vertex is USED when a contributing face names it.
+ *
+ * Clusters.  The K distinct keys of the used vertices, numbered 0 .. K - 1 in ascending key order.
+ *   vertex_cluster[n_verts] int32    that number, -1 for a vertex that is not used
+ *
+ * Surviving faces.  A contributing face maps to its three cluster numbers.  It is COLLAPSED when they are not pairwise distinct.
+ * Otherwise it is rotated cyclically until the smallest number comes first (the orientation is kept); among the faces with the
+ * same rotated triple the one with the lowest face index SURVIVES, the others are DUPLICATES.  A triple and its reverse are
+ * different faces and both stay: a sheet that collapses to zero thickness keeps its two sides.  The F' survivors are listed in
+ * ascending original face index; the V' output vertices are the clusters a survivor names, in ascending cluster number.
+ *   out_faces[n_faces, 3] int32      the first F' rows: the rotated triples, as indices of output vertices
+ *   face_origin[n_faces] int32       the first F': the original face of each (strictly ascending)
+ *   cluster_vertex[n_verts] int32    the first K: the output vertex of cluster k, -1 when no survivor names it; the rest -1
+ *   out_cluster[n_verts] int32       the first V': the cluster of each output vertex (ascending)
+ * totals[9] (uint64, device; the caller reads them once):
+ *   {K, contributing faces, used vertices, vertices finite but outside the grid (used or not), collapsed faces, duplicate faces,
+ *    V', F', status}
+ * status: bit 1 when a sort order named an element outside its range; 0 unless the implementation is wrong (Section 18's style).
+ *
+ * Kernel shape.  Keys and used marks; the used vertices sorted by key with two stable argsorts of Section 4's radix
+ * sort, low word then high word, a vertex that is not used carrying n_cells << 10 in the high word so that it sorts last, each
+ * argsort with only the 8-bit passes the occupied width needs (low word: min(32, 21 + bits(n_cells - 1)) bits; high word:
+ * bits(n_cells) + 10); run heads and an exclusive scan number the clusters.  The rotated triples are sorted by three chained
+ * argsorts (third, second, first number; V for a face that cannot survive; passes by bits(n_verts)); a run head survives.  One scan
+ * over the faces compacts them, one over the clusters numbers the output vertices.  Counts are sums of integers; every output is a
+ * function of the arguments alone and bit-reproducible.
+ *
+ * NULL origin, non-finite origin, h non-finite or <= 0, n_cells = 0 or > 2^21, n_verts >= 2^31, 3 * n_faces >= 2^31, or (with both
+ * counts non-zero) a NULL array, workspace or totals: NSA_EBADARG before anything is launched.  n_verts = 0 or n_faces = 0 launches
+ * nothing, writes nothing and returns 0: all nine totals are zero and every vertex_cluster is -1 by definition, and the caller does
+ * not read them.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device), a function of the two counts alone; 0 for a count of 0 or out of range */
+uint64_t nsa_mesh_cluster_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_cluster(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const double *origin, double h,
+                     uint32_t n_cells, void *workspace, int32_t *vertex_cluster, int32_t *cluster_vertex, int32_t *out_cluster,
+                     int32_t *out_faces, int32_t *face_origin, uint64_t *totals, nsa_stream_t stream);
+
+/* Positions and attributes of the output vertices, after nsa_mesh_cluster on the same mesh, origin and h, from its vertex_cluster and
+ * cluster_vertex.  n_out = V' (rows of the output arrays; an output vertex >= n_out is not written).  Per cluster that has an output
+ * vertex, with coordinates relative to its own cell centre, p = double(v) - centre (component by component):
+ *   m = (sum of p over its used vertices, in ascending vertex index) / count
+ *   for every (contributing face f, corner j) whose corner vertex faces[f][j] is in the cluster, in ascending 3 f + j, with
+ *   p0, p1, p2 the face's three vertices in the order listed, all relative to THIS cluster's centre:
+ *     n = (p1 - p0) x (p2 - p0)        (not normalised: the weight is the squared area; no square root, no division)
+ *     d = -dot(n, p0)
+ *     A += n n^T  (A00 += n_x n_x, A01 += n_x n_y, A02 += n_x n_z, A11 += n_y n_y, A12 += n_y n_z, A22 += n_z n_z) ;  b += n * d
+ *   tr = (A00 + A11) + A22
+ *   placement 0 (mean):     x = m
+ *   placement 1 (quadric):  x = m when tr == 0; otherwise mu = eps * tr, r = -b + mu * m, (A + mu I) s = r solved by Cholesky
+ *                           (L L^T, no pivoting: the matrix is symmetric positive definite for eps > 0, condition <= ~1 / eps),
+ *                           x_k = s_k clamped to [-h / 2, h / 2]; x = m when a component of s is not finite (possible with eps = 0 only)
+ *   position = float(centre + x)
+ * This is Lindstrom's quadric with a Tikhonov pull towards the cluster mean in place of his truncated SVD: no threshold and no
+ * branch on a singular value; the rule is continuous in its inputs, the clamp included.
+ *   out_normals  = (sum of the used member vertices' normals, ascending vertex index) / its Euclidean length
+ *                  sqrt((x * x + y * y) + z * z); (0, 0, 0) when that length is zero or not finite
+ *   out_colours  = (sum of the member colours, same order) / count
+ *   out_cell[n_out, 3] int32 (may be NULL)   the cell of each output vertex
+ * normals and out_normals are both NULL or both given, likewise colours and out_colours.
+ *
+ * Kernel shape.  The vertices sorted stably by cluster and the incidences 3 f + j sorted stably by the cluster of the corner vertex
+ * (one argsort each, passes by bits(n_verts)), so every cluster owns a run in the stated order; one lane per output vertex walks
+ * its two runs.  No atomics: each sum has the one order above, and two runs are bit-identical.  Input arrays that nsa_mesh_cluster
+ * did not write give meaningless positions, never an access out of bounds.
+ *
+ * eps < 0 or not finite, placement not 0 or 1, n_out > n_verts, an attribute without its output or the reverse, the grid errors of
+ * nsa_mesh_cluster, or (with all three counts non-zero) a NULL verts, faces, vertex_cluster, cluster_vertex, workspace or out_verts:
+ * NSA_EBADARG before anything is launched.  A count of zero launches nothing and returns 0.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace, a function of the two counts alone; 0 for a count of 0 or out of range */
+uint64_t nsa_mesh_cluster_place_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_cluster_place(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const float *normals,
+                           const float *colours, const double *origin, double h, double eps, int placement,
+                           const int32_t *vertex_cluster, const int32_t *cluster_vertex, uint32_t n_out, void *workspace,
+                           float *out_verts, float *out_normals, float *out_colours, int32_t *out_cell, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

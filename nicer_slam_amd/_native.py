@@ -405,3 +405,13 @@ lib.nsa_mesh_face_components_workspace.argtypes = [_u32]
 lib.nsa_mesh_face_components.restype = _i
 lib.nsa_mesh_face_components.argtypes = [_p, _p, _p, _u32, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_edges_workspace", "nsa_mesh_edges", "nsa_mesh_face_components_workspace", "nsa_mesh_face_components"]
+lib.nsa_mesh_cluster_workspace.restype = _u64
+lib.nsa_mesh_cluster_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_cluster.restype = _i
+lib.nsa_mesh_cluster.argtypes = [_p, _u32, _p, _u32, ctypes.POINTER(_f64), _f64, _u32, _p, _p, _p, _p, _p, _p, _p, _p]
+lib.nsa_mesh_cluster_place_workspace.restype = _u64
+lib.nsa_mesh_cluster_place_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_cluster_place.restype = _i
+lib.nsa_mesh_cluster_place.argtypes = [_p, _u32, _p, _u32, _p, _p, ctypes.POINTER(_f64), _f64, _f64, _i, _p, _p, _u32, _p, _p, _p,
+                                       _p, _p, _p]
+EXPORTS += ["nsa_mesh_cluster_workspace", "nsa_mesh_cluster", "nsa_mesh_cluster_place_workspace", "nsa_mesh_cluster_place"]
