@@ -17,7 +17,7 @@
 //     p = (a + s ab) + t ac ;  e = q - p ;  d2(q, face) = (e_x e_x + e_y e_y) + e_z e_z
 // The winner is the usable face with the smallest d2 (a NaN d2 never wins), ties to the lowest face index.
 //
-// Index: the grid of mesh_eval.hip (bulk quantiles of a strided subsample, near-cubic cells, border clamping), over the fp32 centroids
+// Index: the grid of bulk_grid.hpp (bulk quantiles of a strided subsample, near-cubic cells, border clamping), over the fp32 centroids
 // cf = fp32(((a + b) + c) / 3) of the usable faces, at most B = min(2F, 2^22) cells.  A face whose box is longer than 2 cells on an
 // axis, or whose shape factor sigma = Lmax^2 / |ab x ac|^2 (Lmax the longest edge) exceeds 2^16 / hmax^2 (hmax the longest cell
 // edge), or whose centroid lies more than 256 cells outside the grid (a stray component far from the bulk), goes on the LARGE LIST
@@ -92,26 +92,15 @@ __device__ __forceinline__ uint32_t face_record(const Grid& g, const float (&a)[
     return large ? g.ncells : (cell[0] * g.R[1] + cell[1]) * g.R[2] + cell[2];
 }
 
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {    // 1024 threads; red[16]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int w = 1; w < 16; ++w) r = op(r, red[w]);
-    return r;
-}
-
 // one workgroup: skip counts, the box of the usable faces' vertices, the bulk of their centroids and the grid over it
 __global__ __launch_bounds__(1024) void k_tri_bounds(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
                                                      uint32_t F, uint32_t cells, Index ix, uint32_t* __restrict__ totals) {
+    using bulk::block_reduce;
+    using bulk::kSubsample;
     __shared__ float sv[3][kSubsample];
     __shared__ float red[16];
     __shared__ uint32_t redu[16];
-    __shared__ float bulk[2][3];
+    __shared__ float s_bulk[2][3];
     const uint32_t tid = threadIdx.x;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     uint32_t skipped[3] = {0, 0, 0};
@@ -147,22 +136,7 @@ __global__ __launch_bounds__(1024) void k_tri_bounds(const float* __restrict__ v
         nf += ok;
     }
     const uint32_t m_f = block_reduce(nf, [](uint32_t p, uint32_t q) { return p + q; }, redu);
-    __syncthreads();
-    const uint32_t k_lo = m_f >> 6, k_hi = m_f ? m_f - 1 - k_lo : 0;
-    for (int ax = 0; ax < 3; ++ax) {
-        for (uint32_t j = tid; j < m; j += 1024) {
-            const float x = sv[ax][j];
-            if (!__builtin_isfinite(x)) continue;
-            uint32_t rank = 0;
-            for (uint32_t i = 0; i < m; ++i) {
-                const float w = sv[ax][i];
-                rank += (w < x) || (w == x && i < j);
-            }
-            if (rank == k_lo) bulk[0][ax] = x;
-            if (rank == k_hi) bulk[1][ax] = x;
-        }
-    }
-    __syncthreads();
+    bulk::rank_bulk(sv, m, m_f, s_bulk);
     if (tid != 0) return;
     if (totals) {
         totals[0] = tot[0];
@@ -170,38 +144,12 @@ __global__ __launch_bounds__(1024) void k_tri_bounds(const float* __restrict__ v
         totals[2] = tot[2];
     }
     Grid g;
-    double e[3], emax = 0.0;
+    bulk::solve(s_bulk[0], s_bulk[1], m_f, cells, g);
+    double hmax = 0.0, h2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         g.gmin[k] = gmin[k];
         g.gmax[k] = gmax[k];
-        g.lo[k] = m_f ? bulk[0][k] : 0.0f;
-        e[k] = m_f ? (double)bulk[1][k] - (double)bulk[0][k] : 0.0;
-        emax = e[k] > emax ? e[k] : emax;
-    }
-    uint32_t R[3] = {1, 1, 1};
-    if (emax > 0.0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e[k] = e[k] > emax * 0x1p-10 ? e[k] : emax * 0x1p-10;
-        double cs = cbrt(e[0] * e[1] * e[2] / cells);
-        for (int it = 0; it < 200; ++it) {             // near-cubic cells, at most `cells` of them
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double r = floor(e[k] / cs);
-                R[k] = r < 1.0 ? 1u : (r > kMaxRes ? kMaxRes : (uint32_t)r);
-            }
-            if ((uint64_t)R[0] * R[1] * R[2] <= cells) break;
-            cs *= 1.0625;
-        }
-        if ((uint64_t)R[0] * R[1] * R[2] > cells) R[0] = R[1] = R[2] = 1;     // (never reached; keeps the cell arrays in bounds)
-    }
-    double hmax = 0.0, h2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float h = emax > 0.0 ? (float)(e[k] / R[k]) : 1.0f;
-        g.h[k] = h > 1e-30f ? h : 1e-30f;
-        g.inv_h[k] = 1.0f / g.h[k];
-        g.R[k] = R[k];
         hmax = fmax(hmax, (double)g.h[k]);
         h2 += (double)g.h[k] * (double)g.h[k];
     }
@@ -212,11 +160,9 @@ __global__ __launch_bounds__(1024) void k_tri_bounds(const float* __restrict__ v
         for (int k = 0; k < 3; ++k) {
             const double lo = g.lo[k], h = g.h[k];
             g.gmin[k] = fmaxf(g.gmin[k], round_down(lo - (kStrayCells + 3.0) * h));
-            g.gmax[k] = fminf(g.gmax[k], round_up(lo + ((double)R[k] + kStrayCells + 3.0) * h));
+            g.gmax[k] = fminf(g.gmax[k], round_up(lo + ((double)g.R[k] + kStrayCells + 3.0) * h));
         }
     }
-    g.ncells = R[0] * R[1] * R[2];
-    g.pad = 0;
     g.sigma_max = kSigmaCells / (hmax * hmax);
     g.diag_max = kLargeCells * sqrt(h2) * (1.0 + 0x1p-30);
     *ix.grid = g;

@@ -9,7 +9,7 @@
 // gives (-1, NaN).  With a radius, a target is accepted only if d2 < r2 = (float)(max_dist * max_dist) (strict, as the radius
 // search of open3d's SearchHybrid); a query with none gives (-1, +inf).
 //
-// Index (built once, reused by every query batch): a uniform grid of at most B = min(2n, 2^22) cells over the bulk of the
+// Index (built once, reused by every query batch): the grid of bulk_grid.hpp, at most B = min(2n, 2^22) cells over the bulk of the
 // targets.  k_nn_bounds (one workgroup) takes the bounding box of all finite targets and, from a strided subsample of 2048, the
 // 1/64 and 63/64 per-axis quantiles ("bulk"); cells are near-cubic over the bulk, at most 1024 per axis, and every target outside
 // the bulk is clamped into a border cell.  k_nn_keys gives each target its cell (non-finite: the sentinel cell `ncells`), the radix
@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "bulk_grid.hpp"
 #include "draw_common.hpp"
 #include "grid_common.hpp"
 #include "mesh_area.hpp"
@@ -40,16 +41,16 @@
 
 namespace nsa {
 
-constexpr uint32_t kNnMaxCells = 1u << 22;
-constexpr uint32_t kNnMaxRes = 1024;
-constexpr uint32_t kNnSubsample = 2048;
+using bulk::axis_cell;
+using bulk::block_reduce;
+using bulk::finite3;
+using bulk::lower_bound;
+using bulk::up256;
+
 constexpr uint32_t kMaxCount = 0x7FFFFFFFu;
 
-struct NnGrid {                  // written by k_nn_bounds, read by every later kernel of the build and by k_nn_query
-    float lo[3], h[3], inv_h[3];
-    uint32_t R[3], ncells, pad;
-    float gmin[3], gmax[3];      // bounding box of the finite targets (+inf / -inf when there are none)
-};
+using NnGrid = bulk::Grid;       // written by k_nn_bounds, read by every later kernel of the build and by k_nn_query; gmin / gmax: the
+                                 // bounding box of the finite targets
 
 struct NnIndex {                 // views into the caller's index buffer (nsa_nn_workspace bytes)
     NnGrid* grid;
@@ -63,17 +64,16 @@ struct NnIndex {                 // views into the caller's index buffer (nsa_nn
     uint32_t* counts;            // [256 * 256]
 };
 
-__host__ __device__ inline uint64_t align256(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 __host__ __device__ inline uint32_t nn_budget(uint32_t n) {
     const uint64_t b = 2ull * n;
-    return (uint32_t)(b < 1 ? 1 : (b > kNnMaxCells ? kNnMaxCells : b));
+    return (uint32_t)(b < 1 ? 1 : (b > bulk::kMaxCells ? bulk::kMaxCells : b));
 }
 
 __host__ __device__ inline uint64_t nn_carve(void* ws, uint32_t n, NnIndex* out) {
     const uint32_t B = nn_budget(n);
     char* base = static_cast<char*>(ws);
     uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
+    auto take = [&](uint64_t bytes) { char* p = base ? base + o : nullptr; o += up256(bytes); return p; };
     NnIndex x;
     x.grid = reinterpret_cast<NnGrid*>(take(sizeof(NnGrid)));
     x.start = reinterpret_cast<uint32_t*>(take(4ull * (B + 2)));
@@ -89,17 +89,6 @@ __host__ __device__ inline uint64_t nn_carve(void* ws, uint32_t n, NnIndex* out)
     return o;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
-// cell index along one axis, clamped into [0, R - 1] (x finite)
-__device__ __forceinline__ uint32_t axis_cell(float x, float lo, float inv_h, uint32_t R) {
-#pragma clang fp contract(off)
-    const float u = (x - lo) * inv_h;
-    return (uint32_t)fminf(fmaxf(u, 0.0f), (float)(R - 1));
-}
-
 __device__ __forceinline__ uint32_t cell_key(const NnGrid& g, float x, float y, float z) {
     if (!finite3(x, y, z)) return g.ncells;
     const uint32_t cx = axis_cell(x, g.lo[0], g.inv_h[0], g.R[0]), cy = axis_cell(y, g.lo[1], g.inv_h[1], g.R[1]),
@@ -107,24 +96,11 @@ __device__ __forceinline__ uint32_t cell_key(const NnGrid& g, float x, float y, 
     return (cx * g.R[1] + cy) * g.R[2] + cz;
 }
 
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {    // 1024 threads; red[16]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int w = 1; w < 16; ++w) r = op(r, red[w]);
-    return r;
-}
-
 __global__ __launch_bounds__(1024) void k_nn_bounds(const float* __restrict__ t, uint32_t n, uint32_t budget, NnIndex ix) {
-    __shared__ float sv[3][kNnSubsample];
+    __shared__ float sv[3][bulk::kSubsample];
     __shared__ float red[16];
     __shared__ uint32_t redu[16];
-    __shared__ float bulk[2][3];
+    __shared__ float s_bulk[2][3];
     const uint32_t tid = threadIdx.x;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t i = tid; i < n; i += 1024) {
@@ -140,9 +116,9 @@ __global__ __launch_bounds__(1024) void k_nn_bounds(const float* __restrict__ t,
         gmax[k] = block_reduce(mx[k], [](float a, float b) { return fmaxf(a, b); }, red);
     }
     // strided subsample; non-finite points are left out of the ranking (+inf and not counted)
-    const uint32_t m = n < kNnSubsample ? n : kNnSubsample;
+    const uint32_t m = n < bulk::kSubsample ? n : bulk::kSubsample;
     uint32_t nf = 0;
-    for (uint32_t j = tid; j < kNnSubsample; j += 1024) {
+    for (uint32_t j = tid; j < bulk::kSubsample; j += 1024) {
         bool ok = false;
         float x = INFINITY, y = INFINITY, z = INFINITY;
         if (j < m) {
@@ -156,58 +132,15 @@ __global__ __launch_bounds__(1024) void k_nn_bounds(const float* __restrict__ t,
         nf += ok;
     }
     const uint32_t m_f = block_reduce(nf, [](uint32_t a, uint32_t b) { return a + b; }, redu);
-    __syncthreads();
-    const uint32_t k_lo = m_f >> 6, k_hi = m_f ? m_f - 1 - k_lo : 0;
-    for (int a = 0; a < 3; ++a) {
-        for (uint32_t j = tid; j < m; j += 1024) {
-            const float v = sv[a][j];
-            if (!__builtin_isfinite(v)) continue;
-            uint32_t rank = 0;
-            for (uint32_t i = 0; i < m; ++i) {
-                const float w = sv[a][i];
-                rank += (w < v) || (w == v && i < j);
-            }
-            if (rank == k_lo) bulk[0][a] = v;
-            if (rank == k_hi) bulk[1][a] = v;
-        }
-    }
-    __syncthreads();
+    bulk::rank_bulk(sv, m, m_f, s_bulk);
     if (tid != 0) return;
     NnGrid g;
-    double e[3], emax = 0.0;
+    bulk::solve(s_bulk[0], s_bulk[1], m_f, budget, g);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         g.gmin[k] = gmin[k];
         g.gmax[k] = gmax[k];
-        g.lo[k] = m_f ? bulk[0][k] : 0.0f;
-        e[k] = m_f ? (double)bulk[1][k] - (double)bulk[0][k] : 0.0;
-        emax = e[k] > emax ? e[k] : emax;
     }
-    uint32_t R[3] = {1, 1, 1};
-    if (emax > 0.0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e[k] = e[k] > emax * 0x1p-10 ? e[k] : emax * 0x1p-10;
-        double c = cbrt(e[0] * e[1] * e[2] / budget);
-        for (int it = 0; it < 200; ++it) {             // near-cubic cells, at most `budget` of them
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double r = floor(e[k] / c);
-                R[k] = r < 1.0 ? 1u : (r > kNnMaxRes ? kNnMaxRes : (uint32_t)r);
-            }
-            if ((uint64_t)R[0] * R[1] * R[2] <= budget) break;
-            c *= 1.0625;
-        }
-        if ((uint64_t)R[0] * R[1] * R[2] > budget) R[0] = R[1] = R[2] = 1;     // (never reached; keeps the cell arrays in bounds)
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float h = emax > 0.0 ? (float)(e[k] / R[k]) : 1.0f;
-        g.h[k] = h > 1e-30f ? h : 1e-30f;
-        g.inv_h[k] = 1.0f / g.h[k];
-        g.R[k] = R[k];
-    }
-    g.ncells = R[0] * R[1] * R[2];
-    g.pad = 0;
     *ix.grid = g;
 }
 
@@ -226,16 +159,6 @@ __global__ __launch_bounds__(256) void k_nn_gather(const float* __restrict__ t, 
     const float x = t[3ull * p], y = t[3ull * p + 1], z = t[3ull * p + 2];
     ix.spts[i] = make_float4(x, y, z, __uint_as_float(p));
     ix.skey[i] = cell_key(g, x, y, z);
-}
-
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t* __restrict__ a, uint32_t n, uint32_t v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // one lane per cell c in [0, ncells + 1]: start[c], and the box of the points of cell c < ncells
@@ -378,7 +301,7 @@ __host__ __device__ inline uint64_t sample_carve(void* ws, uint32_t F, SampleWor
     const uint64_t nb = (F + kAreaBlock - 1) / kAreaBlock;
     char* base = static_cast<char*>(ws);
     uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
+    auto take = [&](uint64_t bytes) { char* p = base ? base + o : nullptr; o += up256(bytes); return p; };
     SampleWork w;
     w.local = reinterpret_cast<double*>(take(8ull * F));
     w.btot = reinterpret_cast<double*>(take(8ull * nb));

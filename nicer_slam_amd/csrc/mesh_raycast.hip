@@ -24,9 +24,10 @@
 // test itself, so no error analysis of the pruning is needed -- only that the pad is wide enough for the clause never to reject
 // what the edge functions accept (header Section 17 states when; tests/test_mesh_raycast_cpu.py asserts it on every case).
 //
-// Tree.  Section 16's: L, the cube, the Morton keys of the centroids, the stable radix argsort, a node per level and distinct key
-// prefix, pre-order numbering with `skip`; no atomics.  This unit keeps its own copy of that build (wn::Node stays as it is) and
-// adds to each node its box and a table of its (up to eight) children by octant.
+// Tree.  Section 16's, its topology built by octree_build.hpp: L, the cube, the Morton keys of the centroids, the stable radix argsort,
+// a node per level and distinct key prefix, pre-order numbering with `skip`; no atomics.  This unit adds to each sorted face its box
+// (inside the shared k_heads) and to each node its box and a table of its (up to eight) children by octant (cleared inside the shared
+// k_nodes, filled by k_rc_children).
 //
 // Walk of one ray (m = 4 [d_x < 0] + 2 [d_y < 0] + [d_z < 0]), from the root:
 //     visit(i):  nodes += 1 ;  the node's interval empty -> return ;  closest hit and enter > best t -> return
@@ -40,23 +41,20 @@
 //
 // Worst cases, slow and never wrong: all centroids in one leaf (every ray through its box tests every face); a face as large as the
 // mesh widens every box above it.
-#include "tri_common.hpp"
+#include "octree_build.hpp"
 
 namespace nsa {
 namespace rc {
 
-using tri::up256;
+using bulk::up256;
+using octree::Head;
+using octree::kLeafBit;
+using octree::kMaxLevel;
+using octree::max_nodes;
 
-constexpr uint32_t kMaxLevel = 10;
-constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kTile = 256;              // faces per LDS tile of k_ray_brute: 15 KiB a workgroup
 constexpr float kPadRel = 0x1p-20f;
-
-struct Head {                    // written by k_rc_bounds and k_rc_scan
-    uint32_t L, n_nodes, n_usable, pad;
-    double lo[3], scale;         // scale = 2^L / side
-};
 
 struct Node {                    // 32 bytes
     float lo[3], hi[3];
@@ -64,6 +62,21 @@ struct Node {                    // 32 bytes
     uint32_t begin;              // first sorted face
 };
 static_assert(sizeof(Node) == 32, "Node is read as one 32-byte record");
+
+// the padded box of a usable face: six fp32, each rounded outwards
+__device__ __forceinline__ void face_box(const float (&a)[3], const float (&b)[3], const float (&c)[3], float (&box)[6]) {
+#pragma clang fp contract(off)
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s = fmaxf(s, fmaxf(fmaxf(fabsf(a[k]), fabsf(b[k])), fabsf(c[k])));
+    const float pad = s * kPadRel;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float lo = fminf(fminf(a[k], b[k]), c[k]) - pad, hi = fmaxf(fmaxf(a[k], b[k]), c[k]) + pad;
+        box[k] = nextafterf(lo, -INFINITY);
+        box[3 + k] = nextafterf(hi, INFINITY);
+    }
+}
 
 struct Tree {                    // views into the caller's buffer (nsa_tri_ray_workspace bytes)
     Head* head;
@@ -77,21 +90,24 @@ struct Tree {                    // views into the caller's buffer (nsa_tri_ray_
     uint32_t* keys[2];           // [F] each: radix ping-pong
     uint32_t* tmp;               // [F]
     uint32_t* counts;            // [256 * 256]
-};
 
-__host__ __device__ inline uint32_t level_of(uint32_t n) {
-    uint32_t L = 0;
-    while (L < kMaxLevel && (8ull << (2 * L)) < (uint64_t)n) ++L;
-    return L;
-}
-__host__ __device__ inline uint64_t max_nodes(uint32_t F) {
-    uint64_t total = 0;
-    for (uint32_t l = 0; l <= level_of(F); ++l) {
-        const uint64_t cells = 1ull << (3 * l);
-        total += cells < F ? cells : F;
+    // the hooks of octree_build.hpp.  k_heads: the box of the face at sorted position i (zeros where there is no usable face)
+    static __device__ __forceinline__ void sorted_face(const Tree& t, const float* __restrict__ v, uint32_t V,
+                                                       const int32_t* __restrict__ f, uint32_t i, uint32_t g, bool live) {
+        float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (live) {
+            float a[3], b[3], c[3];
+            if (tri::load_face(v, V, f, g, a, b, c) == 0) face_box(a, b, c, box);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t.fbox[6ull * i + k] = box[k];
     }
-    return total;
-}
+    // k_nodes: no children yet
+    static __device__ __forceinline__ void new_node(const Tree& t, uint32_t n) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) t.child[8ull * n + o] = 0;
+    }
+};
 
 __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, Tree* out) {
     const uint64_t nmax = max_nodes(F);
@@ -115,194 +131,7 @@ __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, Tree* out) {
     return o;
 }
 
-// ---- build: Section 16's keys, sort, scan and node ranges (a copy: mesh_winding.hip is left as it is) --------------------------------
-
-// one workgroup of 1024: the usable faces' count and the box of their vertices, then L and the cube
-__global__ __launch_bounds__(1024) void k_rc_bounds(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                    Tree t) {
-#pragma clang fp contract(off)
-    __shared__ float s_lo[3][1024], s_hi[3][1024];
-    __shared__ uint32_t s_n[1024];
-    const uint32_t tid = threadIdx.x;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    uint32_t n = 0;
-    for (uint32_t i = tid; i < F; i += 1024) {
-        float a[3], b[3], c[3];
-        if (tri::load_face(v, V, f, i, a, b, c)) continue;
-        ++n;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], fminf(fminf(a[k], b[k]), c[k]));
-            hi[k] = fmaxf(hi[k], fmaxf(fmaxf(a[k], b[k]), c[k]));
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        s_lo[k][tid] = lo[k];
-        s_hi[k][tid] = hi[k];
-    }
-    s_n[tid] = n;
-    __syncthreads();
-    for (uint32_t w = 512; w > 0; w >>= 1) {
-        if (tid < w) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                s_lo[k][tid] = fminf(s_lo[k][tid], s_lo[k][tid + w]);
-                s_hi[k][tid] = fmaxf(s_hi[k][tid], s_hi[k][tid + w]);
-            }
-            s_n[tid] += s_n[tid + w];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        Head h{};
-        h.n_usable = s_n[0];
-        h.L = level_of(h.n_usable);
-        h.n_nodes = 0;
-        double side = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            h.lo[k] = h.n_usable ? (double)s_lo[k][0] + 0.0 : 0.0;         // + 0.0: -0 becomes +0
-            side = fmax(side, h.n_usable ? (double)s_hi[k][0] - (double)s_lo[k][0] : 0.0);
-        }
-        h.scale = h.n_usable ? (double)(1u << h.L) / side : 0.0;
-        *t.head = h;
-    }
-}
-
-__device__ __forceinline__ uint32_t spread3(uint32_t x) {       // bit i of a 10-bit x to bit 3 i
-    x &= 0x3FFu;
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-
-// the key of face i: the Morton code of its leaf cell, or `unusable` (above every code)
-__device__ __forceinline__ uint32_t face_key(const Head& h, const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
-                                             uint32_t i, uint32_t unusable) {
-#pragma clang fp contract(off)
-    float a[3], b[3], c[3];
-    if (tri::load_face(v, V, f, i, a, b, c)) return unusable;
-    uint32_t cell[3];
-    const double top = (double)((1u << h.L) - 1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double cen = (((double)a[k] + (double)b[k]) + (double)c[k]) / 3.0;
-        const double u = (cen - h.lo[k]) * h.scale;
-        cell[k] = (uint32_t)fmin(fmax(u, 0.0), top);
-    }
-    return (spread3(cell[0]) << 2) | (spread3(cell[1]) << 1) | spread3(cell[2]);
-}
-
-__global__ __launch_bounds__(256) void k_rc_keys(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                 uint32_t unusable, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= F) return;
-    t.keys[0][i] = face_key(*t.head, v, V, f, i, unusable);
-}
-
-// the padded box of a usable face: six fp32, each rounded outwards
-__device__ __forceinline__ void face_box(const float (&a)[3], const float (&b)[3], const float (&c)[3], float (&box)[6]) {
-#pragma clang fp contract(off)
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s = fmaxf(s, fmaxf(fmaxf(fabsf(a[k]), fabsf(b[k])), fabsf(c[k])));
-    const float pad = s * kPadRel;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float lo = fminf(fminf(a[k], b[k]), c[k]) - pad, hi = fmaxf(fmaxf(a[k], b[k]), c[k]) + pad;
-        box[k] = nextafterf(lo, -INFINITY);
-        box[3 + k] = nextafterf(hi, INFINITY);
-    }
-}
-
-// sorted keys, the faces' boxes, and h(i) -- at how many levels position i begins a node -- into base[i] (base[F] = 0), for the scan
-__global__ __launch_bounds__(256) void k_rc_heads(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                  uint32_t unusable, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i > F) return;
-    if (i == F) {
-        t.base[F] = 0;
-        return;
-    }
-    const Head h = *t.head;
-    const uint32_t g = t.order[i];
-    const uint32_t key = g < F ? face_key(h, v, V, f, g, unusable) : unusable;
-    t.skey[i] = key;
-    float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t n = 0;
-    if (i < h.n_usable && g < F) {
-        float a[3], b[3], c[3];
-        if (tri::load_face(v, V, f, g, a, b, c) == 0) face_box(a, b, c, box);
-        if (i == 0) {
-            n = h.L + 1;
-        } else {
-            const uint32_t gp = t.order[i - 1];
-            const uint32_t x = key ^ (gp < F ? face_key(h, v, V, f, gp, unusable) : unusable);
-            if (x) n = (31u - (uint32_t)__clz((int)x)) / 3u + 1u;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t.fbox[6ull * i + k] = box[k];
-    t.base[i] = n;
-}
-
-// one workgroup of 1024: base[0 .. F] becomes its exclusive prefix sum; the total is the node count
-__global__ __launch_bounds__(1024) void k_rc_scan(uint32_t F, Tree t) {
-    __shared__ uint32_t s_sum[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n = (uint64_t)F + 1, chunk = (n + 1023) / 1024;
-    const uint64_t lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += t.base[i];
-    s_sum[tid] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {                // Hillis-Steele, inclusive
-        const uint32_t add = tid >= off ? s_sum[tid - off] : 0;
-        __syncthreads();
-        s_sum[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = s_sum[tid] - sum;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const uint32_t x = t.base[i];
-        t.base[i] = run;
-        run += x;
-    }
-    if (tid == 1023) t.head->n_nodes = s_sum[1023];
-}
-
-// the first position in (i, n) whose key >> sh exceeds p (n when there is none)
-__device__ __forceinline__ uint32_t range_end(const uint32_t* __restrict__ skey, uint32_t i, uint32_t n, uint32_t sh, uint32_t p) {
-    uint32_t lo = i + 1, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((skey[mid] >> sh) > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// one lane per sorted position: the nodes that begin there, their ranges and skip indices; no children yet
-__global__ __launch_bounds__(256) void k_rc_nodes(uint32_t F, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const Head h = *t.head;
-    if (i >= F || i >= h.n_usable) return;
-    const uint32_t first = t.base[i], cnt = t.base[i + 1] - first;
-    if (cnt == 0 || cnt > h.L + 1) return;
-    const uint32_t lmin = h.L + 1 - cnt, key = t.skey[i];
-    for (uint32_t l = lmin; l <= h.L; ++l) {
-        const uint32_t n = first + (l - lmin), sh = 3 * (h.L - l);
-        const uint32_t e = range_end(t.skey, i, h.n_usable, sh, key >> sh);
-        t.end[n] = e;
-        t.node[n].begin = i;
-        t.node[n].skip = t.base[e] | (l == h.L ? kLeafBit : 0u);
-#pragma unroll
-        for (int o = 0; o < 8; ++o) t.child[8ull * n + o] = 0;
-    }
-}
+// ---- build: the topology is octree_build.hpp's; the child tables and the boxes of its nodes ---------------------------------------
 
 // one lane per sorted position: every node that begins there enters itself into its parent's table.  The parent of the first node
 // of the position is the node of the level above whose range holds the position: it begins at the first position of that prefix
@@ -362,12 +191,6 @@ __global__ __launch_bounds__(256) void k_rc_boxes(uint32_t F, Tree t) {
             t.node[n].hi[k] = hi[k];
         }
     }
-}
-
-__global__ void k_rc_info(Tree t, uint32_t* __restrict__ info) {
-    info[0] = t.head->L;
-    info[1] = t.head->n_nodes;
-    info[2] = t.head->n_usable;
 }
 
 // ---- query ----------------------------------------------------------------------------------------------------------------------
@@ -660,18 +483,13 @@ int nsa_tri_ray_build(const float* verts, uint32_t n_verts, const int32_t* faces
     if (!verts || !faces || !tree || n_verts == 0) return NSA_EBADARG;
     Tree t;
     carve(tree, n_faces, &t);
-    const uint32_t Lmax = level_of(n_faces), unusable = 1u << (3 * Lmax), nb = (n_faces + 255) / 256;
+    const uint32_t nb = (n_faces + 255) / 256;
     hipStream_t s = (hipStream_t)stream;
     launch_begin();
-    hipLaunchKernelGGL(k_rc_bounds, dim3(1), dim3(1024), 0, s, verts, n_verts, faces, n_faces, t);
-    hipLaunchKernelGGL(k_rc_keys, dim3(nb), dim3(256), 0, s, verts, n_verts, faces, n_faces, unusable, t);
-    radix_argsort(t.keys, t.tmp, t.order, t.counts, n_faces, 0, (3 * Lmax + 1 + 7) / 8, stream);
-    hipLaunchKernelGGL(k_rc_heads, dim3(n_faces / 256 + 1), dim3(256), 0, s, verts, n_verts, faces, n_faces, unusable, t);
-    hipLaunchKernelGGL(k_rc_scan, dim3(1), dim3(1024), 0, s, n_faces, t);
-    hipLaunchKernelGGL(k_rc_nodes, dim3(nb), dim3(256), 0, s, n_faces, t);
+    octree::build(verts, n_verts, faces, n_faces, t, s);
     hipLaunchKernelGGL(k_rc_children, dim3(nb), dim3(256), 0, s, n_faces, t);
     hipLaunchKernelGGL(k_rc_boxes, dim3((uint32_t)((max_nodes(n_faces) + 3) / 4)), dim3(256), 0, s, n_faces, t);
-    if (info) hipLaunchKernelGGL(k_rc_info, dim3(1), dim3(1), 0, s, t, info);
+    if (info) hipLaunchKernelGGL(octree::k_info<Tree>, dim3(1), dim3(1), 0, s, t, info);
     return launch_end();
 }
 

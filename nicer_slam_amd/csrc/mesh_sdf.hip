@@ -100,12 +100,7 @@ __device__ __forceinline__ bool face_vertices(const float* __restrict__ v, uint3
     return true;
 }
 
-__device__ __forceinline__ void cross3(const double (&u)[3], const double (&w)[3], double (&n)[3]) {
-#pragma clang fp contract(off)
-    n[0] = u[1] * w[2] - u[2] * w[1];
-    n[1] = u[2] * w[0] - u[0] * w[2];
-    n[2] = u[0] * w[1] - u[1] * w[0];
-}
+using bulk::cross3;
 
 // n = weight * (ab x ac) / |ab x ac| added to N, component by component
 __device__ __forceinline__ void add_unit_normal(const float (&x)[3][3], double weight, bool weighted, double (&N)[3]) {

@@ -15,20 +15,14 @@
 //     Omega = 2 atan2(det, den), and Omega = 0 when det == 0 (a query on a vertex or in the face's plane: a defined value)
 // A face whose ab x ac points away from q has Omega > 0.
 //
-// Tree.  lo_k = the least coordinate k over the vertices of the usable faces, side = the largest extent over the three axes,
-// L = the smallest integer with 8 * 4^L >= F_usable, at most 10.  Face t has centroid_t = ((a + b) + c) / 3 and lies in the leaf cell
-// cell_k = min(2^L - 1, (uint32) max((centroid_k - lo_k) * (2^L / side), 0)); its key is the 3 L-bit Morton code of the cell (x the highest
-// bit of each triple).  The faces are in the order of the stable radix argsort of their keys: ascending face index within a leaf.  A
-// node (l, p) exists for every level l in [0, L] and every distinct prefix p = key >> 3 (L - l); its faces are a contiguous range
-// of that order.  Per face n_t = (ab x ac) / 2 (component by component), area_t = sqrt((n_x n_x + n_y n_y) + n_z n_z).  Per node, every
-// sum from +0:
+// Tree.  The linear octree of octree_build.hpp over the usable faces: L, the cube, the Morton keys of the centroids
+// centroid_t = ((a + b) + c) / 3, the stable radix argsort, a node per level and distinct key prefix over a contiguous range of the
+// sorted faces, pre-order numbering with `skip`.  That header builds the topology; this unit adds the moments.  Per face
+// n_t = (ab x ac) / 2 (component by component), area_t = sqrt((n_x n_x + n_y n_y) + n_z n_z).  Per node, every sum from +0:
 //     leaf     N = sum n_t, area = sum area_t, M = sum area_t centroid_t, over its faces in sorted order
 //     parent   the same three sums over its children in ascending key order
 //     P = M / area ;  r2 = the largest (x_x x_x + x_y x_y) + x_z x_z, x = v - P, over the vertices v of its faces (a maximum: any order)
-// The nodes are stored in pre-order, children in ascending key order, each with the index `skip` of the first node behind its
-// subtree.  With h(i) the number of levels at which sorted position i begins a node and base = the exclusive prefix sum of h, node
-// (l, first face i) has pre-order index base[i] + (l - lmin(i)), lmin(i) = L + 1 - h(i), and skip = base[end of its range]: no second
-// sort is needed.  No atomic takes part in the build: the order of every sum is fixed by the sort.
+// No atomic takes part in the build: the order of every sum is fixed by the sort.
 //
 // Query.  S = +0, i = 0; while i < nodes: d = P_i - q, d2 = dot(d, d);
 //     d2 > beta^2 r2_i      S += dot(N_i, d) / (d2 sqrt(d2)), i = skip_i                                       (accepted += 1)
@@ -41,23 +35,20 @@
 // Worst cases, slow and never wrong: every face in one leaf (coincident centroids: one lane sums the leaf in the build and every
 // query near it evaluates all of them); a query on the surface descends to the leaves about it.  A query far from the mesh accepts
 // the root: one node.  A node whose only child repeats it (a chain down to a lone face) costs the walk one step per level.
-#include "tri_common.hpp"
+#include "octree_build.hpp"
 
 namespace nsa {
 namespace wn {
 
+using bulk::cross3;
+using bulk::up256;
+using octree::Head;
+using octree::kLeafBit;
+using octree::max_nodes;
 using tri::dot3;
-using tri::up256;
 
-constexpr uint32_t kMaxLevel = 10;
-constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr double kFourPi = 0x1.921fb54442d18p+3;
 constexpr uint32_t kTile = 256;              // faces per LDS tile of k_winding_exact: 9 KiB a workgroup
-
-struct Head {                    // written by k_wn_bounds and k_wn_scan
-    uint32_t L, n_nodes, n_usable, pad;
-    double lo[3], scale;         // scale = 2^L / side
-};
 
 struct Node {                    // 64 bytes
     double P[3], N[3], r2;
@@ -78,22 +69,11 @@ struct Tree {                    // views into the caller's buffer (nsa_tri_wind
     uint32_t* keys[2];           // [F] each: radix ping-pong
     uint32_t* tmp;               // [F]
     uint32_t* counts;            // [256 * 256]
-};
 
-// the level of a mesh of n usable faces, and the most nodes a mesh of F faces can have: at level l at most min(8^l, F)
-__host__ __device__ inline uint32_t level_of(uint32_t n) {
-    uint32_t L = 0;
-    while (L < kMaxLevel && (8ull << (2 * L)) < (uint64_t)n) ++L;
-    return L;
-}
-__host__ __device__ inline uint64_t max_nodes(uint32_t F) {
-    uint64_t total = 0;
-    for (uint32_t l = 0; l <= level_of(F); ++l) {
-        const uint64_t cells = 1ull << (3 * l);
-        total += cells < F ? cells : F;
-    }
-    return total;
-}
+    // the hooks of octree_build.hpp: the topology is all this tree takes from the shared kernels
+    static __device__ __forceinline__ void sorted_face(const Tree&, const float*, uint32_t, const int32_t*, uint32_t, uint32_t, bool) {}
+    static __device__ __forceinline__ void new_node(const Tree&, uint32_t) {}
+};
 
 __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, Tree* out) {
     const uint64_t nmax = max_nodes(F);
@@ -117,177 +97,7 @@ __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, Tree* out) {
     return o;
 }
 
-__device__ __forceinline__ void cross3(const double (&u)[3], const double (&w)[3], double (&n)[3]) {
-#pragma clang fp contract(off)
-    n[0] = u[1] * w[2] - u[2] * w[1];
-    n[1] = u[2] * w[0] - u[0] * w[2];
-    n[2] = u[0] * w[1] - u[1] * w[0];
-}
-
-// ---- build ----------------------------------------------------------------------------------------------------------------------
-
-// one workgroup of 1024: the usable faces' count and the box of their vertices, then L and the cube
-__global__ __launch_bounds__(1024) void k_wn_bounds(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                    Tree t) {
-#pragma clang fp contract(off)
-    __shared__ float s_lo[3][1024], s_hi[3][1024];
-    __shared__ uint32_t s_n[1024];
-    const uint32_t tid = threadIdx.x;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    uint32_t n = 0;
-    for (uint32_t i = tid; i < F; i += 1024) {
-        float a[3], b[3], c[3];
-        if (tri::load_face(v, V, f, i, a, b, c)) continue;
-        ++n;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], fminf(fminf(a[k], b[k]), c[k]));
-            hi[k] = fmaxf(hi[k], fmaxf(fmaxf(a[k], b[k]), c[k]));
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        s_lo[k][tid] = lo[k];
-        s_hi[k][tid] = hi[k];
-    }
-    s_n[tid] = n;
-    __syncthreads();
-    for (uint32_t w = 512; w > 0; w >>= 1) {
-        if (tid < w) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                s_lo[k][tid] = fminf(s_lo[k][tid], s_lo[k][tid + w]);
-                s_hi[k][tid] = fmaxf(s_hi[k][tid], s_hi[k][tid + w]);
-            }
-            s_n[tid] += s_n[tid + w];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        Head h{};
-        h.n_usable = s_n[0];
-        h.L = level_of(h.n_usable);
-        h.n_nodes = 0;
-        double side = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            h.lo[k] = h.n_usable ? (double)s_lo[k][0] + 0.0 : 0.0;         // + 0.0: -0 becomes +0
-            side = fmax(side, h.n_usable ? (double)s_hi[k][0] - (double)s_lo[k][0] : 0.0);
-        }
-        h.scale = h.n_usable ? (double)(1u << h.L) / side : 0.0;
-        *t.head = h;
-    }
-}
-
-__device__ __forceinline__ uint32_t spread3(uint32_t x) {       // bit i of a 10-bit x to bit 3 i
-    x &= 0x3FFu;
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-
-// the key of face i: the Morton code of its leaf cell, or `unusable` (above every code)
-__device__ __forceinline__ uint32_t face_key(const Head& h, const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
-                                             uint32_t i, uint32_t unusable) {
-#pragma clang fp contract(off)
-    float a[3], b[3], c[3];
-    if (tri::load_face(v, V, f, i, a, b, c)) return unusable;
-    uint32_t cell[3];
-    const double top = (double)((1u << h.L) - 1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double cen = (((double)a[k] + (double)b[k]) + (double)c[k]) / 3.0;
-        const double u = (cen - h.lo[k]) * h.scale;
-        cell[k] = (uint32_t)fmin(fmax(u, 0.0), top);
-    }
-    return (spread3(cell[0]) << 2) | (spread3(cell[1]) << 1) | spread3(cell[2]);
-}
-
-__global__ __launch_bounds__(256) void k_wn_keys(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                 uint32_t unusable, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= F) return;
-    t.keys[0][i] = face_key(*t.head, v, V, f, i, unusable);
-}
-
-// sorted keys, and h(i) -- at how many levels position i begins a node -- into base[i] (base[F] = 0), for the scan
-__global__ __launch_bounds__(256) void k_wn_heads(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t F,
-                                                  uint32_t unusable, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i > F) return;
-    if (i == F) {
-        t.base[F] = 0;
-        return;
-    }
-    const Head h = *t.head;
-    const uint32_t key = face_key(h, v, V, f, t.order[i], unusable);
-    t.skey[i] = key;
-    uint32_t n = 0;
-    if (i < h.n_usable) {
-        if (i == 0) {
-            n = h.L + 1;
-        } else {
-            const uint32_t x = key ^ face_key(h, v, V, f, t.order[i - 1], unusable);
-            if (x) n = (31u - (uint32_t)__clz((int)x)) / 3u + 1u;
-        }
-    }
-    t.base[i] = n;
-}
-
-// one workgroup of 1024: base[0 .. F] becomes its exclusive prefix sum; the total is the node count
-__global__ __launch_bounds__(1024) void k_wn_scan(uint32_t F, Tree t) {
-    __shared__ uint32_t s_sum[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n = (uint64_t)F + 1, chunk = (n + 1023) / 1024;
-    const uint64_t lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += t.base[i];
-    s_sum[tid] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {                // Hillis-Steele, inclusive
-        const uint32_t add = tid >= off ? s_sum[tid - off] : 0;
-        __syncthreads();
-        s_sum[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = s_sum[tid] - sum;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const uint32_t x = t.base[i];
-        t.base[i] = run;
-        run += x;
-    }
-    if (tid == 1023) t.head->n_nodes = s_sum[1023];
-}
-
-// the first position in (i, n) whose key >> sh exceeds p (n when there is none)
-__device__ __forceinline__ uint32_t range_end(const uint32_t* __restrict__ skey, uint32_t i, uint32_t n, uint32_t sh, uint32_t p) {
-    uint32_t lo = i + 1, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((skey[mid] >> sh) > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// one lane per sorted position: the nodes that begin there, their ranges and skip indices
-__global__ __launch_bounds__(256) void k_wn_nodes(uint32_t F, Tree t) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const Head h = *t.head;
-    if (i >= F || i >= h.n_usable) return;
-    const uint32_t first = t.base[i], cnt = t.base[i + 1] - first;
-    if (cnt == 0) return;
-    const uint32_t lmin = h.L + 1 - cnt, key = t.skey[i];
-    for (uint32_t l = lmin; l <= h.L; ++l) {
-        const uint32_t n = first + (l - lmin), sh = 3 * (h.L - l);
-        const uint32_t e = range_end(t.skey, i, h.n_usable, sh, key >> sh);
-        t.end[n] = e;
-        t.node[n].begin = i;
-        t.node[n].skip = t.base[e] | (l == h.L ? kLeafBit : 0u);
-    }
-}
+// ---- build: the topology is octree_build.hpp's; the moments and radii of its nodes ------------------------------------------------
 
 __device__ __forceinline__ bool load_sorted(const Tree& t, const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
                                             uint32_t F, uint32_t pos, float (&a)[3], float (&b)[3], float (&c)[3]) {
@@ -387,12 +197,6 @@ __global__ __launch_bounds__(256) void k_wn_radius(const float* __restrict__ v, 
         r2 = o > r2 ? o : r2;
     }
     if (lane == 0) t.node[n].r2 = r2;
-}
-
-__global__ void k_wn_info(Tree t, uint32_t* __restrict__ info) {
-    info[0] = t.head->L;
-    info[1] = t.head->n_nodes;
-    info[2] = t.head->n_usable;
 }
 
 // ---- query ----------------------------------------------------------------------------------------------------------------------
@@ -537,19 +341,14 @@ int nsa_tri_winding_build(const float* verts, uint32_t n_verts, const int32_t* f
     if (!verts || !faces || !tree || n_verts == 0) return NSA_EBADARG;
     Tree t;
     carve(tree, n_faces, &t);
-    const uint32_t Lmax = level_of(n_faces), unusable = 1u << (3 * Lmax), nb = (n_faces + 255) / 256;
+    const uint32_t Lmax = octree::level_of(n_faces), nb = (n_faces + 255) / 256;
     hipStream_t s = (hipStream_t)stream;
     launch_begin();
-    hipLaunchKernelGGL(k_wn_bounds, dim3(1), dim3(1024), 0, s, verts, n_verts, faces, n_faces, t);
-    hipLaunchKernelGGL(k_wn_keys, dim3(nb), dim3(256), 0, s, verts, n_verts, faces, n_faces, unusable, t);
-    radix_argsort(t.keys, t.tmp, t.order, t.counts, n_faces, 0, (3 * Lmax + 1 + 7) / 8, stream);
-    hipLaunchKernelGGL(k_wn_heads, dim3(n_faces / 256 + 1), dim3(256), 0, s, verts, n_verts, faces, n_faces, unusable, t);
-    hipLaunchKernelGGL(k_wn_scan, dim3(1), dim3(1024), 0, s, n_faces, t);
-    hipLaunchKernelGGL(k_wn_nodes, dim3(nb), dim3(256), 0, s, n_faces, t);
+    octree::build(verts, n_verts, faces, n_faces, t, s);
     for (uint32_t l = Lmax + 1; l-- > 0;)
         hipLaunchKernelGGL(k_wn_moments, dim3(nb), dim3(256), 0, s, verts, n_verts, faces, n_faces, l, t);
     hipLaunchKernelGGL(k_wn_radius, dim3((uint32_t)((max_nodes(n_faces) + 3) / 4)), dim3(256), 0, s, verts, n_verts, faces, n_faces, t);
-    if (info) hipLaunchKernelGGL(k_wn_info, dim3(1), dim3(1), 0, s, t, info);
+    if (info) hipLaunchKernelGGL(octree::k_info<Tree>, dim3(1), dim3(1), 0, s, t, info);
     return launch_end();
 }
 

@@ -1,20 +1,24 @@
 // tri_common.hpp -- the index layout, the per-face closest point and the ring walk of the closest-point index (DESIGN 4m, C ABI
 // Section 14), shared by mesh_closest.hip (build, unsigned query) and mesh_sdf.hip (signed and range-limited queries, Section 15).
-// The contract, the bounds and their margins are stated at the head of mesh_closest.hip.
+// The contract, the bounds and their margins are stated at the head of mesh_closest.hip; the grid under the index is bulk_grid.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "bulk_grid.hpp"
 #include "grid_common.hpp"
 #include "radix_sort.hpp"
 
 namespace nsa {
 namespace tri {
 
-constexpr uint32_t kMaxCells = 1u << 22;
-constexpr uint32_t kMaxRes = 1024;
-constexpr uint32_t kSubsample = 2048;
+using bulk::axis_cell;
+using bulk::finite3;
+using bulk::kMaxCells;
+using bulk::lower_bound;
+using bulk::up256;
+
 constexpr uint32_t kMaxCount = 0x7FFFFFFFu;
 constexpr double kLargeCells = 2.0;          // a grid face's box is at most this many cells long on every axis
 constexpr double kSigmaCells = 0x1p16;       // a grid face's sigma is at most this / hmax^2: rho <= 1/4 up to 2^12.5 cells from q,
@@ -25,16 +29,16 @@ constexpr double kRhoMax = 0.25;
 constexpr double kPad = 0x1p-40;             // box padding, relative to the coordinate's magnitude
 constexpr double kSlack = 1.0 + 0x1p-40;     // a bound must exceed best * kSlack
 
-struct Grid {                    // written by k_tri_bounds, read by every later kernel of the build and by k_tri_query
-    float lo[3], h[3], inv_h[3];
-    uint32_t R[3], ncells, pad;
-    float gmin[3], gmax[3];      // bounding box of the vertices of the usable faces (+inf / -inf when there are none), clipped to
-                                 // kStrayCells + 3 cells around the grid: the vertices of every grid face lie inside
+struct Grid : bulk::Grid {       // written by k_tri_bounds, read by every later kernel of the build and by k_tri_query.  gmin / gmax:
+                                 // the box of the vertices of the usable faces, clipped to kStrayCells + 3 cells around the grid:
+                                 // the vertices of every grid face lie inside
     double sigma_max;            // kSigmaCells / hmax^2
     double diag_max;             // upper bound of a grid face's longest edge: kLargeCells * |h|
 };
-// mesh_eval.TriIndex.layout() reads h, R, ncells and the three counts behind start[ncells] at these offsets of the index buffer
-static_assert(offsetof(Grid, h) == 12 && offsetof(Grid, R) == 36 && offsetof(Grid, ncells) == 48 && sizeof(Grid) <= 256,
+// mesh_eval.TriIndex.layout() reads h, R, ncells and the three counts behind start[ncells] at these offsets of the index buffer (the
+// head is the first base of Grid: at offset 0)
+static_assert(offsetof(bulk::Grid, h) == 12 && offsetof(bulk::Grid, R) == 36 && offsetof(bulk::Grid, ncells) == 48 &&
+                  sizeof(Grid) == sizeof(bulk::Grid) + 16 && sizeof(Grid) <= 256,
               "struct Grid moved: update TriIndex.layout() in nicer_slam_amd/mesh_eval.py");
 
 struct Index {                   // views into the caller's index buffer (nsa_tri_workspace bytes)
@@ -49,7 +53,6 @@ struct Index {                   // views into the caller's index buffer (nsa_tr
     uint32_t* counts;            // [256 * 256]
 };
 
-__host__ __device__ inline uint64_t up256(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 __host__ __device__ inline uint32_t budget(uint32_t F) {
     const uint64_t b = 2ull * F;
     return (uint32_t)(b > kMaxCells ? kMaxCells : b);
@@ -75,10 +78,6 @@ __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, Index* out) {
     return o;
 }
 
-__device__ __forceinline__ bool finite3(const float (&p)[3]) {
-    return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]);
-}
-
 // the vertices of face i; 0 = usable, else the cause it is skipped for (1 index, 2 non-finite vertex, 3 zero area)
 __device__ __forceinline__ int load_face(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f, uint32_t i,
                                          float (&a)[3], float (&b)[3], float (&c)[3]) {
@@ -97,23 +96,6 @@ __device__ __forceinline__ int load_face(const float* __restrict__ v, uint32_t V
     const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
     if (nx == 0.0 && ny == 0.0 && nz == 0.0) return 3;
     return 0;
-}
-
-// cell index along one axis, clamped into [0, R - 1] (x finite)
-__device__ __forceinline__ uint32_t axis_cell(float x, float lo, float inv_h, uint32_t R) {
-#pragma clang fp contract(off)
-    const float u = (x - lo) * inv_h;
-    return (uint32_t)fminf(fmaxf(u, 0.0f), (float)(R - 1));
-}
-
-__device__ __forceinline__ uint32_t lower_bound(const uint32_t* __restrict__ a, uint32_t n, uint32_t x) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 struct Best {
