@@ -1393,6 +1393,84 @@ int nsa_mesh_cluster_place(const float *verts, uint32_t n_verts, const int32_t *
                            const int32_t *vertex_cluster, const int32_t *cluster_vertex, uint32_t n_out, void *workspace,
                            float *out_verts, float *out_normals, float *out_colours, int32_t *out_cell, nsa_stream_t stream);
 
+/* ---- Section 20: mesh orientation (consistent winding, orientability, outward by volume; DESIGN 4s, csrc/mesh_orient.hip) ---- */
+
+/* A consistent winding for faces[n_faces, 3] int32, after nsa_mesh_edges (Section 18) on the same mesh, from its face_edges,
+ * edge_start, edge_halfedges and its totals as they lie on the device (totals[0] = E is read there, never on the host).
+ * 3 * n_faces < 2^31.  tests/orient_ref.py restates this statement as a sequential breadth-first two-colouring.  Integer work only.
+ *
+ * Joining rule.  Two contributing faces are JOINED across an edge only when that edge carries exactly two half-edges (trimesh's
+ * face_adjacency rule).  An edge with one half-edge, or with three or more, joins nothing: a winding across a non-manifold edge
+ * is not defined.  Half-edge 3 f + k runs faces[f][k] -> faces[f][(k + 1) % 3]; the two faces AGREE when their half-edges run in
+ * opposite directions along the edge.  The closure is transitive.  (Departure from Section 18's face components, which join across
+ * every edge of count >= 2: orient_label cuts at a non-manifold edge, as trimesh's split does.)
+ *
+ * Double cover.  2 * n_faces nodes: node 2 f is face f as given, node 2 f + 1 is face f reversed.  An agreeing pair (f, g)
+ * unites 2 f ~ 2 g and 2 f + 1 ~ 2 g + 1; a disagreeing pair unites 2 f ~ 2 g + 1 and 2 f + 1 ~ 2 g.  The union-find is Section
+ * 11's uf_find / uf_unite, unchanged.  After all unions, with r0 = find(2 f) and r1 = find(2 f + 1):
+ *   orient_label[n_faces] int32   min(r0, r1) >> 1: the smallest face index of the face's component; -1 for a face that does not
+ *                                 contribute
+ *   orientable[n_faces] uint8     r0 != r1.  A component whose two sheets meet is not orientable (a Moebius strip, a Klein bottle);
+ *                                 the value is the same for every face of a component; 0 for a face that does not contribute
+ *   flip[n_faces] uint8           orientable and r0 > r1.  Reversing the flipped faces winds every orientable component consistently
+ *                                 with its smallest face, which keeps its winding; a non-orientable component is left as it is
+ * totals[4] (uint64, device): {components, non-orientable components, flipped faces, status}
+ * status: Section 11's bits (1: walk, 2: hook); 0 unless the implementation is wrong.
+ *
+ * Determinism.  parent[x] <= x holds throughout, so a root is the smallest node of its tree whatever the interleaving, and the
+ * atomics decide nothing in the output: every output is a function of the arguments alone and bit-reproducible.  Input arrays that
+ * nsa_mesh_edges did not write give meaningless outputs, never an access out of bounds.
+ *
+ * Kernel shape: one lane per edge for the unions, one per face for the labels, per-block integer counts added by one
+ * workgroup.  No floating point, no atomics outside the union-find (and the or of its cap report).
+ *
+ * NULL arguments or 3 * n_faces >= 2^31: NSA_EBADARG before anything is launched.  n_faces = 0 launches nothing, writes nothing and
+ * returns 0.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_faces = 0 or 3 * n_faces >= 2^31) */
+uint64_t nsa_mesh_orient_workspace(uint32_t n_faces);
+
+int nsa_mesh_orient(const int32_t *faces, uint32_t n_faces, const int32_t *face_edges, const int32_t *edge_start,
+                    const int32_t *edge_halfedges, const uint64_t *edge_totals, void *workspace, int32_t *orient_label,
+                    uint8_t *orientable, uint8_t *flip, uint64_t *totals, nsa_stream_t stream);
+
+/* Outward by volume, after nsa_mesh_orient on the same mesh: which of its two consistent windings an orientable, closed component
+ * gets.  verts[n_verts, 3] fp32; origin[3] fp32 ON THE DEVICE (the caller passes o = the centre of the bounding box of the used
+ * vertices rounded to fp32; any finite point gives a valid rule, a point near the mesh the tightest bound).
+ * tests/orient_ref.py restates this with math.fsum.
+ *
+ * Components are those of orient_label.  A component is CLOSED when every half-edge of its faces lies on an edge of count 2
+ * (edge_start[e + 1] - edge_start[e] == 2).  The rule is strict: a tetrahedron that touches another along an edge is not closed.
+ * Per component c of n_c faces, in float64 on the fp32 inputs, every operation rounded on its own:
+ *   S_c = (sum over its faces of s_f * det(a - o, b - o, c - o)) / 6,   s_f = -1 for a flipped face, +1 otherwise
+ *   P_c = (sum over its faces of perm(|a - o|, |b - o|, |c - o|)) / 6   (the same six products with absolute values)
+ *   det(a, b, c) = (a_x (b_y c_z - b_z c_y) + a_y (b_z c_x - b_x c_z)) + a_z (b_x c_y - b_y c_x)
+ * The component is DECIDED when it is closed, orientable and |S_c| > (n_c + 16) * 2^-52 * P_c, the forward error bound of the sum,
+ * doubled; a decided component is TOGGLED when S_c < 0.  Open, non-orientable and undecided components keep nsa_mesh_orient's
+ * winding.  The sums are indexed by the component's label (its smallest face); entries at other indices are not written:
+ *   comp_S[n_faces], comp_P[n_faces] float64;  comp_n[n_faces] int32;  comp_flags[n_faces] uint8: 1 closed | 2 decided | 4 toggled
+ *   flip_out[n_faces] uint8     flip[f] xor toggled(component of f); 0 for a face that does not contribute
+ * totals[5] (uint64, device): {closed components, decided components, toggled components, flipped faces after the toggles, status}
+ * status: 4 when the sort order is not a permutation or a run does not start at its label; 0 unless the implementation is wrong.
+ *
+ * Order of the additions.  The faces are sorted stably by label (Section 4's radix argsort), so a component is one run in ascending
+ * face index.  Blocks of 1024 sorted positions: within a block a segmented Hillis-Steele scan (x_t += x_(t - d), d = 1, 2, 4, ...,
+ * while t - d is in the same run and block); a run that crosses blocks leaves one partial per block, and those are added by 256
+ * threads, thread t taking partials t, t + 256, ... in order, then a binary tree over the threads.  No atomics: the sums are a
+ * function of the arguments alone and bit-reproducible; they are NOT the sums in face order (the bound above covers any order).
+ *
+ * NULL arguments (verts may be NULL when n_verts = 0), n_verts >= 2^31 or 3 * n_faces >= 2^31: NSA_EBADARG before anything is
+ * launched.  n_faces = 0 launches nothing and returns 0.  A face index outside [0, n_verts) is never dereferenced (the face adds
+ * zero).  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_faces = 0 or 3 * n_faces >= 2^31) */
+uint64_t nsa_mesh_orient_volume_workspace(uint32_t n_faces);
+
+int nsa_mesh_orient_volume(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, const int32_t *face_edges,
+                           const int32_t *edge_start, const int32_t *orient_label, const uint8_t *orientable, const uint8_t *flip,
+                           const float *origin, void *workspace, double *comp_S, double *comp_P, int32_t *comp_n,
+                           uint8_t *comp_flags, uint8_t *flip_out, uint64_t *totals, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

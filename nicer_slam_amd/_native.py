@@ -415,3 +415,12 @@ lib.nsa_mesh_cluster_place.restype = _i
 lib.nsa_mesh_cluster_place.argtypes = [_p, _u32, _p, _u32, _p, _p, ctypes.POINTER(_f64), _f64, _f64, _i, _p, _p, _u32, _p, _p, _p,
                                        _p, _p, _p]
 EXPORTS += ["nsa_mesh_cluster_workspace", "nsa_mesh_cluster", "nsa_mesh_cluster_place_workspace", "nsa_mesh_cluster_place"]
+lib.nsa_mesh_orient_workspace.restype = _u64
+lib.nsa_mesh_orient_workspace.argtypes = [_u32]
+lib.nsa_mesh_orient.restype = _i
+lib.nsa_mesh_orient.argtypes = [_p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+lib.nsa_mesh_orient_volume_workspace.restype = _u64
+lib.nsa_mesh_orient_volume_workspace.argtypes = [_u32]
+lib.nsa_mesh_orient_volume.restype = _i
+lib.nsa_mesh_orient_volume.argtypes = [_p, _u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_orient_workspace", "nsa_mesh_orient", "nsa_mesh_orient_volume_workspace", "nsa_mesh_orient_volume"]

@@ -181,6 +181,7 @@ class TriIndex:
         self._winding = None                       # (tree buffer, info) of Section 16, built on first use
         self._ray = None                           # (tree buffer, info) of Section 17, built on first use
         self._topology = {}                        # weld setting -> report of Section 18, computed on first use
+        self._orientation = {}                     # weld setting -> result of Section 20, computed on first use
 
     @property
     def skipped(self):
@@ -249,6 +250,16 @@ class TriIndex:
             from .mesh_topology import topology
             self._topology[weld] = topology({"verts": self.verts, "faces": self.faces}, weld=weld)
         return dict(self._topology[weld])
+
+    def orientation(self, weld=True):
+        """``mesh_topology.orientation`` for the index's mesh (header Section 20): (orient_label, orientable, flip, report), computed
+        on first use and kept, once per ``weld`` setting, like ``topology``"""
+        weld = bool(weld)
+        if weld not in self._orientation:
+            from .mesh_topology import orientation
+            self._orientation[weld] = orientation({"verts": self.verts, "faces": self.faces}, weld=weld)
+        label, orientable, flip, report = self._orientation[weld]
+        return label, orientable, flip, dict(report)
 
     @torch.no_grad()
     def signed_query(self, points, max_dist=None, flip=False, weld=True, counts=False, normals=False):

@@ -10,11 +10,13 @@ index of mesh_eval.TriIndex.
   ``w > 0.5`` instead: an inside / outside test for meshes with holes.  The default ``"normal"`` is the pseudo-normal rule, unchanged.
   ``sign="auto"`` picks between the two: "normal" when the mesh is closed and consistently oriented, which
   ``mesh_topology.topology`` decides exactly, "winding" otherwise; ``resolve_sign`` returns the rule used.
+  ``orient=True`` (``--orient``) on the functions that take a ``sign=`` winds the mesh consistently and its closed components outward
+  first (``mesh_topology.orient``); "auto" is then resolved on the result.  The default changes nothing.
 * ``mesh_sdf_grid(mesh, resolution, ...)``: a narrow-band SDF volume of the mesh, NaN outside the band, in the point order of
   inference.get_grid_uniform; inference.marching_cubes meshes it as it is.
 * ``sdf_field_metrics(sdf, mesh, ...)``: the learned SDF field (a model, through inference.sdf_values, or any callable) against the
   mesh's signed distance at points scattered about its surface -- the field itself, not its marching-cubes level set.
-* ``python -m nicer_slam_amd.mesh_sdf MESH.ply --resolution R --bounds LO HI --band B --out SDF.npy [--flip]
+* ``python -m nicer_slam_amd.mesh_sdf MESH.ply --resolution R --bounds LO HI --band B --out SDF.npy [--flip] [--orient]
   [--sign winding|auto [--beta B | --exact]] [--points P.npy --out-dist D.npy [--out-winding W.npy]]``.
 
 For an open mesh the "normal" sign is that of the nearest surface element, not an inside / outside test; the "winding" sign is one.
@@ -43,6 +45,16 @@ def _on_device(points, index):
 
 
 SIGNS = ("normal", "winding", "auto")
+
+
+def _oriented(mesh, orient, weld=True, points=None):
+    """the TriIndex the functions below work on: that of ``mesh`` itself, or with ``orient`` that of
+    ``mesh_topology.orient(mesh, outward="volume", weld=weld)`` -- wound consistently, closed components outward"""
+    index = _index(mesh, points)
+    if not orient:
+        return index
+    from .mesh_topology import orient as orient_mesh
+    return TriIndex(index.verts, orient_mesh({"verts": index.verts, "faces": index.faces}, outward="volume", weld=weld)["faces"])
 
 
 def resolve_sign(mesh, sign, weld=True):
@@ -89,14 +101,16 @@ def _winding_signed(index, pts, max_dist, flip, beta):
 
 
 @torch.no_grad()
-def signed_distance(mesh, points, max_dist=None, flip=False, weld=True, sign="normal", beta=2.0):
+def signed_distance(mesh, points, max_dist=None, flip=False, weld=True, sign="normal", beta=2.0, orient=False):
     """[m] float64: the signed distance of ``points`` (CUDA tensor or array [m, 3]) to ``mesh`` (dict with ``verts`` and ``faces``, or
     a TriIndex): ``TriIndex.signed_query(...)[0]``.  +inf (-inf with ``flip``) where nothing lies within ``max_dist``.
     ``sign="winding"``: the same magnitude, negative where the winding number (of the mesh with its normals turned by ``flip``)
     exceeds 0.5 -- inside / outside also for a mesh with holes, where the hole counts as closed by a surface on which w = 1/2;
-    ``beta`` as in ``winding_number``; +inf where nothing lies within ``max_dist``, whatever ``flip``."""
+    ``beta`` as in ``winding_number``; +inf where nothing lies within ``max_dist``, whatever ``flip``.
+    ``orient=True``: the mesh goes through ``mesh_topology.orient(outward="volume")`` first, and ``sign="auto"`` is resolved on the
+    result -- for a mesh whose faces are not wound consistently, or all inwards."""
     sign, beta = _sign_rule(sign, beta, "signed_distance")
-    index = _index(mesh, points)
+    index = _oriented(mesh, orient, weld, points)
     sign = resolve_sign(index, sign, weld)
     if sign == "winding":
         return _winding_signed(index, _on_device(points, index), max_dist, flip, beta)
@@ -104,12 +118,15 @@ def signed_distance(mesh, points, max_dist=None, flip=False, weld=True, sign="no
 
 
 @torch.no_grad()
-def contains(mesh, points, flip=False, weld=True, method="normal", beta=2.0):
+def contains(mesh, points, flip=False, weld=True, method="normal", beta=2.0, orient=False):
     """[m] bool: whether each point lies strictly inside ``mesh`` -- a CLOSED manifold mesh with outward normals (``flip`` for inward
     ones).  A point on the surface, and a non-finite point, is not inside.  On an open mesh the answer is the side of the nearest
     surface element and says nothing about an inside.  ``method="winding"``: whether the winding number exceeds 0.5 (a NaN is not
-    inside) -- an answer for open meshes too, with every hole closed by the surface on which w = 1/2."""
+    inside) -- an answer for open meshes too, with every hole closed by the surface on which w = 1/2.  ``orient`` as in
+    ``signed_distance``."""
     method, beta = _sign_rule(method, beta, "contains")
+    if orient:
+        mesh = _oriented(mesh, True, weld, points)
     if method == "auto":
         mesh = _index(mesh, points)
         method = resolve_sign(mesh, method, weld)
@@ -134,14 +151,15 @@ def grid_points(ax, lo, hi):
 
 
 @torch.no_grad()
-def mesh_sdf_grid(mesh, resolution, grid_boundary=(-1, 1), band=None, flip=False, chunk=1 << 22, weld=True, sign="normal", beta=2.0):
+def mesh_sdf_grid(mesh, resolution, grid_boundary=(-1, 1), band=None, flip=False, chunk=1 << 22, weld=True, sign="normal", beta=2.0,
+                  orient=False):
     """fp32 [R, R, R]: the signed distance to ``mesh`` at the points of ``inference.get_grid_uniform(R, grid_boundary)``, in that
     list's order (the flat index runs over (y, x, z); ``.permute(1, 0, 2)`` is the (x, y, z) volume inference.marching_cubes takes,
     as in inference.sdf_grid).  ``band`` (a distance; None: none): points farther than it from the mesh are NaN, and their queries
     stop after the few rings the band reaches -- without it a grid over the whole cube is the slow case of DESIGN 4m.
     inference.marching_cubes emits no face for a cell with a non-finite corner, so the volume can be meshed as it is.
     ``sign="winding"``: the sign of ``signed_distance(..., sign="winding", beta=beta)``; the winding number is evaluated only at the
-    points within the band, so a banded grid still costs what the band sets."""
+    points within the band, so a banded grid still costs what the band sets.  ``orient`` as in ``signed_distance``."""
     sign, beta = _sign_rule(sign, beta, "mesh_sdf_grid")
     resolution = int(resolution)
     if resolution < 2 or resolution ** 3 >= 1 << 40:
@@ -152,7 +170,7 @@ def mesh_sdf_grid(mesh, resolution, grid_boundary=(-1, 1), band=None, flip=False
         raise ValueError("mesh_sdf_grid: band must be >= 0 or None")
     if chunk < 1:
         raise ValueError("mesh_sdf_grid: chunk must be >= 1")
-    index = _index(mesh)
+    index = _oriented(mesh, orient, weld)
     sign = resolve_sign(index, sign, weld)
     ax = grid_axis(resolution, grid_boundary, index.device)
     n = resolution ** 3
@@ -182,18 +200,19 @@ def field_metrics(f, d, band):
 
 
 @torch.no_grad()
-def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0, flip=False, weld=True, sign="normal", beta=2.0):
+def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0, flip=False, weld=True, sign="normal", beta=2.0,
+                      orient=False):
     """The SDF field ``sdf`` against the signed distance to ``mesh`` (the ground truth, or any surface the field should be the SDF
     of).  ``sdf``: a model (evaluated through inference.sdf_values) or a callable taking CUDA points [n, 3] fp32 and returning [n]
     values.  The points are ``mesh_eval.sample_surface(mesh, n_points, seed)`` each moved by a draw of N(0, sigma^2) per coordinate
     from a torch generator seeded with ``seed``, so they lie on both sides of the surface and on it.  Of the points within ``band``
     of the mesh: "mean abs error" and "rms error" of |f - d|, "sign agreement" (the share with (f < 0) == (d < 0)) and "points" (how
     many counted).  ``flip``: the mesh's normals point inwards.  ``sign="winding"``: d takes its sign from the winding number
-    (``signed_distance``), the rule to use when the mesh is open."""
+    (``signed_distance``), the rule to use when the mesh is open.  ``orient`` as in ``signed_distance``."""
     sign, beta = _sign_rule(sign, beta, "sdf_field_metrics")
     if not (n_points > 0 and sigma >= 0 and band >= 0):
         raise ValueError("sdf_field_metrics: needs n_points > 0, sigma >= 0 and band >= 0")
-    index = _index(mesh)
+    index = _oriented(mesh, orient, weld)
     sign = resolve_sign(index, sign, weld)
     pts, _ = sample_surface(index.verts, index.faces, int(n_points), seed)
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
@@ -229,6 +248,8 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=2.0, help="accuracy of the hierarchical winding number (>= 1)")
     ap.add_argument("--exact", action="store_true", help="the exact winding number: beta = +inf")
     ap.add_argument("--out-winding", metavar="W.npy", help="the winding numbers of --points, float64")
+    ap.add_argument("--orient", action="store_true",
+                    help="wind the mesh consistently, closed components outward, first (mesh_topology.orient)")
     a = ap.parse_args(argv)
     if (a.resolution is None) != (a.out is None):
         ap.error("--resolution and --out go together")
@@ -243,7 +264,7 @@ def main(argv=None):
     beta = math.inf if a.exact else a.beta
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_sdf: needs a GPU")
-    index = _index(read_ply(a.mesh))
+    index = _oriented(read_ply(a.mesh), a.orient)
     rule = resolve_sign(index, a.sign)
     result = {}
     if a.sign == "auto":                                       # (the other two say themselves; their output stays as it was)
