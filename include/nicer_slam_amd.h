@@ -1471,6 +1471,97 @@ int nsa_mesh_orient_volume(const float *verts, uint32_t n_verts, const int32_t *
                            const float *origin, void *workspace, double *comp_S, double *comp_P, int32_t *comp_n,
                            uint8_t *comp_flags, uint8_t *flip_out, uint64_t *totals, nsa_stream_t stream);
 
+/* ---- Section 21: mesh smoothing (vertex rings, Laplacian / Taubin steps, vertex normals; DESIGN 4t, csrc/mesh_smooth.hip) ---- */
+
+/* The vertex rings of a mesh, after nsa_mesh_edges (Section 18) on the same mesh, from its edges and its totals as they lie on the
+ * device (totals[0] = E is read there, never on the host).  6 * n_faces < 2^31 (the offsets are int32), n_verts < 2^31.
+ * tests/smooth_ref.py restates this section in numpy.  Integer work only; no atomics.
+ *   ring_start[n_verts + 1] int32   CSR offsets: row v owns [ring_start[v], ring_start[v + 1]); ring_start[n_verts] = 2 E
+ *   ring[6 * n_faces] int32         the neighbour index;          the first 2 E entries are valid, the rest are not written
+ *   ring_edge[6 * n_faces] int32    the edge id of {v, neighbour}, so any per-edge property (edge_count) is one gather
+ * Row v lists every u with {u, v} an edge, in ascending u: the neighbours below v come from the edges with hi == v, those above from
+ * the edges with lo == v.  A vertex on no contributing face has an empty row.
+ *
+ * Kernel shape: the edge table is sorted by (lo, hi); one stable argsort of Section 4's radix sort by hi, with only the
+ * 8-bit passes n_verts needs, gives the (hi, lo) order (the 3 * n_faces - E positions past E carry n_verts and sort last).  Then
+ * ring_start[v] = #{lo < v} + #{hi < v}, two binary searches and no scan, and the slot of every entry is a closed form of the two
+ * counts.  Every output is a function of the arguments alone and bit-reproducible.  An edge with an end outside [0, n_verts) takes no
+ * part; arrays that nsa_mesh_edges did not write give meaningless rows, never an access out of bounds.
+ *
+ * NULL arguments, n_verts >= 2^31 or 6 * n_faces >= 2^31: NSA_EBADARG before anything is launched.  n_faces = 0 launches nothing,
+ * writes nothing and returns 0 (every row is empty by definition).  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_faces = 0, 6 * n_faces >= 2^31, n_verts >= 2^31) */
+uint64_t nsa_mesh_ring_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_ring(const int32_t *edges, const uint64_t *edge_totals, uint32_t n_verts, uint32_t n_faces, void *workspace,
+                  int32_t *ring_start, int32_t *ring, int32_t *ring_edge, nsa_stream_t stream);
+
+#define NSA_SMOOTH_FREE 0   /* boundary vertices move like any other */
+#define NSA_SMOOTH_FIXED 1  /* boundary vertices keep their input */
+#define NSA_SMOOTH_CURVE 2  /* a boundary vertex is smoothed along the boundary edges only */
+
+/* n_steps smoothing steps over the rings of nsa_mesh_ring, with the edge_count of nsa_mesh_edges for the same mesh.  verts[n_verts, 3]
+ * fp32; fixed[n_verts] uint8 or NULL; factors[n_steps] float64 ON THE HOST, |f| <= 1 (Laplacian: lambda repeated; Taubin: lambda,
+ * mu, lambda, mu, ...); boundary one of NSA_SMOOTH_*; max_move > 0, +inf for none.  All float64 on the fp32 inputs, every operation
+ * rounded on its own, nothing contracted; tests/smooth_ref.py restates it operation by operation and the device equals it bit for bit.
+ *
+ * x^0_v = double(verts[v]).
+ *   live(v)          the row of v is not empty and its three coordinates are finite
+ *   on_boundary(v)   some entry of its row lies on an edge with edge_count == 1
+ *   v MOVES          live(v), fixed[v] == 0, and not (boundary == FIXED and on_boundary(v))
+ *   N'(v)            the entries u of the row with live(u), in row order; when boundary == CURVE and on_boundary(v) only those whose
+ *                    edge has edge_count == 1, so a rim is smoothed along itself and does not creep inward.  A non-manifold edge is
+ *                    an ordinary edge.
+ * One step with factor f, for all vertices at once from the previous step's positions: a moving v with n = |N'(v)| > 0 gets, per
+ * component,  s = ((x_u1 + x_u2) + x_u3) + ...,  m = s / n,  d = m - x_v,  y_v = x_v + f * d,  and with a finite max_move
+ * y_v = min(max(y_v, x^0_v - max_move), x^0_v + max_move).  Every other vertex keeps x_v.
+ * out[n_verts, 3] fp32: the positions after the last step rounded to nearest.  A vertex that cannot move -- not live, fixed, held at
+ * the boundary, or without a live neighbour -- is returned with its input BITS, NaN payloads included.  n_steps = 0 copies the input.
+ * state[n_verts] uint8 (out): 1 live | 2 on_boundary | 4 moves | 8 moves and |N'| > 0.
+ *
+ * Kernel shape: a prologue writes the float64 positions and the state byte, a second pass compacts every row to N' (both
+ * are constant over the steps), then one launch per step, one lane per vertex, over ping-pong float64 positions in the workspace; the
+ * last step rounds to fp32.  No atomics anywhere.
+ *
+ * NULL arguments (fixed may be NULL; the ring arrays and edge_count may be NULL when n_faces = 0, factors when n_steps = 0), a factor
+ * with |f| > 1 or NaN, max_move <= 0 or NaN, an unknown boundary, n_verts >= 2^31 or 6 * n_faces >= 2^31: NSA_EBADARG before anything
+ * is launched.  n_verts = 0 launches nothing and returns 0.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_verts = 0 or >= 2^31, 6 * n_faces >= 2^31) */
+uint64_t nsa_mesh_smooth_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_smooth(const float *verts, uint32_t n_verts, uint32_t n_faces, const int32_t *ring_start, const int32_t *ring,
+                    const int32_t *ring_edge, const int32_t *edge_count, const uint8_t *fixed, const double *factors, uint32_t n_steps,
+                    int boundary, double max_move, void *workspace, float *out, uint8_t *state, nsa_stream_t stream);
+
+#define NSA_NORMALS_AREA 0
+#define NSA_NORMALS_ANGLE 1
+
+/* Vertex normals from the faces.  verts[n_verts, 3] fp32, faces[n_faces, 3] int32, 3 * n_faces < 2^31; weighting one of NSA_NORMALS_*.
+ * The CORNERS are c = 3 f + k of the faces that contribute by Section 18's rule (indices in [0, n_verts), pairwise distinct) and whose
+ * three vertices are finite.  At corner c, with p0 the corner's vertex, p1 the next and p2 the previous vertex of the face, in float64
+ * from the fp32 coordinates, every operation rounded on its own:
+ *   a = p1 - p0,  b = p2 - p0,  n = a x b = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x)
+ * which follows the face winding (mesh_eval's face normal).  Per vertex, over its corners in ASCENDING c, starting from zero:
+ *   AREA:   N = sum of n
+ *   ANGLE:  N = sum of theta * (n / |n|),  |n| = sqrt((n_x^2 + n_y^2) + n_z^2),  theta = atan2(|n|, (a_x b_x + a_y b_y) + a_z b_z);
+ *           corners with |n| = 0 are skipped
+ * normals[n_verts, 3] fp32 = N / |N| rounded to nearest, |N| = sqrt((N_x^2 + N_y^2) + N_z^2); the zero vector when |N| is zero or not
+ * finite, which covers a vertex without a corner.  The AREA form is + - * / and sqrt only and equals tests/smooth_ref.py bit for bit;
+ * the ANGLE form depends on the device's atan2 in the last bits of float64.
+ * The corner-by-vertex order is one stable argsort of the 3 F corner keys (csrc/corner_table.hpp, shared with Section 15's
+ * adjacency).  No atomics; bit-reproducible.
+ *
+ * NULL arguments (faces and workspace may be NULL when n_faces = 0), an unknown weighting, n_verts >= 2^31 or 3 * n_faces >= 2^31:
+ * NSA_EBADARG before anything is launched.  n_verts = 0 launches nothing.  Nothing is allocated or synchronised. */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (a zero count, n_verts >= 2^31, 3 * n_faces >= 2^31) */
+uint64_t nsa_mesh_vertex_normals_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_vertex_normals(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, int weighting, void *workspace,
+                            float *normals, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -424,3 +424,19 @@ lib.nsa_mesh_orient_volume_workspace.argtypes = [_u32]
 lib.nsa_mesh_orient_volume.restype = _i
 lib.nsa_mesh_orient_volume.argtypes = [_p, _u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_orient_workspace", "nsa_mesh_orient", "nsa_mesh_orient_volume_workspace", "nsa_mesh_orient_volume"]
+lib.nsa_mesh_ring_workspace.restype = _u64
+lib.nsa_mesh_ring_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_ring.restype = _i
+lib.nsa_mesh_ring.argtypes = [_p, _p, _u32, _u32, _p, _p, _p, _p, _p]
+lib.nsa_mesh_smooth_workspace.restype = _u64
+lib.nsa_mesh_smooth_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_smooth.restype = _i
+lib.nsa_mesh_smooth.argtypes = [_p, _u32, _u32, _p, _p, _p, _p, _p, ctypes.POINTER(_f64), _u32, _i, _f64, _p, _p, _p, _p]
+lib.nsa_mesh_vertex_normals_workspace.restype = _u64
+lib.nsa_mesh_vertex_normals_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_vertex_normals.restype = _i
+lib.nsa_mesh_vertex_normals.argtypes = [_p, _u32, _p, _u32, _i, _p, _p, _p]
+EXPORTS += ["nsa_mesh_ring_workspace", "nsa_mesh_ring", "nsa_mesh_smooth_workspace", "nsa_mesh_smooth",
+            "nsa_mesh_vertex_normals_workspace", "nsa_mesh_vertex_normals"]
+SMOOTH_FREE, SMOOTH_FIXED, SMOOTH_CURVE = 0, 1, 2                           # NSA_SMOOTH_* of header Section 21
+NORMALS_AREA, NORMALS_ANGLE = 0, 1                                          # NSA_NORMALS_*

@@ -20,69 +20,38 @@
 // answer is the unbounded one, or none.
 //
 // Adjacency: the 3F corners keyed by adjacency vertex (V for a face that does not contribute), the stable radix argsort of
-// radix_sort.hpp -- corner 3g + k in index order, so ascending g within a vertex -- and the start offsets by binary search.  No atomic
-// takes part; the order of every sum is fixed by the sort.  A query that lands on a vertex of valence k walks k corners.
+// radix_sort.hpp -- corner 3g + k in index order, so ascending g within a vertex -- and the start offsets by binary search
+// (corner_table.hpp).  No atomic takes part; the order of every sum is fixed by the sort.  A query that lands on a vertex of valence k
+// walks k corners.
 #include "tri_common.hpp"
+#include "corner_table.hpp"
 
 namespace nsa {
 namespace tri {
 
-struct Adjacency {               // views into the caller's adjacency buffer (nsa_tri_adjacency_workspace bytes)
-    uint32_t* start;             // [V + 2]: first sorted position of key i; key V = corners of faces that do not contribute
-    uint32_t* corner;            // [3 F]: corners 3 g + k sorted by key, ascending within a key
-    uint32_t* skey;              // [3 F]: sorted keys
-    uint32_t* keys[2];           // [3 F] each: radix ping-pong
-    uint32_t* tmp;               // [3 F]
-    uint32_t* counts;            // [256 * 256]
-};
+// the adjacency buffer (nsa_tri_adjacency_workspace bytes) is the corner table of corner_table.hpp, which the vertex normals of
+// mesh_smooth.hip share: start [V + 2], corner [3 F] sorted by key and ascending within a key, and the sort's buffers
+using Adjacency = corners::Table;
 
 __host__ __device__ inline uint64_t carve_adjacency(void* ws, uint32_t V, uint32_t F, Adjacency* out) {
-    char* base = static_cast<char*>(ws);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { char* p = base ? base + o : nullptr; o += up256(bytes); return p; };
-    Adjacency x;
-    x.start = reinterpret_cast<uint32_t*>(take(4ull * ((uint64_t)V + 2)));
-    x.corner = reinterpret_cast<uint32_t*>(take(12ull * F));
-    x.skey = reinterpret_cast<uint32_t*>(take(12ull * F));
-    x.keys[0] = reinterpret_cast<uint32_t*>(take(12ull * F));
-    x.keys[1] = reinterpret_cast<uint32_t*>(take(12ull * F));
-    x.tmp = reinterpret_cast<uint32_t*>(take(12ull * F));
-    x.counts = reinterpret_cast<uint32_t*>(take(4ull * kRadixCountWords));
-    if (out) *out = x;
-    return o;
+    return corners::carve(ws, V, F, out);
 }
 
 // the key of corner i = 3 g + k: its adjacency vertex, or V when face g does not contribute
-__device__ __forceinline__ uint32_t corner_key(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
-                                               const int32_t* __restrict__ adj, uint32_t i) {
-    const uint32_t g = i / 3;
-    const int32_t j0 = adj[3ull * g], j1 = adj[3ull * g + 1], j2 = adj[3ull * g + 2];
-    if ((uint32_t)j0 >= V || (uint32_t)j1 >= V || (uint32_t)j2 >= V) return V;
-    float a[3], b[3], c[3];
-    if (load_face(v, V, f, g, a, b, c)) return V;
-    return (uint32_t)adj[i];
-}
-
-__global__ __launch_bounds__(256) void k_adj_keys(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
-                                                  const int32_t* __restrict__ adj, uint32_t n_corners, Adjacency ad) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_corners) return;
-    ad.keys[0][i] = corner_key(v, V, f, adj, i);
-}
-
-__global__ __launch_bounds__(256) void k_adj_gather(const float* __restrict__ v, uint32_t V, const int32_t* __restrict__ f,
-                                                    const int32_t* __restrict__ adj, uint32_t n_corners, Adjacency ad) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_corners) return;
-    ad.skey[i] = corner_key(v, V, f, adj, ad.corner[i]);
-}
-
-// one lane per key i in [0, V + 1]
-__global__ __launch_bounds__(256) void k_adj_start(uint32_t V, uint32_t n_corners, Adjacency ad) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i > V + 1) return;
-    ad.start[i] = lower_bound(ad.skey, n_corners, i);
-}
+struct AdjacencyKey {
+    const float* v;
+    uint32_t V;
+    const int32_t* f;
+    const int32_t* adj;
+    __device__ uint32_t operator()(uint32_t i) const {
+        const uint32_t g = i / 3;
+        const int32_t j0 = adj[3ull * g], j1 = adj[3ull * g + 1], j2 = adj[3ull * g + 2];
+        if ((uint32_t)j0 >= V || (uint32_t)j1 >= V || (uint32_t)j2 >= V) return V;
+        float a[3], b[3], c[3];
+        if (load_face(v, V, f, g, a, b, c)) return V;
+        return (uint32_t)adj[i];
+    }
+};
 
 // ---- the pseudo-normal ----------------------------------------------------------------------------------------------------------
 
@@ -279,14 +248,8 @@ int nsa_tri_adjacency_build(const float* verts, uint32_t n_verts, const int32_t*
         return NSA_EBADARG;
     Adjacency ad;
     carve_adjacency(adjacency, n_verts, n_faces, &ad);
-    const uint32_t P = 3 * n_faces, nb = (P + 255) / 256;
-    uint32_t bits = 1;
-    while ((1ull << bits) <= (uint64_t)n_verts) ++bits;                    // keys are <= n_verts
     launch_begin();
-    hipLaunchKernelGGL(k_adj_keys, dim3(nb), dim3(256), 0, (hipStream_t)stream, verts, n_verts, faces, adjacency_faces, P, ad);
-    radix_argsort(ad.keys, ad.tmp, ad.corner, ad.counts, P, 0, (bits + 7) / 8, stream);
-    hipLaunchKernelGGL(k_adj_gather, dim3(nb), dim3(256), 0, (hipStream_t)stream, verts, n_verts, faces, adjacency_faces, P, ad);
-    hipLaunchKernelGGL(k_adj_start, dim3((n_verts + 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_verts, P, ad);
+    corners::build(AdjacencyKey{verts, n_verts, faces, adjacency_faces}, n_verts, n_faces, ad, stream);
     return launch_end();
 }
 

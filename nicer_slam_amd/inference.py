@@ -181,20 +181,28 @@ def vertex_colours(model, verts, normals, chunk=1 << 20):
 
 
 @torch.no_grad()
-def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22, simplify=None):
+def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22, simplify=None,
+                 smooth=None):
     """get_surface_trace on the device (plots.py:87-155): ``sdf_grid`` -> ``marching_cubes`` with the grid's spacing and origin
     -> (``color``) ``vertex_colours``.  Returns the marching_cubes dict, plus ``colors`` [V,3] in [0,1] when ``color`` is set.
     A level outside the volume's range gives empty tensors (the reference prints "NO MESH" and writes nothing).
     ``simplify``: a dict of ``mesh_simplify.simplify`` keywords (``cell=`` or ``target_faces=``, ...), applied after the colouring;
-    None leaves the mesh as marching cubes made it."""
+    None leaves the mesh as marching cubes made it.
+    ``smooth``: a dict of ``mesh_smooth.smooth`` keywords (``method=``, ``iterations=``, ...), applied after the colouring -- the
+    colours are queried on the true level set -- and before ``simplify``; None leaves the vertices where marching cubes put them."""
     if simplify is not None and not isinstance(simplify, dict):
         raise ValueError("extract_mesh: simplify must be None or a dict of mesh_simplify.simplify keywords")
+    if smooth is not None and not isinstance(smooth, dict):
+        raise ValueError("extract_mesh: smooth must be None or a dict of mesh_smooth.smooth keywords")
     vol = sdf_grid(model, resolution, grid_boundary, stage, chunk)
     ax = torch.linspace(grid_boundary[0], grid_boundary[1], resolution, dtype=torch.float64)     # get_grid_uniform's axis
     step = float(ax[1] - ax[0]) if resolution > 1 else 1.0
     mesh = marching_cubes(vol, level, (step,) * 3, (float(ax[0]),) * 3)
     if color:
         mesh["colors"] = vertex_colours(model, mesh["verts"], mesh["normals"], min(chunk, 1 << 20))
+    if smooth is not None:
+        from .mesh_smooth import smooth as smooth_mesh
+        mesh = smooth_mesh(mesh, **smooth)
     if simplify is not None:
         from .mesh_simplify import simplify as simplify_mesh
         mesh = simplify_mesh(mesh, **simplify)

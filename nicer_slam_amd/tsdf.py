@@ -201,13 +201,20 @@ class TSDFVolume:
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, min_weight=1):
+    def extract_mesh(self, min_weight=1, smooth=None):
         """The zero level of the observed volume: the ``inference.marching_cubes`` dict (verts, normals, faces), plus ``colors`` when
-        the volume has colour -- what ``inference.write_ply`` and ``mesh_eval.mesh_metrics`` take."""
+        the volume has colour -- what ``inference.write_ply`` and ``mesh_eval.mesh_metrics`` take.  ``smooth``: a dict of
+        ``mesh_smooth.smooth`` keywords, applied after the colours are sampled on the true level set (the depth noise of the
+        frames is on that surface); None leaves the mesh as marching cubes made it."""
+        if smooth is not None and not isinstance(smooth, dict):
+            raise ValueError("extract_mesh: smooth must be None or a dict of mesh_smooth.smooth keywords")
         from .inference import marching_cubes
         mesh = marching_cubes(self.surface_volume(min_weight), 0.0, (self.voxel_length,) * 3, self.centre0)
         if self.colour is not None:
             mesh["colors"] = self.sample_colour(mesh["verts"])
+        if smooth is not None:
+            from .mesh_smooth import smooth as smooth_mesh
+            mesh = smooth_mesh(mesh, **smooth)
         return mesh
 
 
