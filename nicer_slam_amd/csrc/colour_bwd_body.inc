@@ -206,11 +206,23 @@
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) { gx[d] = xhalf_sum(gx[d]); gd[d] = xhalf_sum(gd[d]); gg[d] = xhalf_sum(gg[d]); }
+#ifdef NSA_BODY_HANDOFF
+    // two-phase kernel: the next phase takes the feature cotangent, the updated normal cotangent and d/dx from these registers.
+    // Every lane forms the sum its pair's first lane stores (a clamped lane the one of the point it repeats): same operands, same bits.
+#pragma unroll
+    for (int j = 0; j < HS; ++j) ho_fb[j] = ib[j];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { ho_gx[d] = gx[d]; ho_n[d] = a.g_grad[(size_t)q * 3 + d] + gg[d]; }
+#endif
     if (live && h == 0) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             a.g_x[(size_t)q * 3 + d] = gx[d];
             a.g_dir[(size_t)q * 3 + d] = gd[d];
+#ifdef NSA_BODY_HANDOFF
+            a.g_grad[(size_t)q * 3 + d] = ho_n[d];
+#else
             a.g_grad[(size_t)q * 3 + d] += gg[d];
+#endif
         }
     }

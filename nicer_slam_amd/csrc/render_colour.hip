@@ -267,8 +267,9 @@ __global__ __launch_bounds__(256, 2) void k_colour_bwd(ColourArgs a, GridGeom16 
 // ---- colour backward + coarse SDF backward as two phases of ONE 32-point launch (tracking: no parameter gradients) ------------------
 // The two kernels tile the same points the same way (workgroup = 4 waves x 32 points), the coarse backward consumes what the colour
 // backward has just written (feature and normal cotangents, d/dx to accumulate onto) and both run only two rounds of waves at the
-// tracking batch: as one launch the input burst of a round is paid once, the coarse phase re-reads its cotangents from L2 and one
-// launch disappears.  The bodies are the two kernels' own statements (colour_bwd_body.inc, sdfnet_bwd_body.inc): identical results.
+// tracking batch: as one launch the input burst of a round is paid once, the coarse phase takes its cotangents from the colour
+// phase's registers and one launch disappears.  The bodies are the two kernels' own statements (colour_bwd_body.inc,
+// sdfnet_bwd_body.inc): identical results.
 #define NSA_SDFNET_AS_HEADER
 #include "render_sdfnet.hip"
 #undef NSA_SDFNET_AS_HEADER
@@ -282,6 +283,11 @@ namespace nsa {
 __global__ __launch_bounds__(64 * NSA_CC_NW, 2) void k_colour_coarse_bwd(ColourArgs ca, GridGeom16 cgeom, SdfNetArgs sa, GridGeom16 sgeom) {
     __shared__ __attribute__((aligned(16))) float stage[2 * kStageFloats];
     static_assert(kStageFloats >= kColStage, "the colour phase stages its parts in the SDF kernel's buffers");
+    // what phase 1 hands to phase 2 in registers (NSA_BODY_HANDOFF in the two bodies): the feature cotangent, the updated normal
+    // cotangent and the d/dx to accumulate onto, of the point both phases give to this lane.  The global stores stay (the fine
+    // backward and k_track_finish read them); phase 2 no longer reads them back behind the store drain.
+    float ho_fb[HS], ho_n[3], ho_gx[3];
+#define NSA_BODY_HANDOFF
     {   // phase 1: k_colour_bwd<false>
         constexpr bool MAP = false;
         using Seq = ColBwdOps<false>;
@@ -289,8 +295,7 @@ __global__ __launch_bounds__(64 * NSA_CC_NW, 2) void k_colour_coarse_bwd(ColourA
         const GridGeom16& geom = cgeom;
 #include "colour_bwd_body.inc"
     }
-    __syncthreads();     // every wave is done with the colour phase's last staged part before the buffers are refilled; the feature /
-                         // normal cotangents and d/dx this workgroup wrote are complete (vmcnt(0) + barrier)
+    __syncthreads();     // every wave is done with the colour phase's last staged part before the buffers are refilled
     {   // phase 2: k_sdfnet_bwd<4, 8, 1, false> on the same tiles
         constexpr int L = 4, C = 8, NH = 1;
         constexpr bool MAP = false;
@@ -300,6 +305,7 @@ __global__ __launch_bounds__(64 * NSA_CC_NW, 2) void k_colour_coarse_bwd(ColourA
         const GridGeom16& geom = sgeom;
 #include "sdfnet_bwd_body.inc"
     }
+#undef NSA_BODY_HANDOFF
 }
 #undef NSA_BODY_NW
 

@@ -245,11 +245,9 @@ __device__ __forceinline__ void slots_to_x(const float (&x)[3], float divide_fac
 // This is the reverse of the grad-sdf assembly w.r.t. the reverse-pass vector; the grid Hessian term is NOT part of
 // it (hashgrid.py:134).  Also returns the positional-encoding second-derivative term
 //   xbar_d += n_d * sum_k -(4^k) (sin * dl_sin + cos * dl_cos)      (dl = reverse-pass vector of this point).
-template <int L, int C>
-__device__ __forceinline__ void x_to_slots_tangent(const float (&x)[3], float divide_factor, const float* __restrict__ table,
-                                                   const GridGeom16& geom, int h, const float (&in)[SDF_IN_STEPS],
-                                                   const float (&n)[3], const float (&dl)[3 * 16],
-                                                   float (&tin)[SDF_IN_STEPS], float (&xbar)[3]) {
+// The two parts of it: the positional-encoding slots 0..19 with the second-derivative term (needs the reverse-pass vector dl) ...
+__device__ __forceinline__ void pe_tangent(int h, const float (&in)[SDF_IN_STEPS], const float (&n)[3], const float (&dl)[3 * 16],
+                                           float (&tin)[SDF_IN_STEPS], float (&xbar)[3]) {
     tin[0] = h ? n[2] : n[0];
     tin[1] = h ? 0.0f : n[1];
     xbar[0] = xbar[1] = xbar[2] = 0.0f;
@@ -265,6 +263,48 @@ __device__ __forceinline__ void x_to_slots_tangent(const float (&x)[3], float di
         xbar[g0 % 3] += h ? 0.0f : t;
         xbar[g1 % 3] += h ? t : 0.0f;
     }
+}
+
+// ... and the grid slots of one level from its corner rows: tin[c] = sum_corners k_corner row_corner[c],
+// k_corner = sum_d n_d d w_corner / d x_d.  Needs only the rows, the blend weights and n -- nothing the network computes.
+template <int C>
+__device__ __forceinline__ void grid_level_tangent(const float (&v)[8][C], const float (&w)[3], const float (&dw)[3], float scale,
+                                                   bool inside, const float (&n)[3], float chain, float* tin_level) {
+    float k[8];
+#pragma unroll
+    for (int corner = 0; corner < 8; ++corner) k[corner] = 0.0f;
+#pragma unroll
+    for (int gd = 0; gd < 3; ++gd) {
+#pragma unroll
+        for (int face = 0; face < 4; ++face) {
+            float wt = scale;
+            int lo = 0;
+#pragma unroll
+            for (int nd = 0; nd < 2; ++nd) {
+                const int d = (nd >= gd) ? nd + 1 : nd;
+                if ((face >> nd) & 1) { wt *= w[d]; lo |= 1 << d; }
+                else                  { wt *= 1.0f - w[d]; }
+            }
+            const float t = wt * dw[gd] * n[gd] * chain;
+            k[lo | (1 << gd)] += t;
+            k[lo] -= t;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner) acc = fmaf(k[corner], v[corner][c], acc);
+        tin_level[c] = inside ? acc : 0.0f;
+    }
+}
+
+template <int L, int C>
+__device__ __forceinline__ void x_to_slots_tangent(const float (&x)[3], float divide_factor, const float* __restrict__ table,
+                                                   const GridGeom16& geom, int h, const float (&in)[SDF_IN_STEPS],
+                                                   const float (&n)[3], const float (&dl)[3 * 16],
+                                                   float (&tin)[SDF_IN_STEPS], float (&xbar)[3]) {
+    pe_tangent(h, in, n, dl, tin, xbar);
     float u[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) u[d] = to_unit(x[d], divide_factor);
@@ -277,34 +317,48 @@ __device__ __forceinline__ void x_to_slots_tangent(const float (&x)[3], float di
         const bool inside = locate<3>(u, lg.scale, cell, w, dw);
         float v[8][C];
         gather_corners<3, C>(table, lg, cell, v);
-        float k[8];
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) k[corner] = 0.0f;
-#pragma unroll
-        for (int gd = 0; gd < 3; ++gd) {
-#pragma unroll
-            for (int face = 0; face < 4; ++face) {
-                float wt = lg.scale;
-                int lo = 0;
-#pragma unroll
-                for (int nd = 0; nd < 2; ++nd) {
-                    const int d = (nd >= gd) ? nd + 1 : nd;
-                    if ((face >> nd) & 1) { wt *= w[d]; lo |= 1 << d; }
-                    else                  { wt *= 1.0f - w[d]; }
-                }
-                const float t = wt * dw[gd] * n[gd] * chain;
-                k[lo | (1 << gd)] += t;
-                k[lo] -= t;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int corner = 0; corner < 8; ++corner) acc = fmaf(k[corner], v[corner][c], acc);
-            tin[20 + jl * C + c] = inside ? acc : 0.0f;
-        }
+        grid_level_tangent<C>(v, w, dw, lg.scale, inside, n, chain, &tin[20 + jl * C]);
     }
+}
+
+// First-layer inputs AND the grid slots of their tangent along n from ONE corner gather (the backward without the LDS Jacobian:
+// grid_slots followed by the grid part of x_to_slots_tangent, the same statements on the same rows).  The tangent slots are not
+// needed before the reverse pass is through: they wait in a lane-private LDS column, tcol[jl * level_stride + c * 64]
+// (grid_tangent_slots reads them back), not in registers that two GEMMs would have to carry.
+template <int L, int C>
+__device__ __forceinline__ void sdf_net_inputs_tangent(const float (&x)[3], float divide_factor, const float* __restrict__ table,
+                                                       const GridGeom16& geom, int h, const float (&n)[3],
+                                                       float (&in)[SDF_IN_STEPS], float* tcol, int level_stride) {
+    pe_slots(x, h, in);
+    float u[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) u[d] = to_unit(x[d], divide_factor);
+    const float chain = 1.0f / (2.0f * divide_factor);
+#pragma unroll
+    for (int jl = 0; jl < L / 2; ++jl) {
+        const LevelGeom g = geom.lv[2 * jl + h];
+        uint32_t cell[3];
+        float w[3], dw[3];
+        const bool inside = locate<3>(u, g.scale, cell, w, dw);
+        float v[8][C];
+        gather_corners<3, C>(table, g, cell, v);
+        float f[C];
+        blend<3, C>(v, w, f);
+#pragma unroll
+        for (int c = 0; c < C; ++c) in[20 + jl * C + c] = inside ? f[c] : 0.0f;
+        float t[C];
+        grid_level_tangent<C>(v, w, dw, g.scale, inside, n, chain, t);
+#pragma unroll
+        for (int c = 0; c < C; ++c) tcol[jl * level_stride + c * 64] = t[c];
+    }
+}
+
+template <int L, int C>
+__device__ __forceinline__ void grid_tangent_slots(const float* tcol, int level_stride, float (&tin)[SDF_IN_STEPS]) {
+#pragma unroll
+    for (int jl = 0; jl < L / 2; ++jl)
+#pragma unroll
+        for (int c = 0; c < C; ++c) tin[20 + jl * C + c] = tcol[jl * level_stride + c * 64];
 }
 
 // The same two contractions as slots_to_x / x_to_slots_tangent with the grid part read from the Jacobian kept by
@@ -339,21 +393,7 @@ template <int L, int C>
 __device__ __forceinline__ void tangent_from_jac(float divide_factor, const float* jstore, int h, const float (&in)[SDF_IN_STEPS],
                                                  const float (&n)[3], const float (&dl)[3 * 16], float (&tin)[SDF_IN_STEPS],
                                                  float (&xbar)[3]) {
-    tin[0] = h ? n[2] : n[0];
-    tin[1] = h ? 0.0f : n[1];
-    xbar[0] = xbar[1] = xbar[2] = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        const int g0 = 2 * j, g1 = 2 * j + 1;
-        const float sc = h ? (float)(1 << (g1 / 3)) : (float)(1 << (g0 / 3));
-        const float nd = h ? n[g1 % 3] : n[g0 % 3];
-        const float s = in[2 + 2 * j], c = in[3 + 2 * j];
-        tin[2 + 2 * j] = sc * c * nd;
-        tin[3 + 2 * j] = -sc * s * nd;
-        const float t = -sc * sc * (s * dl[2 + 2 * j] + c * dl[3 + 2 * j]) * nd;
-        xbar[g0 % 3] += h ? 0.0f : t;
-        xbar[g1 % 3] += h ? t : 0.0f;
-    }
+    pe_tangent(h, in, n, dl, tin, xbar);
     const float chain = 1.0f / (2.0f * divide_factor);
 #pragma unroll
     for (int jl = 0; jl < L / 2; ++jl)

@@ -1,6 +1,17 @@
 // sdfnet_bwd_body.inc -- the body of k_sdfnet_bwd<L, C, NH, MAP> (render_sdfnet.hip), textually included by that kernel and by the
 // two-phase kernel k_colour_coarse_bwd (render_colour.hip).  Expects in scope: SdfNetArgs a, GridGeom16 geom, float* stage
 // (2 x kStageFloats floats), constexpr L, C, NH, MAP, `using P = SdfPack<NH>`, `using Seq = SdfOps<NH, true>`.
+// NSA_BODY_HANDOFF (set by k_colour_coarse_bwd): the cotangents are in scope as ho_n / ho_fb / ho_gx -- what the colour phase has just
+// stored to a.g_grad / a.g_feat / a.g_x for this lane's point (all three given and accumulate == 1 there) -- and are not read back.
+#ifdef NSA_BODY_HANDOFF
+#define NSA_COT_N(d_) ho_n[d_]
+#define NSA_COT_F(q_) ho_fb[q_]
+#define NSA_COT_X(d_) ho_gx[d_]
+#else
+#define NSA_COT_N(d_) (a.g_grad ? a.g_grad[(size_t)q * 3 + (d_)] : 0.0f)
+#define NSA_COT_F(q_) (a.g_feat ? a.g_feat[(size_t)tile * 32 * 64 + lane + (q_) * 64] : 0.0f)
+#define NSA_COT_X(d_) a.g_x[(size_t)q * 3 + (d_)]
+#endif
     stage_begin<Seq>(stage, a.wp);
     const int lane = threadIdx.x & 63;
     const int h = lane >> 5;
@@ -20,8 +31,24 @@
     constexpr bool kJacLds = (NH > 1) || MAP;
     __shared__ float jac_lds[kJacLds ? 4 * (L / 2) * 3 * C * 64 : 1];
     float* jstore = kJacLds ? jac_lds + (threadIdx.x >> 6) * ((L / 2) * 3 * C * 64) + lane : nullptr;
+    // Without the LDS Jacobian (two workgroups per CU) the grid slots of the tangent input come from the rows gathered for the
+    // recompute: they need the rows, the blend weights and nbar, nothing the network produces -- one corner gather and one locate
+    // per level fewer.  They wait for the tangent sweep in the part of the stage buffers that the staged fragments leave free
+    // (kLdsPieces of 3 fragments are staged): level jl of this lane's two in the tail of buffer jl, 64 * C floats per wave.
+    constexpr int kStageUsed = kStageFloats / 3 * kLdsPieces;
+    constexpr bool kTanHead = !kJacLds && L / 2 <= 2 && kStageFloats - kStageUsed >= NSA_BODY_NW * 64 * C;
+    float* tcol = stage + kStageUsed + (threadIdx.x >> 6) * (64 * C) + lane;
+    // the cotangents of the outputs: there they are requested with the point, ahead of the gather that nbar then joins; the other
+    // kernels are at their register cap and load them after the reverse pass
+    float nbar[3], sbar = 0.0f;
+    if (kTanHead) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) nbar[d] = NSA_COT_N(d);
+        sbar = a.g_sdf ? a.g_sdf[q] : 0.0f;
+    }
     float in[SDF_IN_STEPS];
-    sdf_net_inputs<L, C>(x, a.divide_factor, a.table, geom, h, in, jstore);
+    if (kTanHead) sdf_net_inputs_tangent<L, C>(x, a.divide_factor, a.table, geom, h, nbar, in, tcol, kStageFloats);
+    else          sdf_net_inputs<L, C>(x, a.divide_factor, a.table, geom, h, in, jstore);
     using E = SE<NH>;
     const bool emit = MAP && a.emit != nullptr && wave_live;   // (a clamped wave must not touch the last tile's rows)
     const Emitter em{emit ? a.emit + (size_t)tile * 32 + (lane & 31) : nullptr, a.emit_ld, live};
@@ -34,10 +61,11 @@
         for (int s = 0; s < SDF_IN_STEPS; ++s) em.slot(E::H0, s, h, in[s]);
     }
 
-    float nbar[3];
+    if (!kTanHead) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) nbar[d] = a.g_grad ? a.g_grad[(size_t)q * 3 + d] : 0.0f;
-    const float sbar = a.g_sdf ? a.g_sdf[q] : 0.0f;
+        for (int d = 0; d < 3; ++d) nbar[d] = NSA_COT_N(d);
+        sbar = a.g_sdf ? a.g_sdf[q] : 0.0f;
+    }
 
     // ---- tangent sweep: e_k = sp''(a_k) dh_k ta_k (kept in e[k-1]) ----
     float e[NH][HS];
@@ -46,7 +74,10 @@
     {
         float tin[SDF_IN_STEPS];
         if (kJacLds) tangent_from_jac<L, C>(a.divide_factor, jstore, h, in, nbar, dl, tin, xb2);
-        else         x_to_slots_tangent<L, C>(x, a.divide_factor, a.table, geom, h, in, nbar, dl, tin, xb2);
+        else if (kTanHead) {
+            pe_tangent(h, in, nbar, dl, tin, xb2);
+            grid_tangent_slots<L, C>(tcol, kStageFloats, tin);
+        } else x_to_slots_tangent<L, C>(x, a.divide_factor, a.table, geom, h, in, nbar, dl, tin, xb2);
         if (emit) {
 #pragma unroll
             for (int s = 0; s < SDF_IN_STEPS; ++s) em.slot(E::TIN, s, h, tin[s]);
@@ -90,9 +121,8 @@
     float ab_bound;             // >= this lane's largest |ab| (the next GEMM takes its scale from it)
     {
         float fb[HS];
-        const float* fsrc = a.g_feat ? a.g_feat + (size_t)tile * 32 * 64 + lane : nullptr;
 #pragma unroll
-        for (int q = 0; q < HS; ++q) fb[q] = fsrc ? fsrc[q * 64] : 0.0f;
+        for (int j = 0; j < HS; ++j) fb[j] = NSA_COT_F(j);
         if (emit) {
 #pragma unroll
             for (int q = 0; q < HS; ++q) em.hid(E::FB, q, h, fb[q]);
@@ -159,7 +189,10 @@
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float v = gx[d];
-            if (a.accumulate) v += a.g_x[(size_t)q * 3 + d];
+            if (a.accumulate) v += NSA_COT_X(d);
             a.g_x[(size_t)q * 3 + d] = v;
         }
     }
+#undef NSA_COT_N
+#undef NSA_COT_F
+#undef NSA_COT_X
