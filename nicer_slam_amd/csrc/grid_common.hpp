@@ -2,8 +2,17 @@
 // that touches a multi-resolution grid.  Algorithm per reference code/hashencoder/src/hashencoder.cu
 // (index rule :35-73, geometry :179-181, cell split :188-195); the host derives everything that is
 // point-independent once per call and hands it to the kernels as kernel arguments (SGPR loads).
+//
+// The first part of this header -- level classification and the pure index arithmetic (level_row, generic_corner_terms /
+// generic_corner_row, corner_offsets) -- also compiles with a plain host compiler: tests/grid_index_host_check.cpp sweeps the very
+// functions the kernels call.  Everything that needs the HIP runtime sits under `#if defined(__HIPCC__)` below.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define NSA_INDEX_FN __host__ __device__ __forceinline__
+#else
+#define NSA_INDEX_FN inline
+#endif
 #include <stdint.h>
 #include <math.h>
 
@@ -96,6 +105,118 @@ inline bool has_generic_level(const LevelGeom* lv, uint32_t L) {
     return false;
 }
 
+// ---- pure index arithmetic (host and device) ---------------------------------------------------
+// 24-bit multiply of the fast-dense corner addressing (v_mul_u32_u24 on the device)
+NSA_INDEX_FN uint32_t umul24(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul24(a, b);
+#else
+    return (a & 0xFFFFFFu) * (b & 0xFFFFFFu);
+#endif
+}
+
+template <int D>
+NSA_INDEX_FN uint32_t level_row(const LevelGeom& g, const uint32_t (&q)[D]) {
+    uint32_t idx;
+    if (g.flags & LV_HASHED) {                        // wave-uniform branch (level is per block)
+        idx = q[0];                                   // prime[0] == 1
+        if (D > 1) idx ^= q[1] * 2654435761u;
+        if (D > 2) idx ^= q[2] * 805459861u;
+    } else {
+        idx = q[0];
+        if (D > 1) idx += q[1] * g.s1;
+        if (D > 2) idx += q[2] * g.s2;
+    }
+    if (g.flags & LV_POW2) return idx & (g.rows - 1u);
+    if (g.flags & LV_SUBONCE) return idx >= g.rows ? idx - g.rows : idx;
+    return idx % g.rows;
+}
+
+// The index part of gather_corners_generic (below): per dimension the two candidate terms (cell, cell + 1), (q * prime) for hashed
+// levels, (q * stride) for dense ones ...
+template <int D>
+NSA_INDEX_FN void generic_corner_terms(const LevelGeom& g, const uint32_t (&cell)[D], uint32_t (&term)[D][2]) {
+    const bool hashed = (g.flags & LV_HASHED) != 0;
+    term[0][0] = cell[0];
+    term[0][1] = cell[0] + 1u;
+    if (D > 1) {
+        const uint32_t m1 = hashed ? 2654435761u : g.s1;
+        term[1][0] = cell[1] * m1;
+        term[1][1] = term[1][0] + m1;
+    }
+    if (D > 2) {
+        const uint32_t m2 = hashed ? 805459861u : g.s2;
+        term[2][0] = cell[2] * m2;
+        term[2][1] = term[2][0] + m2;
+    }
+}
+
+// ... and the row of one corner from them: xor resp. add, `& mask`, ONE conditional subtract.  That is the level's modulo for
+// every cell with cell[d] + 1 <= res (every in-range point, u <= 1) on a level that is not LV_GENERIC, and for ANY cell on a level
+// whose row count is a power of two.  On a dense non-power-of-two level (LV_SUBONCE) a cell beyond the resolution -- the garbage
+// cell of a point far outside the cube -- gives an index of 2 * rows or more, and the row returned here is past the level.
+template <int D, bool GENERIC>
+NSA_INDEX_FN uint32_t generic_corner_row(const LevelGeom& g, const uint32_t (&term)[D][2], int corner) {
+    const bool hashed = (g.flags & LV_HASHED) != 0;
+    uint32_t x = term[0][corner & 1], a = x;
+#pragma unroll
+    for (int d = 1; d < D; ++d) {
+        const uint32_t t = term[d][(corner >> d) & 1];
+        x ^= t;
+        a += t;
+    }
+    uint32_t idx = (hashed ? x : a) & g.mask;
+    idx = idx >= g.rows ? idx - g.rows : idx;
+    if (GENERIC) {
+        if ((g.flags & LV_GENERIC) != 0) idx = (hashed ? x : a) % g.rows;
+    }
+    return idx;
+}
+
+// Fast form of the fused kernels (D = 3, levels classified by make_grid_geom): the BYTE offsets of the eight corner rows from
+// the table base, then eight loads with the table pointer in SGPRs and the 32-bit offset in a VGPR (global_load ... saddr) --
+// no 64-bit address arithmetic per corner.  A lane takes the path of ITS level (the lanes of a wave may hold different levels; a
+// path no lane needs is skipped; only offsets are formed inside the branches, so the loads stay one vector instruction per row):
+//   LV_FASTDENSE  offset of corner (0,0,0) by a shift-add and two 24-bit multiply-adds with the level's byte strides, the
+//                 other corners by seven adds.  The only modulo a dense level ever needs is at its upper boundary (cell + 1 ==
+//                 resolution, i.e. a coordinate of exactly 1.0): such a lane takes the generic path;
+//   LV_FASTHASH   power-of-two hashed level: the four (y, z) prime-term combinations once, then xor / and / shift-add per corner;
+//   otherwise     the generic index arithmetic.
+template <int C>
+NSA_INDEX_FN void corner_offsets(const LevelGeom& g, const uint32_t (&cell)[3], uint32_t (&off)[8]) {
+    constexpr uint32_t B = C * 4;
+    // every corner row inside the level <=> the last one is; all byte offsets then stay below 2^31 (no wrap-around), and a
+    // garbage cell of an out-of-range point -- whose result is discarded -- cannot address outside the table either
+    uint32_t o00 = umul24(cell[1], g.s1B) + (cell[0] * B + g.row0B);
+    o00 = umul24(cell[2], g.s2B) + o00;
+    if ((g.flags & LV_FASTDENSE) && o00 < g.limB) {
+        const uint32_t o10 = o00 + g.s1B, o01 = o00 + g.s2B, o11 = o01 + g.s1B;
+        off[0] = o00; off[1] = o00 + B; off[2] = o10; off[3] = o10 + B;
+        off[4] = o01; off[5] = o01 + B; off[6] = o11; off[7] = o11 + B;
+    } else if (g.flags & LV_FASTHASH) {
+        const uint32_t y0 = cell[1] * 2654435761u, y1 = y0 + 2654435761u;
+        const uint32_t z0 = cell[2] * 805459861u, z1 = z0 + 805459861u;
+        const uint32_t yz[4] = {y0 ^ z0, y1 ^ z0, y0 ^ z1, y1 ^ z1};
+        const uint32_t x0 = cell[0], x1 = cell[0] + 1u;
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner)
+            off[corner] = ((((corner & 1) ? x1 : x0) ^ yz[corner >> 1]) & g.mask) * B + g.row0B;
+    } else {
+        const bool hashed = (g.flags & LV_HASHED) != 0;
+        const uint32_t m1 = hashed ? 2654435761u : g.s1, m2 = hashed ? 805459861u : g.s2;
+        const uint32_t t0[2] = {cell[0], cell[0] + 1u}, t1[2] = {cell[1] * m1, cell[1] * m1 + m1}, t2[2] = {cell[2] * m2, cell[2] * m2 + m2};
+#pragma unroll
+        for (int corner = 0; corner < 8; ++corner) {
+            const uint32_t a0 = t0[corner & 1], a1 = t1[(corner >> 1) & 1], a2 = t2[corner >> 2];
+            uint32_t idx = (hashed ? (a0 ^ a1 ^ a2) : (a0 + a1 + a2)) & g.mask;
+            idx = idx >= g.rows ? idx - g.rows : idx;
+            idx = idx < g.rows ? idx : g.rows - 1u;        // (garbage cell of a far out-of-range point: stay inside the level)
+            off[corner] = idx * B + g.row0B;
+        }
+    }
+}
+
+#if defined(__HIPCC__)
 // hipGetLastError() also reports stale non-errors left by OTHER runtime calls on this host thread (e.g. PyTorch's
 // hipEventQuery -> hipErrorNotReady), so every entry point clears it before launching and reads it after.
 inline void launch_begin() { (void)hipGetLastError(); }
@@ -115,23 +236,6 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
 // the IEEE division sequence when divide_factor == 1 -- every shipped configuration -- was measured: no gain in any kernel, +4 us in
 // the colour forward, whose first gathers then wait behind the branch; profiles/r03_ab_experiments.txt.)
 __device__ __forceinline__ float to_unit(float x, float divide_factor) { return (x / divide_factor + 1.0f) / 2.0f; }
-
-template <int D>
-__device__ __forceinline__ uint32_t level_row(const LevelGeom& g, const uint32_t (&q)[D]) {
-    uint32_t idx;
-    if (g.flags & LV_HASHED) {                        // wave-uniform branch (level is per block)
-        idx = q[0];                                   // prime[0] == 1
-        if (D > 1) idx ^= q[1] * 2654435761u;
-        if (D > 2) idx ^= q[2] * 805459861u;
-    } else {
-        idx = q[0];
-        if (D > 1) idx += q[1] * g.s1;
-        if (D > 2) idx += q[2] * g.s2;
-    }
-    if (g.flags & LV_POW2) return idx & (g.rows - 1u);
-    if (g.flags & LV_SUBONCE) return idx >= g.rows ? idx - g.rows : idx;
-    return idx % g.rows;
-}
 
 // Run-merged, row-coalesced atomic scatter of C-channel rows.
 // Measured on MI355X (tools/micro/atomic_bench.hip): float atomics retire at ~20 G REQUESTS/s chip-wide, independent of
@@ -302,78 +406,12 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float (&v
 template <int D, int C, bool GENERIC = false>
 __device__ __forceinline__ void gather_corners_generic(const float* __restrict__ table, const LevelGeom& g,
                                                        const uint32_t (&cell)[D], float (&v)[1 << D][C]) {
-    const bool hashed = (g.flags & LV_HASHED) != 0;
     uint32_t term[D][2];
-    term[0][0] = cell[0];
-    term[0][1] = cell[0] + 1u;
-    if (D > 1) {
-        const uint32_t m1 = hashed ? 2654435761u : g.s1;
-        term[1][0] = cell[1] * m1;
-        term[1][1] = term[1][0] + m1;
-    }
-    if (D > 2) {
-        const uint32_t m2 = hashed ? 805459861u : g.s2;
-        term[2][0] = cell[2] * m2;
-        term[2][1] = term[2][0] + m2;
-    }
+    generic_corner_terms<D>(g, cell, term);
 #pragma unroll
     for (int corner = 0; corner < (1 << D); ++corner) {
-        uint32_t x = term[0][corner & 1], a = x;
-#pragma unroll
-        for (int d = 1; d < D; ++d) {
-            const uint32_t t = term[d][(corner >> d) & 1];
-            x ^= t;
-            a += t;
-        }
-        uint32_t idx = (hashed ? x : a) & g.mask;
-        idx = idx >= g.rows ? idx - g.rows : idx;
-        if (GENERIC) {
-            if ((g.flags & LV_GENERIC) != 0) idx = (hashed ? x : a) % g.rows;
-        }
+        const uint32_t idx = generic_corner_row<D, GENERIC>(g, term, corner);
         load_row<C>(table + (size_t)(g.row0 + idx) * C, v[corner]);
-    }
-}
-
-// Fast form of the fused kernels (D = 3, levels classified by make_grid_geom): the BYTE offsets of the eight corner rows from
-// the table base, then eight loads with the table pointer in SGPRs and the 32-bit offset in a VGPR (global_load ... saddr) --
-// no 64-bit address arithmetic per corner.  A lane takes the path of ITS level (the lanes of a wave may hold different levels; a
-// path no lane needs is skipped; only offsets are formed inside the branches, so the loads stay one vector instruction per row):
-//   LV_FASTDENSE  offset of corner (0,0,0) by a shift-add and two 24-bit multiply-adds with the level's byte strides, the
-//                 other corners by seven adds.  The only modulo a dense level ever needs is at its upper boundary (cell + 1 ==
-//                 resolution, i.e. a coordinate of exactly 1.0): such a lane takes the generic path;
-//   LV_FASTHASH   power-of-two hashed level: the four (y, z) prime-term combinations once, then xor / and / shift-add per corner;
-//   otherwise     the generic index arithmetic.
-template <int C>
-__device__ __forceinline__ void corner_offsets(const LevelGeom& g, const uint32_t (&cell)[3], uint32_t (&off)[8]) {
-    constexpr uint32_t B = C * 4;
-    // every corner row inside the level <=> the last one is; all byte offsets then stay below 2^31 (no wrap-around), and a
-    // garbage cell of an out-of-range point -- whose result is discarded -- cannot address outside the table either
-    uint32_t o00 = __umul24(cell[1], g.s1B) + (cell[0] * B + g.row0B);
-    o00 = __umul24(cell[2], g.s2B) + o00;
-    if ((g.flags & LV_FASTDENSE) && o00 < g.limB) {
-        const uint32_t o10 = o00 + g.s1B, o01 = o00 + g.s2B, o11 = o01 + g.s1B;
-        off[0] = o00; off[1] = o00 + B; off[2] = o10; off[3] = o10 + B;
-        off[4] = o01; off[5] = o01 + B; off[6] = o11; off[7] = o11 + B;
-    } else if (g.flags & LV_FASTHASH) {
-        const uint32_t y0 = cell[1] * 2654435761u, y1 = y0 + 2654435761u;
-        const uint32_t z0 = cell[2] * 805459861u, z1 = z0 + 805459861u;
-        const uint32_t yz[4] = {y0 ^ z0, y1 ^ z0, y0 ^ z1, y1 ^ z1};
-        const uint32_t x0 = cell[0], x1 = cell[0] + 1u;
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner)
-            off[corner] = ((((corner & 1) ? x1 : x0) ^ yz[corner >> 1]) & g.mask) * B + g.row0B;
-    } else {
-        const bool hashed = (g.flags & LV_HASHED) != 0;
-        const uint32_t m1 = hashed ? 2654435761u : g.s1, m2 = hashed ? 805459861u : g.s2;
-        const uint32_t t0[2] = {cell[0], cell[0] + 1u}, t1[2] = {cell[1] * m1, cell[1] * m1 + m1}, t2[2] = {cell[2] * m2, cell[2] * m2 + m2};
-#pragma unroll
-        for (int corner = 0; corner < 8; ++corner) {
-            const uint32_t a0 = t0[corner & 1], a1 = t1[(corner >> 1) & 1], a2 = t2[corner >> 2];
-            uint32_t idx = (hashed ? (a0 ^ a1 ^ a2) : (a0 + a1 + a2)) & g.mask;
-            idx = idx >= g.rows ? idx - g.rows : idx;
-            idx = idx < g.rows ? idx : g.rows - 1u;        // (garbage cell of a far out-of-range point: stay inside the level)
-            off[corner] = idx * B + g.row0B;
-        }
     }
 }
 
@@ -446,5 +484,7 @@ __device__ __forceinline__ void jacobian_row(const float (&v)[1 << D][C], const 
         for (int c = 0; c < C; ++c) j[c] += wt * (v[hi][c] - v[lo][c]) * dw[gd];
     }
 }
+
+#endif  // __HIPCC__
 
 }  // namespace nsa

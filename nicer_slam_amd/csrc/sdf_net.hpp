@@ -104,10 +104,15 @@ __device__ __forceinline__ void sdf_net_inputs(const float (&x)[3], float divide
     grid_slots<L, C>(x, divide_factor, table, geom, h, in, jstore);
 }
 
-// NOTE on out-of-range points: the table gather above still runs for them (addresses stay inside the level because
-// of the modulo), only the result is zeroed -- same values as kernel_grid's early-out (hashencoder.cu:161-177).
-// A point with NaN coordinates is "inside" for the reference's </> tests; cell then comes from (uint)NaN: keep the
-// gather in range by construction of level_row (mask / modulo), values are garbage-in garbage-out on both sides.
+// NOTE on out-of-range points: the table gather above still runs for them and only the result is zeroed -- same values as
+// kernel_grid's early-out (hashencoder.cu:161-177).  What keeps the READ in range (grid_common.hpp; swept on the host by
+// tests/grid_index_host_check.cpp): corner_offsets (the sampler's fast form) never leaves the table for any cell; the generic form
+// (every other fused caller) stays inside the level for any cell on a hashed or power-of-two level (`& mask`), and on a dense level
+// with another row count (LV_SUBONCE: `& mask` is a no-op and ONE conditional subtract follows) only while cell + 1 <= res, i.e. for
+// unit coordinates up to 1 and a little beyond.  A point FAR outside the cube (|x| of several divide_factor: no ray
+// sample, but an explicit point of nsa_sdf_points can be one) forms a read past such a level; the value is discarded, the address
+// is not checked ("The grid kernels against float64": the sweep's numbers and the guard that is not built).
+// A point with NaN coordinates is "inside" for the reference's </> tests; its cell is (uint)NaN = 0: in range.
 
 // SDF value only (sampler pass): acc chain through the hidden layers, then the sdf row as a VALU dot.
 template <int NH>

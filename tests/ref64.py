@@ -8,15 +8,41 @@ which is exactly the term the reference drops (hashgrid.py:134, restated in orac
 positional encoding, weight norm, Softplus(beta = 100), ReLU, sigmoid, the COMBINE and color_stage = "base" -- is plain torch in the
 requested dtype with autograd (create_graph for the double backward through grad sdf).
 
+``grid="exact"`` puts tests/grid_ref64.py's encoder (the grid itself in the requested dtype, with the same dropped term and the discrete
+part taken from the fp32 inputs) in the place of the linearisation and makes the tables differentiable inputs: sdf_table_grad and
+colour_table_grad give the table gradients the mapping kernels accumulate -- the value path plus, for the SDF grids, the table's
+share of the double backward through grad sdf.  The default stays the linearisation.
+
 Inputs are the explicit fp32 tensors the kernels see; ``dtype=torch.float32`` evaluates the same graph in fp32 (tests/test_ref64_cpu.py
 holds that to oracle/render_ref.py)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+import grid_ref64
 from oracle.hashenc import OracleBackend
 
 F64 = torch.float64
+
+
+class ExactGrids:
+    """grid="exact": per grid the table as a differentiable leaf in the working dtype and the discrete plan of the batch"""
+
+    def __init__(self):
+        self.tables, self.plans = {}, {}
+
+    def features(self, key, x, x0, emb, spec, divide_factor, dtype):
+        u32 = ((x0 / divide_factor + 1) / 2).contiguous()          # the fp32 unit coordinate decides range and cell
+        self.plans[key] = plan = grid_ref64.Plan(u32, spec)
+        plan.record = []
+        self.tables[key] = table = emb.detach().to(dtype).requires_grad_(True)
+        return grid_ref64.grid_features((x / divide_factor + 1) / 2, table, spec, plan=plan)
+
+
+def _grid(exact, key, x, x0, emb, spec, divide_factor, dtype):
+    if exact is None:
+        return _linear_grid(x, x0, emb, spec, divide_factor, dtype)
+    return exact.features(key, x, x0, emb, spec, divide_factor, dtype)
 
 
 def _linear_grid(x, x0, emb, spec, divide_factor, dtype):
@@ -46,8 +72,8 @@ def _lin(params, prefix, h, dtype):
     return F.linear(h, v * (g / v.norm(2, dim=1, keepdim=True)), b)
 
 
-def _sdf_net(params, prefix, spec, x, x0, dtype):
-    feat = _linear_grid(x, x0, params[prefix + ".encoding.embeddings"], spec.grid, spec.divide_factor, dtype)
+def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None):
+    feat = _grid(exact, prefix, x, x0, params[prefix + ".encoding.embeddings"], spec.grid, spec.divide_factor, dtype)
     h = torch.cat((_pe(x, spec.multires), feat), dim=-1)
     for l in range(spec.n_linear):
         h = _lin(params, f"{prefix}.lin{l}", h, dtype)
@@ -59,39 +85,64 @@ def _sdf_net(params, prefix, spec, x, x0, dtype):
 NETS = {"coarse": "implicit_network.coarse", "fine": "implicit_network.fine"}
 
 
-def _sdf_graph(params, cfg, x0, nets, dtype):
+def _sdf_graph(params, cfg, x0, nets, dtype, exact=None):
     x = x0.detach().to(dtype).requires_grad_(True)
     sdf, feat, grad = 0, 0, 0
     for which in nets:
-        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype)
+        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype, exact)
         s = out[:, 0]
         (g,) = torch.autograd.grad(s, x, torch.ones_like(s), create_graph=True)
         sdf, feat, grad = sdf + s, feat + out[:, 1:], grad + g
     return x, sdf, feat, grad
 
 
-def sdf_forward(params, cfg, x0, nets=("coarse", "fine"), dtype=F64):
+def _exact(grid):
+    assert grid in ("linear", "exact"), grid
+    return ExactGrids() if grid == "exact" else None
+
+
+def sdf_forward(params, cfg, x0, nets=("coarse", "fine"), dtype=F64, grid="linear"):
     """-> sdf [P], grad sdf [P,3], feature [P,64] of the networks in ``nets`` (summed: the COMBINE for both)."""
-    _x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype)
+    _x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid))
     return sdf.detach(), grad.detach(), feat.detach()
 
 
-def sdf_backward(params, cfg, x0, g_sdf=None, g_feat=None, g_grad=None, nets=("coarse", "fine"), dtype=F64):
-    """d/dx of  g_sdf . sdf + g_feat . feature + g_grad . grad sdf  (any cotangent may be None = absent) -> [P,3]."""
-    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype)
+def _sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype):
     obj = 0
     for g, y in ((g_sdf, sdf), (g_feat, feat), (g_grad, grad)):
         if g is not None:
             obj = obj + (g.to(dtype) * y).sum()
+    return obj
+
+
+def sdf_backward(params, cfg, x0, g_sdf=None, g_feat=None, g_grad=None, nets=("coarse", "fine"), dtype=F64, grid="linear"):
+    """d/dx of  g_sdf . sdf + g_feat . feature + g_grad . grad sdf  (any cotangent may be None = absent) -> [P,3]."""
+    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid))
+    obj = _sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype)
     if not torch.is_tensor(obj):
         return torch.zeros_like(x).detach()
     (gx,) = torch.autograd.grad(obj, x)
     return gx
 
 
-def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype):
+def sdf_table_grad(params, cfg, x0, which, g_sdf=None, g_feat=None, g_grad=None, dtype=F64):
+    """grid="exact": -> (d/dx [P,3], d/d table [rows, C] of the network ``which``, plan).  The table gradient is the value path plus
+    the table's share of the double backward through grad sdf.  plan.record lists what reached the grid, in order: ("first", g) for
+    every first backward (the last one is the value path: g = d objective / d features), ("second", g, q) for the double backward
+    (g = d sdf / d features, q = the cotangent of J^T g in unit coordinates): enough to form every row's contributions."""
+    exact = ExactGrids()
+    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, (which,), dtype, exact)
+    obj = _sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype)
+    table, plan = exact.tables[NETS[which]], exact.plans[NETS[which]]
+    if not torch.is_tensor(obj):
+        return torch.zeros_like(x).detach(), torch.zeros_like(table).detach(), plan
+    gx, gt = torch.autograd.grad(obj, (x, table))
+    return gx, gt, plan
+
+
+def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact=None):
     x, n, d, f = (t.detach().to(dtype).requires_grad_(True) for t in (x0, normals, dirs, feats))
-    gf = _linear_grid(x, x0, params["rendering_network.encoding.embeddings"], cfg.colour_grid, cfg.colour_divide_factor, dtype)
+    gf = _grid(exact, "colour", x, x0, params["rendering_network.encoding.embeddings"], cfg.colour_grid, cfg.colour_divide_factor, dtype)
     if not grid_grad:                     # color_stage == "base": the colour grid feature is detached (base_networks.py:337-339)
         gf = gf.detach()
     h = torch.cat([x, _pe(d, cfg.multires_view), n, f, gf], dim=-1)
@@ -113,3 +164,11 @@ def colour_backward(params, cfg, x0, normals, dirs, feats, g_rgb, grid_grad=1, d
     ins, rgb = _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype)
     gs = torch.autograd.grad((g_rgb.to(dtype) * rgb).sum(), ins)
     return dict(zip(("x", "normals", "dirs", "feat"), gs))
+
+
+def colour_table_grad(params, cfg, x0, normals, dirs, feats, g_rgb, dtype=F64):
+    """grid="exact", grid_grad = 1: -> (dict(x, normals, dirs, feat), d/d colour table [rows, 2], plan) of d(g_rgb . rgb)."""
+    exact = ExactGrids()
+    ins, rgb = _colour_graph(params, cfg, x0, normals, dirs, feats, 1, dtype, exact)
+    gs = torch.autograd.grad((g_rgb.to(dtype) * rgb).sum(), ins + (exact.tables["colour"],))
+    return dict(zip(("x", "normals", "dirs", "feat"), gs[:4])), gs[4], exact.plans["colour"]

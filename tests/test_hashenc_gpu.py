@@ -2,7 +2,9 @@
 and the reference-captured goldens.  Needs an MI355X.
 
 Tolerances (fp32): forward/Jacobian abs 1e-5 + rel 1e-4 of the table magnitude; scattered table
-gradients rel 1e-3 (float atomics reorder the sums; hipcc contracts a*b+c to FMA, the oracle is unfused)."""
+gradients rel 1e-3 (float atomics reorder the sums; hipcc contracts a*b+c to FMA, the oracle is unfused).
+These are tolerances on the scale of a whole tensor; tests/test_grid_float64_gpu.py holds the same kernels to float64 per (point, level)
+and per touched table row."""
 import numpy as np
 import pytest
 import torch
