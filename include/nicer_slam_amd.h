@@ -1562,6 +1562,105 @@ uint64_t nsa_mesh_vertex_normals_workspace(uint32_t n_verts, uint32_t n_faces);
 int nsa_mesh_vertex_normals(const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces, int weighting, void *workspace,
                             float *normals, nsa_stream_t stream);
 
+/* ---- Section 22: mesh decimation (parallel edge collapse with quadric error; DESIGN 4u, csrc/mesh_decimate.hip) ---- */
+
+/* Garland-Heckbert edge collapse in ROUNDS of independent collapses.  The caller drives the rounds: per round nsa_mesh_edges (Section
+ * 18) and nsa_mesh_ring (Section 21) on the CURRENT faces, then nsa_mesh_decimate_round, then one read of totals.  verts[n_verts, 3]
+ * fp32, faces[n_faces, 3] int32 (the caller's working copy, rewritten in place), 6 * n_faces < 2^31, n_verts < 2^31.
+ * tests/decimate_ref.py restates this section in numpy and the device equals it element for element, bit for bit.
+ *
+ * Arithmetic.  Float64 throughout, + - * / only, every operation rounded on its own (nothing contracted), every sum in the stated
+ * order; (u . w) = (u_x w_x + u_y w_y) + u_z w_z; u x w = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x).  No square root
+ * and no transcendental function: a cost that differs in its last bit changes which edge wins.  No atomics anywhere.
+ *
+ * State (nsa_mesh_decimate_state_bytes, device, the caller's, opaque): per vertex x_v = double(verts[v]); the quadric
+ * Q_v = (a00, a01, a02, a11, a12, a22, b0, b1, b2, c, w), eleven float64; the colour double(colors[v]) when colors is given;
+ * vertex_map[v] = v; the bytes locked(v) and moved(v) = 0; and the number of log rows written.
+ *
+ * nsa_mesh_decimate_init, from the edge table and the rings of the input faces:
+ *   plane(n, p, s): d = -(n . p); adds s n_i n_j to a_ij as (s n_i) n_j, (s n_i) d to b_i, (s d) d to c and s (n . n) to w; without
+ *   a scale the products are n_i n_j, n_i d, d d and n . n.
+ *   A face is FINITE when it contributes by Section 18's rule and its nine coordinates are finite; its n = (p1 - p0) x (p2 - p0),
+ *   unnormalised, p_k the vertex at faces[f][k].
+ *   Q_v, starting from zero: first plane(n, p0) of every finite face at v, in ascending corner id 3 f + k (csrc/corner_table.hpp, one
+ *   lane per vertex); then, along the row of v in ascending neighbour u, for every edge {u, v} with edge_count == 1 whose face is
+ *   finite: e = x_hi - x_lo, m = e x n, s = boundary_weight / (e . e), plane(m, x_lo, s), skipped when e . e is not positive or s
+ *   is not finite.  (Garland and Heckbert's boundary constraint; m . m = (e . e)(n . n), so the weight is boundary_weight n . n in
+ *   the units of the face terms.)
+ *   locked(v): a coordinate of v is not finite; fixed[v] != 0; or some entry u of its row is not finite (v is then a vertex of a face
+ *   with a non-finite vertex), lies on an edge with edge_count > 2, or -- boundary == NSA_DECIMATE_BOUNDARY_FIXED -- on an edge with
+ *   edge_count == 1.  A locked vertex never takes part in a collapse; the locks are those of the input and do not change.
+ *
+ * nsa_mesh_decimate_round, for every edge i = (lo, hi) of the current table, the first failing test giving its class:
+ *   LOCK     locked(lo) or locked(hi), or edge_count not 1 or 2.
+ *   Placement.  Q = Q_lo + Q_hi (component by component), m = (x_lo + x_hi) * 0.5, tr = (a00 + a11) + a22, mu = eps * tr.  With
+ *            A' = A + mu I on the diagonal and r = mu * m - b, LDL^T in the pivot order 0, 1, 2:
+ *              d0 = a'00; l10 = a01 / d0; l20 = a02 / d0; d1 = a'11 - l10 a01; t = a12 - l20 a01; l21 = t / d1;
+ *              d2 = (a'22 - l20 a02) - l21 t;  y0 = r0; y1 = r1 - l10 y0; y2 = (r2 - l20 y0) - l21 y1;
+ *              x2 = y2 / d2; x1 = y1 / d1 - l21 x2; x0 = (y0 / d0 - l10 x1) - l20 x2.
+ *            x = m when tr is zero or not finite, a pivot d0, d1, d2 is not positive, or x is not finite.
+ *   Cost.    (A x)_i = (a_i0 x0 + a_i1 x1) + a_i2 x2; cost = ((x . A x) + 2 (b . x)) + c with the un-regularised Q, then max(0, cost).
+ *   ERROR    the cost is not finite, or has_limit and not cost <= max_error2 * w (max_error2 = max_error^2, squared by the caller:
+ *            the n . n weighted mean squared distance to the planes collected so far).
+ *   LINK     common = the size of the intersection of the two ascending rows; virt = 1 when edge_count == 2 and both ends have a row
+ *            entry on an edge with edge_count == 1 (both touch the virtual vertex beyond the boundary), else 0; fails unless
+ *            common + virt == edge_count, and unless |row lo| + |row hi| - common (the union, both ends included) >= 5, or >= 4 for
+ *            edge_count == 1: the merged vertex keeps three neighbours, two along a boundary.
+ *   FOLD     every face around lo or hi that does not hold both, with n before and n' with that end at x: fails unless
+ *            (n . n') > 0 and (n . n')^2 > (min_cos2 * (n . n)) * (n' . n').  A zero n or n' fails.
+ *   CANDIDATE otherwise; its KEY is (the uint64 bits of cost, mix(lo << 32 | hi)).  Non-negative doubles order as their bits.  mix is
+ *            the finaliser of splitmix64 on 64-bit words -- z = w + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31) -- a bijection, so every key is distinct.  (The plain word
+ *            lo << 32 | hi would do for that, but it orders equal costs by the vertex numbering: on a flat region, where every cost
+ *            is exactly 0, a lattice numbered row by row then has two or three local minima and a round takes as many collapses.)
+ * Selection: m1(v) = the smallest key over the candidate edges of row v; m2(v) = the smallest m1 over v and its row; an edge is
+ * SELECTED iff its key equals m2(lo) and m2(hi).  No end of a selected edge lies within one edge of an end of another,
+ * so the round equals its collapses applied one after another in any order, and the globally smallest candidate is always selected.
+ * Prefix: the selected edges in ascending key (four stable radix argsorts, the two halves of the edge word and then of the cost
+ * bits, least significant first); with has_target the edge at sorted position p is TAKEN iff F_c - (the sum of edge_count over the positions
+ * before p) > target_faces, F_c the contributing faces of the table; without, all are taken.  A collapse removes edge_count faces.
+ * Application, per taken edge: with colours t = ((x - x_lo) . e) / (e . e), e = x_hi - x_lo (0 when e . e is not positive), clamped
+ * to [0, 1], colour_lo += t * (colour_hi - colour_lo); x_lo = x; Q_lo = Q; vertex_map[hi] = lo; moved(lo) = 1; the row
+ * (round, lo, hi, cost bits) goes to log[4 * (rows so far + p)] when that row is below log_rows.  Then every corner naming hi names
+ * lo (a collapsed face has a repeated index and stops contributing by Section 18's rule: nothing is compacted), and vertex_map is
+ * composed so that every entry names a vertex that maps to itself.
+ * totals[14] (uint64, device): {round, E, F_c before, candidates, rejected by lock, by error, by link, by fold, selected, taken,
+ *   faces removed, F_c after, log rows so far, status (1: a sort order left its range; 0 unless the implementation is wrong)}.
+ *
+ * nsa_mesh_decimate_finish: out_verts = the input BITS of a vertex that never moved, else x_v rounded to fp32; out_colors likewise;
+ * vertex_map[v] = the surviving vertex v was merged into.
+ *
+ * Kernel shape: one lane per edge slot, vertex or corner; the totals and the prefix rule in one workgroup.  Every index
+ * read from a table is range-checked before use, and every loop runs over a row or run whose ends were checked against the table's
+ * length.  NULL arguments (colors, fixed and -- with log_rows = 0 -- log may be NULL), an unknown boundary, a negative or non-finite
+ * boundary_weight or eps, min_cos2 outside [0, 1), a negative max_error2 with has_limit, n_verts >= 2^31 or 6 * n_faces >= 2^31:
+ * NSA_EBADARG before anything is launched.  n_verts = 0 or n_faces = 0 launches nothing and returns 0.  Nothing is allocated or
+ * synchronised. */
+
+#define NSA_DECIMATE_BOUNDARY_QUADRIC 0  /* boundary edges add their constraint planes */
+#define NSA_DECIMATE_BOUNDARY_FIXED 1    /* and their ends are locked */
+
+/* bytes of the state (256-byte aligned, device); 0 for n_verts = 0 or >= 2^31 */
+uint64_t nsa_mesh_decimate_state_bytes(uint32_t n_verts);
+
+/* bytes of workspace for init and round (256-byte aligned, device); 0 for an invalid count (a zero count, n_verts >= 2^31,
+ * 6 * n_faces >= 2^31) */
+uint64_t nsa_mesh_decimate_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_decimate_init(const float *verts, const float *colors, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                           const int32_t *edge_count, const int32_t *edge_start, const int32_t *edge_halfedges, const int32_t *ring_start,
+                           const int32_t *ring, const int32_t *ring_edge, const uint8_t *fixed, int boundary, double boundary_weight,
+                           void *workspace, void *state, nsa_stream_t stream);
+
+int nsa_mesh_decimate_round(uint32_t n_verts, int32_t *faces, uint32_t n_faces, const int32_t *edges, const int32_t *edge_count,
+                            const int32_t *edge_start, const int32_t *edge_halfedges, const uint64_t *edge_totals,
+                            const int32_t *ring_start, const int32_t *ring, const int32_t *ring_edge, uint32_t round, int has_target,
+                            uint64_t target_faces, int has_limit, double max_error2, double min_cos2, double eps, int has_colors,
+                            void *workspace, void *state, uint64_t *log, uint32_t log_rows, uint64_t *totals, nsa_stream_t stream);
+
+int nsa_mesh_decimate_finish(const float *verts, const float *colors, uint32_t n_verts, const void *state, float *out_verts,
+                             float *out_colors, int32_t *vertex_map, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -440,3 +440,17 @@ EXPORTS += ["nsa_mesh_ring_workspace", "nsa_mesh_ring", "nsa_mesh_smooth_workspa
             "nsa_mesh_vertex_normals_workspace", "nsa_mesh_vertex_normals"]
 SMOOTH_FREE, SMOOTH_FIXED, SMOOTH_CURVE = 0, 1, 2                           # NSA_SMOOTH_* of header Section 21
 NORMALS_AREA, NORMALS_ANGLE = 0, 1                                          # NSA_NORMALS_*
+lib.nsa_mesh_decimate_state_bytes.restype = _u64
+lib.nsa_mesh_decimate_state_bytes.argtypes = [_u32]
+lib.nsa_mesh_decimate_workspace.restype = _u64
+lib.nsa_mesh_decimate_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_decimate_init.restype = _i
+lib.nsa_mesh_decimate_init.argtypes = [_p, _p, _u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _i, _f64, _p, _p, _p]
+lib.nsa_mesh_decimate_round.restype = _i
+lib.nsa_mesh_decimate_round.argtypes = [_u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _u32, _i, _u64, _i, _f64, _f64, _f64, _i, _p, _p,
+                                        _p, _u32, _p, _p]
+lib.nsa_mesh_decimate_finish.restype = _i
+lib.nsa_mesh_decimate_finish.argtypes = [_p, _p, _u32, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_decimate_state_bytes", "nsa_mesh_decimate_workspace", "nsa_mesh_decimate_init", "nsa_mesh_decimate_round",
+            "nsa_mesh_decimate_finish"]
+DECIMATE_BOUNDARY_QUADRIC, DECIMATE_BOUNDARY_FIXED = 0, 1                   # NSA_DECIMATE_BOUNDARY_* of header Section 22

@@ -182,14 +182,18 @@ def vertex_colours(model, verts, normals, chunk=1 << 20):
 
 @torch.no_grad()
 def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22, simplify=None,
-                 smooth=None):
+                 smooth=None, decimate=None):
     """get_surface_trace on the device (plots.py:87-155): ``sdf_grid`` -> ``marching_cubes`` with the grid's spacing and origin
     -> (``color``) ``vertex_colours``.  Returns the marching_cubes dict, plus ``colors`` [V,3] in [0,1] when ``color`` is set.
     A level outside the volume's range gives empty tensors (the reference prints "NO MESH" and writes nothing).
     ``simplify``: a dict of ``mesh_simplify.simplify`` keywords (``cell=`` or ``target_faces=``, ...), applied after the colouring;
     None leaves the mesh as marching cubes made it.
     ``smooth``: a dict of ``mesh_smooth.smooth`` keywords (``method=``, ``iterations=``, ...), applied after the colouring -- the
-    colours are queried on the true level set -- and before ``simplify``; None leaves the vertices where marching cubes put them."""
+    colours are queried on the true level set -- and before ``simplify``; None leaves the vertices where marching cubes put them.
+    ``decimate``: a dict of ``mesh_decimate.decimate`` keywords (``target_faces=`` or ``max_error=``, ...), applied last, after
+    ``simplify``; None collapses nothing."""
+    if decimate is not None and not isinstance(decimate, dict):
+        raise ValueError("extract_mesh: decimate must be None or a dict of mesh_decimate.decimate keywords")
     if simplify is not None and not isinstance(simplify, dict):
         raise ValueError("extract_mesh: simplify must be None or a dict of mesh_simplify.simplify keywords")
     if smooth is not None and not isinstance(smooth, dict):
@@ -206,6 +210,9 @@ def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage=
     if simplify is not None:
         from .mesh_simplify import simplify as simplify_mesh
         mesh = simplify_mesh(mesh, **simplify)
+    if decimate is not None:
+        from .mesh_decimate import decimate as decimate_mesh
+        mesh = decimate_mesh(mesh, **decimate)
     return mesh
 
 

@@ -201,11 +201,14 @@ class TSDFVolume:
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, min_weight=1, smooth=None):
+    def extract_mesh(self, min_weight=1, smooth=None, decimate=None):
         """The zero level of the observed volume: the ``inference.marching_cubes`` dict (verts, normals, faces), plus ``colors`` when
         the volume has colour -- what ``inference.write_ply`` and ``mesh_eval.mesh_metrics`` take.  ``smooth``: a dict of
         ``mesh_smooth.smooth`` keywords, applied after the colours are sampled on the true level set (the depth noise of the
-        frames is on that surface); None leaves the mesh as marching cubes made it."""
+        frames is on that surface); None leaves the mesh as marching cubes made it.  ``decimate``: a dict of
+        ``mesh_decimate.decimate`` keywords, applied last; None collapses nothing."""
+        if decimate is not None and not isinstance(decimate, dict):
+            raise ValueError("extract_mesh: decimate must be None or a dict of mesh_decimate.decimate keywords")
         if smooth is not None and not isinstance(smooth, dict):
             raise ValueError("extract_mesh: smooth must be None or a dict of mesh_smooth.smooth keywords")
         from .inference import marching_cubes
@@ -215,6 +218,9 @@ class TSDFVolume:
         if smooth is not None:
             from .mesh_smooth import smooth as smooth_mesh
             mesh = smooth_mesh(mesh, **smooth)
+        if decimate is not None:
+            from .mesh_decimate import decimate as decimate_mesh
+            mesh = decimate_mesh(mesh, **decimate)
         return mesh
 
 
