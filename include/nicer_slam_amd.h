@@ -1661,6 +1661,94 @@ int nsa_mesh_decimate_round(uint32_t n_verts, int32_t *faces, uint32_t n_faces, 
 int nsa_mesh_decimate_finish(const float *verts, const float *colors, uint32_t n_verts, const void *state, float *out_verts,
                              float *out_colors, int32_t *vertex_map, nsa_stream_t stream);
 
+/* ---- Section 23: hole filling (boundary loops traced, ranked and patched; DESIGN 4v, csrc/mesh_fill.hip) ---- */
+
+/* Closes the holes of a mesh with polar patches, after nsa_mesh_edges (Section 18) on the same face list.  verts[n_verts, 3] fp32,
+ * optional colors fp32 [n_verts, 3], faces[n_faces, 3] int32, n_verts < 2^31, H = 3 * n_faces < 2^31.  names (NULL = faces) is the
+ * face list the edge table was built from when that is not faces itself (welded names, mesh_eval.welded_faces); the topology and the
+ * pinch test read names, the positions and the patch read faces.  n_boundary = B is the number of boundary edges in the edge table's
+ * totals, which the caller has read back.  tests/fill_ref.py restates this section in numpy and the device equals it element for
+ * element, bit for bit.
+ *
+ * Arithmetic.  Float64 throughout on the fp32 inputs, + - * / only, every operation rounded on its own (nothing contracted), every
+ * sum in the stated order starting from zero; (u . w) = (u_x w_x + u_y w_y) + u_z w_z; u x w = (u_y w_z - u_z w_y, u_z w_x - u_x w_z,
+ * u_x w_y - u_y w_x).  No square root and no transcendental function.  No atomics anywhere.
+ *
+ * Items.  A BOUNDARY half-edge h = 3 f + k runs a -> b on an edge with edge_count == 1 (Section 18's half-edges and classes).  The B
+ * boundary half-edges in ascending id are the ITEMS 0 .. B - 1 (one exclusive scan of the flags).
+ *
+ * Successor.  From g = 3 f + (k + 1) % 3, which leaves b: while the edge of g is not a boundary edge -- it must have edge_count == 2
+ * and edge_forward == 1, otherwise the item is BLOCKED -- step to the twin t, the other entry of the edge's run in edge_halfedges,
+ * and set g = 3 (t / 3) + (t % 3 + 1) % 3, which leaves b again.  More than n_faces steps set status bit 1 and block the item.
+ * next(i) = the item of g; a blocked item is its own successor and a TERMINAL.  Rotation stays inside one fan of faces.
+ *
+ * Pinch.  An item is PINCHED when another item starts at the same vertex (by name): one stable radix argsort of the B start
+ * vertices (Section 4's sort) and a comparison with the two neighbours in that order.
+ *
+ * Loops.  ceil(log2(max(B, 2))) + 1 double-buffered rounds of pointer jumping, each item carrying (smallest item seen, jump pointer,
+ * reached a terminal).  An item that reaches a terminal lies on an OPEN CHAIN and belongs to no loop.  Otherwise its LEADER is the
+ * smallest item of its cycle.  As many rounds of Wyllie's list ranking, the cycle cut in front of its leader, give rank(i), the
+ * steps from the leader, and the loop's length n.  The L loops are numbered in ascending leader; loop_start is the exclusive scan
+ * of n over the leaders; order[loop_start + rank] = h.  (Departure from Section 18, which counts the components of the boundary
+ * graph: the counts agree when no item is pinched or blocked.  Two holes that touch in a vertex are one component there and one
+ * figure-eight loop here, the rotation running from one hole into the other through the fan between them; it holds two pinched
+ * items and is not filled.  A boundary that runs into a non-manifold or inconsistent edge is an open chain.)
+ *
+ * Per loop, one lane walking its segment of order in rank order, p_i the start vertex of its i-th half-edge, i + 1 taken mod n:
+ *   c = (sum p_i) / n;  the mean colour likewise when colors is given (zero otherwise)
+ *   box lo / hi: a running "if p < lo: lo = p" / "if p > hi: hi = p" from p_0;  D2 = |hi - lo|^2
+ *   R2 = (sum |p_i - c|^2) / n;  L2 = (sum |p_{i+1} - p_i|^2) / n
+ *   n_i = (p_{i+1} - c) x (p_i - c);  A = sum n_i
+ * Class, the first that applies: NONFINITE 1 (a coordinate of some p_i is not finite; the row's reals are zero and its ring count
+ * 0), PINCHED 2 (it holds a pinched item), TOO_MANY_EDGES 3 (has_max_edges and n > max_edges), TOO_LARGE 4 (has_max_size and
+ * D2 > max_size2, squared by the caller), FOLDED 5 (skip_folded and some n_i . A <= 0: the loop is not star-shaped about c),
+ * FILLED 0.  Ring count K = rings when rings > 0; else the smallest K >= 1 with (double(K) * double(K)) * L2 >= R2, at most max_rings.
+ * A filled loop gets new_verts = (K - 1) n + 1 and new_faces = n (2 K - 1), every other loop 0 and 0; vert_offset and face_offset
+ * are their exclusive scans over the loops.
+ *   loop_ints[B, 9] int64, the first L rows: leader half-edge, n, loop_start, class, K, new_verts, new_faces, vert_offset, face_offset
+ *   loop_reals[B, 18] float64, the first L rows: c, mean colour, box lo, box hi, D2, R2, L2, A
+ *   halfedges[B], next[B] (items), leader[B] (item, -1 on an open chain), rank[B] int32; flags[B] uint8: 1 blocked | 2 pinched |
+ *   4 open chain | 8 the step cap was hit; order[B] int32, the first B - (open-chain items) valid
+ *   totals[12] (uint64, device): {B, L, filled, nonfinite, pinched, too_many_edges, too_large, folded, open-chain items,
+ *   new vertices, new faces, status (1: a rotation hit its cap; 2: the flags do not add up to n_boundary; 0 unless the input arrays
+ *   are not Section 18's of this face list)}
+ *
+ * nsa_mesh_fill_emit, after one read of totals[9] and totals[10].  Ring 0 of a filled loop is the loop itself, r_0[i] the start
+ * vertex of order[loop_start + i]; ring j, 1 <= j < K, is q_{j,i} = c + t_j * (p_i - c), t_j = double(K - j) / double(K), at index
+ * n_verts + vert_offset + (j - 1) n + i; the centre c at n_verts + vert_offset + (K - 1) n.  Colours by the same formula about the
+ * mean colour.  Positions and colours are rounded to fp32.  Faces run against the boundary half-edges: between rings j and j + 1
+ * (r_j[i+1], r_j[i], r_{j+1}[i]) then (r_j[i+1], r_{j+1}[i], r_{j+1}[i+1]); from the last ring (r_{K-1}[i+1], r_{K-1}[i], centre).
+ * Face order is by loop, then ring, then i.  new_verts[n_new_verts, 3], new_colors and new_faces[n_new_faces, 3] hold the appended
+ * rows alone: the caller keeps the old vertices and faces in front of them, bit for bit.
+ *
+ * Kernel shape: one lane per half-edge, item or loop; one lane per new face in emit, the first face of (ring, i) writing
+ * the vertex there.  Every index read from a table is range-checked before use.  NULL arguments (colors / new_colors together, names),
+ * rings or max_rings > 65535, max_rings = 0, a negative or NaN max_size2 with has_max_size, n_boundary > 3 * n_faces,
+ * n_verts + n_new_verts >= 2^31, n_verts >= 2^31 or 3 * n_faces >= 2^31: NSA_EBADARG before anything is launched.  n_faces = 0 or
+ * n_boundary = 0 (and n_new_faces = 0 in emit) launches nothing, writes nothing and returns 0.  Nothing is allocated or synchronised. */
+
+#define NSA_FILL_FILLED 0
+#define NSA_FILL_NONFINITE 1
+#define NSA_FILL_PINCHED 2
+#define NSA_FILL_TOO_MANY_EDGES 3
+#define NSA_FILL_TOO_LARGE 4
+#define NSA_FILL_FOLDED 5
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (a zero count, 3 * n_faces >= 2^31, n_boundary > 3 * n_faces) */
+uint64_t nsa_mesh_fill_workspace(uint32_t n_faces, uint32_t n_boundary);
+
+int nsa_mesh_fill_loops(const float *verts, const float *colors, uint32_t n_verts, const int32_t *faces, const int32_t *names,
+                        uint32_t n_faces, const int32_t *edge_count, const int32_t *edge_forward, const int32_t *edge_start,
+                        const int32_t *edge_halfedges, const int32_t *face_edges, const uint64_t *edge_totals, uint32_t n_boundary,
+                        int has_max_edges, uint64_t max_edges, int has_max_size, double max_size2, uint32_t rings, uint32_t max_rings,
+                        int skip_folded, void *workspace, int32_t *halfedges, int32_t *next, uint8_t *flags, int32_t *leader,
+                        int32_t *rank, int32_t *order, int64_t *loop_ints, double *loop_reals, uint64_t *totals, nsa_stream_t stream);
+
+int nsa_mesh_fill_emit(const float *verts, const float *colors, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                       const int32_t *order, uint32_t n_boundary, const int64_t *loop_ints, const double *loop_reals,
+                       const uint64_t *totals, uint64_t n_new_verts, uint64_t n_new_faces, float *new_verts, float *new_colors,
+                       int32_t *new_faces, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -454,3 +454,12 @@ lib.nsa_mesh_decimate_finish.argtypes = [_p, _p, _u32, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_decimate_state_bytes", "nsa_mesh_decimate_workspace", "nsa_mesh_decimate_init", "nsa_mesh_decimate_round",
             "nsa_mesh_decimate_finish"]
 DECIMATE_BOUNDARY_QUADRIC, DECIMATE_BOUNDARY_FIXED = 0, 1                   # NSA_DECIMATE_BOUNDARY_* of header Section 22
+lib.nsa_mesh_fill_workspace.restype = _u64
+lib.nsa_mesh_fill_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_fill_loops.restype = _i
+lib.nsa_mesh_fill_loops.argtypes = [_p, _p, _u32, _p, _p, _u32, _p, _p, _p, _p, _p, _p, _u32, _i, _u64, _i, _f64, _u32, _u32, _i, _p, _p, _p, _p,
+                                    _p, _p, _p, _p, _p, _p, _p]
+lib.nsa_mesh_fill_emit.restype = _i
+lib.nsa_mesh_fill_emit.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p, _u64, _u64, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_fill_workspace", "nsa_mesh_fill_loops", "nsa_mesh_fill_emit"]
+FILL_CLASSES = ("filled", "nonfinite", "pinched", "too_many_edges", "too_large", "folded")         # NSA_FILL_* of header Section 23

@@ -182,7 +182,7 @@ def vertex_colours(model, verts, normals, chunk=1 << 20):
 
 @torch.no_grad()
 def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22, simplify=None,
-                 smooth=None, decimate=None):
+                 smooth=None, decimate=None, fill_holes=None):
     """get_surface_trace on the device (plots.py:87-155): ``sdf_grid`` -> ``marching_cubes`` with the grid's spacing and origin
     -> (``color``) ``vertex_colours``.  Returns the marching_cubes dict, plus ``colors`` [V,3] in [0,1] when ``color`` is set.
     A level outside the volume's range gives empty tensors (the reference prints "NO MESH" and writes nothing).
@@ -191,7 +191,11 @@ def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage=
     ``smooth``: a dict of ``mesh_smooth.smooth`` keywords (``method=``, ``iterations=``, ...), applied after the colouring -- the
     colours are queried on the true level set -- and before ``simplify``; None leaves the vertices where marching cubes put them.
     ``decimate``: a dict of ``mesh_decimate.decimate`` keywords (``target_faces=`` or ``max_error=``, ...), applied last, after
-    ``simplify``; None collapses nothing."""
+    ``simplify``; None collapses nothing.
+    ``fill_holes``: a dict of ``mesh_fill.fill_holes`` keywords (``max_edges=``, ``max_size=``, ...), applied after the colouring
+    and before ``smooth``, ``simplify`` and ``decimate`` -- a mesh cut by the grid's box is closed there; None fills nothing."""
+    if fill_holes is not None and not isinstance(fill_holes, dict):
+        raise ValueError("extract_mesh: fill_holes must be None or a dict of mesh_fill.fill_holes keywords")
     if decimate is not None and not isinstance(decimate, dict):
         raise ValueError("extract_mesh: decimate must be None or a dict of mesh_decimate.decimate keywords")
     if simplify is not None and not isinstance(simplify, dict):
@@ -204,6 +208,9 @@ def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage=
     mesh = marching_cubes(vol, level, (step,) * 3, (float(ax[0]),) * 3)
     if color:
         mesh["colors"] = vertex_colours(model, mesh["verts"], mesh["normals"], min(chunk, 1 << 20))
+    if fill_holes is not None:
+        from .mesh_fill import fill_holes as fill_mesh
+        mesh = fill_mesh(mesh, **fill_holes)
     if smooth is not None:
         from .mesh_smooth import smooth as smooth_mesh
         mesh = smooth_mesh(mesh, **smooth)

@@ -1,0 +1,262 @@
+"""Hole filling on the device: boundary loops traced, ranked and patched (C ABI Section 23, csrc/mesh_fill.hip).
+
+* ``fill_holes(mesh, max_edges=None, max_size=None, rings="auto", ...)``: the mesh with every hole that passes the limits closed by a
+  polar patch -- rings of the loop shrunk towards its centroid, then a fan to the centre -- oriented like the faces around it.  Old
+  vertices and faces keep their indices and bits; the new ones are appended.
+* ``boundary_loops(mesh)``: the ordered vertex loops of the boundary, which ``mesh_topology.boundary_edges`` cannot give.
+* ``python -m nicer_slam_amd.mesh_fill IN.ply --out OUT.ply [--max-edges N] [--max-size D] [--rings auto|K] [--fair N]
+  [--keep-folded] [--normals keep|angle|area|none] [--weld] [--list] [--json]``
+
+A loop is a cycle of the successor relation "rotate about the end vertex inside the fan of faces to the next boundary half-edge"; no
+atomics, float64 with every operation rounded on its own, and the result equals the numpy statement in tests/fill_ref.py bit for bit.
+Two holes that touch in a vertex are one figure-eight loop (``pinched``), a boundary that runs into a non-manifold or inconsistent edge
+is an open chain, a loop that is not star-shaped about its centroid is ``folded``: none of them is filled.  Filling is BY INDEX unless
+``weld=True``.
+
+numpy in, numpy out; torch in, torch out on the caller's device.  There is no CPU path: a missing GPU is an error.
+"""
+import argparse
+import json
+import math
+import sys
+
+import numpy as np
+import torch
+
+from . import _native
+from ._native import lib, check
+from .mesh_smooth import WEIGHTING, _mesh, _vertex_normals
+from .mesh_topology import _edge_table, _mesh_arrays, _need_gpu
+
+CLASSES = _native.FILL_CLASSES
+TOTALS = ("n_boundary", "n_loops", "n_filled", "n_nonfinite", "n_pinched", "n_too_many_edges", "n_too_large", "n_folded",
+          "n_open_chain", "n_new_verts", "n_new_faces", "status")
+INT_COLS = ("leader", "n", "start", "class", "rings", "new_verts", "new_faces", "vert_offset", "face_offset")
+REAL_COLS = (("centre", 0, 3), ("color", 3, 6), ("box_lo", 6, 9), ("box_hi", 9, 12), ("size2", 12, 13), ("radius2", 13, 14),
+             ("edge2", 14, 15), ("area_normal", 15, 18))
+FLAG_BLOCKED, FLAG_PINCHED, FLAG_OPEN_CHAIN = 1, 2, 4
+NORMALS = ("keep", "angle", "area", "none", None)
+_MAX_RINGS = 65535
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _checked_args(max_edges, max_size, rings, max_rings, fair, lam, normals):
+    """(rings as the C entry takes it: 0 for "auto")"""
+    if max_edges is not None and (isinstance(max_edges, bool) or int(max_edges) != max_edges or max_edges < 0):
+        raise ValueError("fill_holes: max_edges must be a non-negative integer")
+    if max_size is not None and not (math.isfinite(float(max_size)) and float(max_size) >= 0.0):
+        raise ValueError("fill_holes: max_size must be finite and >= 0")
+    if isinstance(max_rings, bool) or int(max_rings) != max_rings or not 1 <= max_rings <= _MAX_RINGS:
+        raise ValueError(f"fill_holes: 1 <= max_rings <= {_MAX_RINGS}")
+    if rings != "auto" and (isinstance(rings, (bool, str)) or int(rings) != rings or not 1 <= rings <= _MAX_RINGS):
+        raise ValueError(f"fill_holes: rings must be 'auto' or an integer in [1, {_MAX_RINGS}]")
+    if isinstance(fair, bool) or int(fair) != fair or fair < 0 or fair >= 1 << 30:
+        raise ValueError("fill_holes: fair must be a count")
+    if not 0.0 < float(lam) <= 1.0:
+        raise ValueError("fill_holes: 0 < lam <= 1")
+    if normals not in NORMALS:
+        raise ValueError(f"fill_holes: normals must be one of {NORMALS}, got {normals!r}")
+    return 0 if rings == "auto" else int(rings)
+
+
+@torch.no_grad()
+def _loops(v, f, names, mask, colors, V, F, max_edges, max_size, rings, max_rings, skip_folded):
+    """nsa_mesh_fill_loops on device arrays: a dict of the item arrays [B], ``ints`` [L, 9], ``reals`` [L, 18], the device copies the
+    emit call reads, and ``totals`` (ints).  Reads Section 18's totals back once, to size the B-long buffers and the round count, and
+    the twelve totals of Section 23 once (two synchronisations)."""
+    dev = v.device
+    t, et = _edge_table(f if names is None else names, V, F, mask)
+    B = et["n_boundary"]
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    r = dict(B=B, halfedges=i32(B), next=i32(B), flags=torch.empty(B, dtype=torch.uint8, device=dev), leader=i32(B), rank=i32(B),
+             order=i32(B), ints=torch.zeros(B, len(INT_COLS), dtype=torch.int64, device=dev),
+             reals=torch.zeros(B, 18, dtype=torch.float64, device=dev), totals=dict.fromkeys(TOTALS, 0))
+    r["_ints"], r["_reals"], r["_order"] = r["ints"], r["reals"], r["order"]
+    if F == 0 or B == 0:
+        return r
+    ws = torch.empty(lib.nsa_mesh_fill_workspace(F, B), dtype=torch.uint8, device=dev)
+    tot = torch.zeros(len(TOTALS), dtype=torch.int64, device=dev)
+    ptr = lambda x: None if x is None else x.data_ptr()
+    check(lib.nsa_mesh_fill_loops(v.data_ptr(), ptr(colors), V, f.data_ptr(), ptr(names), F, t["edge_count"].data_ptr(),
+                                  t["edge_forward"].data_ptr(), t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(),
+                                  t["face_edges"].data_ptr(), t["_totals"].data_ptr(), B, int(max_edges is not None), int(max_edges or 0),
+                                  int(max_size is not None), 0.0 if max_size is None else float(max_size) * float(max_size), rings,
+                                  int(max_rings), int(bool(skip_folded)), ws.data_ptr(), r["halfedges"].data_ptr(), r["next"].data_ptr(),
+                                  r["flags"].data_ptr(), r["leader"].data_ptr(), r["rank"].data_ptr(), r["order"].data_ptr(),
+                                  r["ints"].data_ptr(), r["reals"].data_ptr(), tot.data_ptr(), _stream(dev)))
+    r["_totals"] = tot
+    host = dict(zip(TOTALS, (int(x) for x in tot.cpu())))
+    if host["status"] != 0:
+        raise RuntimeError(f"fill_holes: the loop tracing reported status {host['status']} (1: a rotation hit its step cap, 2: the "
+                           "boundary half-edges do not add up to the edge table's count); this is a bug")
+    L = host["n_loops"]
+    r.update(totals=host, ints=r["ints"][:L], reals=r["reals"][:L], order=r["order"][:B - host["n_open_chain"]])
+    return r
+
+
+@torch.no_grad()
+def _emit(v, f, colors, V, F, r):
+    """nsa_mesh_fill_emit: (verts [V + NV, 3], colours or None, faces [F + NF, 3]) with the input as their prefix"""
+    dev, NV, NF = v.device, r["totals"]["n_new_verts"], r["totals"]["n_new_faces"]
+    if V + NV >= 1 << 31 or 3 * (F + NF) >= 1 << 31:
+        raise ValueError("fill_holes: the filled mesh leaves the index range (n_verts < 2^31, 3 * n_faces < 2^31)")
+    out_v = torch.cat([v, torch.zeros(NV, 3, dtype=torch.float32, device=dev)])
+    out_c = None if colors is None else torch.cat([colors, torch.zeros(NV, 3, dtype=torch.float32, device=dev)])
+    out_f = torch.cat([f, torch.full((NF, 3), -1, dtype=torch.int32, device=dev)])
+    if NF:
+        check(lib.nsa_mesh_fill_emit(v.data_ptr(), None if colors is None else colors.data_ptr(), V, f.data_ptr(), F,
+                                     r["_order"].data_ptr(), r["B"], r["_ints"].data_ptr(), r["_reals"].data_ptr(),
+                                     r["_totals"].data_ptr(), NV, NF, out_v[V:].data_ptr(),
+                                     None if out_c is None else out_c[V:].data_ptr(), out_f[F:].data_ptr(), _stream(dev)))
+    return out_v, out_c, out_f
+
+
+def _arrays(mesh, name, weld, device):
+    """(verts, faces, names or None, mask or None, colours or None, V, F, give)"""
+    v, f, V, F, give = _mesh(mesh, name, device)
+    colors = mesh.get("colors")
+    if colors is not None:
+        if tuple(colors.shape) != (V, 3):
+            raise ValueError(f"{name}: colors must be [V, 3]")
+        colors = (colors if torch.is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors))).to(v.device).float().contiguous()
+    names = mask = None
+    if weld and F and V:
+        names, _, _, mask, _, _ = _mesh_arrays({"verts": v, "faces": f}, True, v.device, name)
+    return v, f, names, mask, colors, V, F, give
+
+
+def _report(r, give, V, NV):
+    out = {k: give(r[k]) for k in ("halfedges", "next", "flags", "rank", "order", "ints", "reals")}
+    out["item_leader"] = give(r["leader"])
+    ints = r["ints"].cpu()
+    out.update({k: ints[:, i].tolist() for i, k in enumerate(INT_COLS)})
+    out["class"] = [CLASSES[c] for c in out["class"]]
+    out.update({k: give(r["reals"][:, a:b].reshape(-1) if b - a == 1 else r["reals"][:, a:b]) for k, a, b in REAL_COLS})
+    out["totals"] = dict(r["totals"])
+    mask = torch.zeros(V + NV, dtype=torch.bool, device=r["ints"].device)
+    mask[V:] = True
+    out["new_vertex"] = give(mask)
+    return out
+
+
+def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, skip_folded=True, fair=0, lam=0.5, normals="keep",
+               weld=False, return_report=False, device="cuda"):
+    """``mesh`` (a dict with ``verts`` [V, 3] and ``faces`` [F, 3], optionally ``colors`` and ``normals`` [V, 3]; numpy or torch) with
+    its holes filled (header Section 23): a new dict of the same kind; the input's vertices and faces are a prefix of the result's.
+      max_edges     fill only loops of at most this many edges (``too_many_edges`` otherwise); None: no limit.
+      max_size      fill only loops whose bounding-box diagonal is at most this length (``too_large``); None: no limit.
+      rings         "auto": the patch of a loop of n edges has K rings of n vertices, K the smallest with K^2 * (mean squared edge
+                    length) >= mean squared distance to the centroid, at most ``max_rings``; an integer forces K.
+      skip_folded   leave out a loop that is not star-shaped about its centroid (some fan triangle faces against the others).
+      fair          N > 0: ``mesh_smooth.smooth(method="laplacian", iterations=N, lam=lam)`` with every old vertex fixed, which
+                    relaxes the patches alone.
+      normals       "keep": the stored normals of the old vertices stay and the new vertices get angle-weighted ones (nothing when
+                    the mesh stores none); "angle" / "area": ``mesh_smooth.vertex_normals`` of the result; "none" or None: none.
+      weld          trace the loops on ``mesh_eval.welded_faces`` names, so that seams of repeated vertices are no boundary; the
+                    patch names the duplicate its boundary half-edge names.
+    Colours of new vertices are interpolated like their positions, between the loop's vertices and its mean colour.
+    ``return_report=True`` appends a dict: per loop (ascending smallest half-edge) ``leader``, ``n``, ``start``, ``class``, ``rings``,
+    ``new_verts``, ``new_faces``, ``vert_offset``, ``face_offset``, ``centre``, ``color``, ``box_lo``, ``box_hi``, ``size2``,
+    ``radius2``, ``edge2``, ``area_normal`` (and the same as ``ints`` [L, 9] / ``reals`` [L, 18]); per boundary half-edge
+    ``halfedges``, ``next``, ``flags`` (1 blocked | 2 pinched | 4 open chain), ``item_leader``, ``rank``, and ``order``; ``totals``;
+    and the ``new_vertex`` mask.  Not built: minimum-area or advancing-front triangulations, refinement to the surrounding edge density,
+    curvature-continuing fairing, a self-intersection test beyond the star test.  Reads the edge table's totals back once, to size the
+    buffers of the B boundary half-edges and the round count, and this unit's twelve totals once (two synchronisations)."""
+    k_rings = _checked_args(max_edges, max_size, rings, max_rings, fair, lam, normals)
+    v, f, names, mask, colors, V, F, give = _arrays(mesh, "fill_holes", weld, device)
+    stored = mesh.get("normals")
+    if normals == "keep" and stored is not None and tuple(stored.shape) != (V, 3):
+        raise ValueError("fill_holes: normals must be [V, 3]")
+    r = _loops(v, f, names, mask, colors, V, F, max_edges, max_size, k_rings, max_rings, skip_folded)
+    out_v, out_c, out_f = _emit(v, f, colors, V, F, r)
+    NV = out_v.shape[0] - V
+    if fair and NV:
+        from .mesh_smooth import smooth
+        fixed = torch.ones(V + NV, dtype=torch.uint8, device=v.device)
+        fixed[V:] = 0
+        out_v = smooth({"verts": out_v, "faces": out_f}, method="laplacian", iterations=int(fair), lam=lam, fixed=fixed,
+                       normals=None)["verts"]
+    result = {k: x for k, x in mesh.items() if k not in ("verts", "faces", "colors", "normals")}
+    result["verts"], result["faces"] = give(out_v), give(out_f)
+    if out_c is not None:
+        result["colors"] = give(out_c)
+    if normals in WEIGHTING:
+        result["normals"] = give(_vertex_normals(out_v.contiguous(), out_f.contiguous(), V + NV, F + out_f.shape[0] - F, normals))
+    elif normals == "keep" and stored is not None:
+        old = (stored if torch.is_tensor(stored) else torch.from_numpy(np.ascontiguousarray(stored))).to(v.device).float()
+        new = _vertex_normals(out_v.contiguous(), out_f.contiguous(), V + NV, out_f.shape[0], "angle")[V:] if NV else old[:0]
+        result["normals"] = give(torch.cat([old, new]))
+    if return_report:
+        return result, _report(r, give, V, NV)
+    return result
+
+
+def boundary_loops(mesh, weld=False, device="cuda"):
+    """The ordered boundary loops of ``mesh``, a dict: ``loop_start`` [L + 1], ``vertices`` (the start vertices of the loops'
+    half-edges in rank order, loop after loop; each loop runs the way its boundary half-edges run), ``halfedges`` likewise, ``class``
+    (what ``fill_holes`` with its defaults would make of each loop) and ``n_open_chain``, the boundary half-edges on no loop."""
+    v, f, names, mask, colors, V, F, give = _arrays(mesh, "boundary_loops", weld, device)
+    r = _loops(v, f, names, mask, None, V, F, None, None, 0, 64, True)
+    order = r["order"].long()
+    n = r["ints"][:, 1]
+    start = torch.cat([torch.zeros(1, dtype=torch.int64, device=v.device), torch.cumsum(n, 0)])
+    return dict(loop_start=give(start), vertices=give(f.reshape(-1)[order]), halfedges=give(r["order"]),
+                **{"class": [CLASSES[c] for c in r["ints"][:, 3].tolist()]}, n_open_chain=r["totals"]["n_open_chain"])
+
+
+def format_report(rep):
+    t = rep["totals"]
+    lines = [f"{t['n_boundary']} boundary half-edges: {t['n_loops']} loops ({t['n_filled']} filled), {t['n_open_chain']} on open chains; "
+             f"+{t['n_new_verts']} vertices, +{t['n_new_faces']} faces"]
+    skipped = ", ".join(f"{t['n_' + c]} {c}" for c in CLASSES[1:] if t["n_" + c])
+    return lines[0] + (f"; skipped: {skipped}" if skipped else "")
+
+
+def main(argv=None):
+    from .inference import read_ply, write_ply
+    ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_fill", description=__doc__.splitlines()[0])
+    ap.add_argument("mesh", metavar="IN.ply")
+    ap.add_argument("--out", default=None, metavar="OUT.ply")
+    ap.add_argument("--max-edges", type=int, default=None, help="fill only loops of at most this many edges")
+    ap.add_argument("--max-size", type=float, default=None, help="fill only loops whose bounding-box diagonal is at most this")
+    ap.add_argument("--rings", default="auto", help="auto, or the number of rings of every patch")
+    ap.add_argument("--fair", type=int, default=0, help="Laplacian steps over the new vertices")
+    ap.add_argument("--keep-folded", action="store_true", help="fill loops that are not star-shaped as well")
+    ap.add_argument("--normals", choices=("keep", "angle", "area", "none"), default="keep")
+    ap.add_argument("--weld", action="store_true")
+    ap.add_argument("--list", action="store_true", help="print one line per loop")
+    ap.add_argument("--json", action="store_true", help="print the totals as one JSON object")
+    a = ap.parse_args(argv)
+    if a.out is None and not a.list:
+        ap.error("give --out, --list or both")
+    if a.rings != "auto":
+        try:
+            a.rings = int(a.rings)
+        except ValueError:
+            ap.error("--rings takes auto or an integer")
+    _need_gpu("mesh_fill")
+    try:
+        mesh = read_ply(a.mesh)
+        r, rep = fill_holes(mesh, max_edges=a.max_edges, max_size=a.max_size, rings=a.rings, skip_folded=not a.keep_folded, fair=a.fair,
+                            normals=a.normals, weld=a.weld, return_report=True)
+        if a.out is not None:
+            ply = {k: torch.from_numpy(np.ascontiguousarray(r[k])) for k in ("verts", "faces", "normals", "colors") if k in r}
+            if "normals" not in ply:                      # (write_ply stores normals; a file without them gets zeros)
+                ply["normals"] = torch.zeros_like(ply["verts"])
+            write_ply(a.out, ply)
+    except (ValueError, OSError) as e:
+        print(f"mesh_fill: {e}", file=sys.stderr)
+        raise SystemExit(2)
+    t = rep["totals"]
+    if a.list and not a.json:
+        for l in range(t["n_loops"]):
+            print(f"loop {l}: {rep['n'][l]} edges, {rep['class'][l]}, {rep['rings'][l]} rings, size {math.sqrt(float(rep['size2'][l])):.6g}")
+    print(json.dumps(t) if a.json else format_report(rep) + (f" -> {a.out}" if a.out else ""))
+    return t
+
+
+if __name__ == "__main__":
+    main()

@@ -201,12 +201,15 @@ class TSDFVolume:
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, min_weight=1, smooth=None, decimate=None):
+    def extract_mesh(self, min_weight=1, smooth=None, decimate=None, fill_holes=None):
         """The zero level of the observed volume: the ``inference.marching_cubes`` dict (verts, normals, faces), plus ``colors`` when
         the volume has colour -- what ``inference.write_ply`` and ``mesh_eval.mesh_metrics`` take.  ``smooth``: a dict of
         ``mesh_smooth.smooth`` keywords, applied after the colours are sampled on the true level set (the depth noise of the
         frames is on that surface); None leaves the mesh as marching cubes made it.  ``decimate``: a dict of
-        ``mesh_decimate.decimate`` keywords, applied last; None collapses nothing."""
+        ``mesh_decimate.decimate`` keywords, applied last; None collapses nothing.  ``fill_holes``: a dict of
+        ``mesh_fill.fill_holes`` keywords, applied after the colours and before ``smooth`` and ``decimate``; None fills nothing."""
+        if fill_holes is not None and not isinstance(fill_holes, dict):
+            raise ValueError("extract_mesh: fill_holes must be None or a dict of mesh_fill.fill_holes keywords")
         if decimate is not None and not isinstance(decimate, dict):
             raise ValueError("extract_mesh: decimate must be None or a dict of mesh_decimate.decimate keywords")
         if smooth is not None and not isinstance(smooth, dict):
@@ -215,6 +218,9 @@ class TSDFVolume:
         mesh = marching_cubes(self.surface_volume(min_weight), 0.0, (self.voxel_length,) * 3, self.centre0)
         if self.colour is not None:
             mesh["colors"] = self.sample_colour(mesh["verts"])
+        if fill_holes is not None:
+            from .mesh_fill import fill_holes as fill_mesh
+            mesh = fill_mesh(mesh, **fill_holes)
         if smooth is not None:
             from .mesh_smooth import smooth as smooth_mesh
             mesh = smooth_mesh(mesh, **smooth)
