@@ -1749,6 +1749,76 @@ int nsa_mesh_fill_emit(const float *verts, const float *colors, uint32_t n_verts
                        const uint64_t *totals, uint64_t n_new_verts, uint64_t n_new_faces, float *new_verts, float *new_colors,
                        int32_t *new_faces, nsa_stream_t stream);
 
+/* ---- Section 24: minimum-area patches for holes that are not star-shaped (csrc/mesh_fill_area.hip) ---- */
+
+/* Triangulates boundary loops of Section 23 without a new vertex, minimum total area first, after nsa_mesh_fill_loops on the same
+ * arrays.  A loop of n edges has the vertices p_0 .. p_{n-1}, the start vertices of its half-edges in rank order; its patch has n - 2
+ * faces.  tests/fill_area_ref.py restates this section in numpy and the device equals it element for element, bit for bit.
+ *
+ * Arithmetic.  Float64 on the fp32 positions; + - * rounded one by one, nothing contracted; Section 23's dot and cross products; one
+ * square root per triangle, which must be IEEE correctly rounded: the device's sqrt(double) is (tests/test_mesh_fill_area_gpu.py pins
+ * it against numpy on 10^5 values, half of them beside a rounding boundary), so none is written out here.
+ *
+ * Weight.  a = p_j - p_i, b = p_k - p_i, c = a x b, n2 = c . c, e = the largest of a . a, b . b, (b - a) . (b - a) (a running
+ * "if x > e: e = x" from a . a).  T(i, j, k) = 0.5 * sqrt(n2) when n2 > min_sin2 * (e * e), +inf otherwise; min_sin2 is squared by
+ * the caller.  A collinear run of loop vertices therefore gets no zero-area face for free.
+ *
+ * Table, for 0 <= i < k < n.  W[i][i+1] = 0; W[i][k] = the minimum over i < j < k of (W[i][j] + W[j][k]) + T(i, j, k); J[i][k] is the
+ * smallest j that attains it (i + 1 when every candidate is +inf).  The minimum is over (value, j) pairs, a pair winning on a smaller
+ * value or an equal value and a smaller j: associative and commutative, so every order of reduction gives the same bits.
+ *
+ * Forbidden chords.  A pair (i, k) that is no loop edge (k = i + 1, or (0, n - 1)) is a chord.  It is FORBIDDEN when Section 18's
+ * edges (sorted by (lo, hi); found by bisection) hold the edge between the names of p_i and p_k, names being the face list the edge
+ * table was built from, or when the two names are equal or invalid; its W[i][k] is +inf, set after the minimum is taken (J stays).
+ * A patch then never puts a third face on an edge of the mesh.
+ *
+ * Class of a loop (area_ints column 0): -1 not selected (its Section 23 class c has bit c of class_mask clear); AREA_FILLED 0;
+ * AREA_TOO_MANY_EDGES 1 (n > max_area_edges: nothing is computed); NO_TRIANGULATION 2 (n < 3, known to the plan, or W[0][n-1] not
+ * finite, known after the tables).  The loop stays open in the last two.
+ *
+ * nsa_mesh_fill_area_plan (one launch): area_ints[B, 6] int64, the first L rows {class, n, table_offset, plan_face_offset,
+ * row_offset, 0}: the exclusive scans of n^2, n - 2 and n over the loops that take a table (selected, 3 <= n <= max_area_edges), and
+ * plan_totals[8] (uint64, device) {selected, loops with a table, too many edges, cells = sum n^2, max n, plan faces = sum (n - 2),
+ * rows = sum n, 0}.  The caller reads plan_totals back once, sizes the workspace with nsa_mesh_fill_area_workspace(cells, rows) and
+ * new_faces[plan faces, 3], and passes the numbers on.
+ *
+ * nsa_mesh_fill_area_tables: positions and names per row; chord mask and start values per cell; one launch per diagonal
+ * d = 2 .. max n - 1 over the cells (i, i + d) of all tabled loops; then the final classes, area[B] (W[0][n-1]; 0 without a table),
+ * area_ints column 5 = face_offset, the exclusive scan of n - 2 over the AREA_FILLED loops, and final_totals[4] {area_filled,
+ * area_too_many_edges, no_triangulation, faces}; then the faces.  Face numbering is pre-order: the sub-tree of (i, k) holds k - i - 1
+ * triangles; with j = J[i][k] the triangle (i, j, k) has number base, the sub-tree of (i, j) starts at base + 1 and that of (j, k)
+ * at base + 1 + (j - i - 1); the root (0, n - 1) has base = the loop's offset.  The triangle is written (p_k, p_j, p_i), against the
+ * boundary half-edges, naming the vertices the half-edges name.  new_faces is written in the PLAN's numbering (plan_face_offset):
+ * the n - 2 rows of a loop that turned out NO_TRIANGULATION are (-1, -1, -1), and the caller drops them, which gives the final
+ * numbering (face_offset).  Emit is one lane per face descending from the root, so no stack and no order of emission exists.
+ *
+ * Workspace: W and its transposed copy (float64 per cell), J (int32 per cell), the mask (a byte per cell), and per row the position
+ * (3 float64), the loop and the name; in the order W, transposed W, positions, J, row loops, row names, mask, each part rounded up
+ * to 256 bytes (the tests read W, J and the mask there).  NULL arguments (names excepted), max_area_edges = 0 or > 16384, class_mask >= 64, a negative
+ * or NaN min_sin2, counts outside Section 23's ranges, cells / rows / max_n that cannot belong together (max_n < 3 or > 16384,
+ * rows > n_boundary, cells < max_n^2 or > 16384 rows, faces > rows): NSA_EBADARG before anything is launched.  All four counts zero
+ * (no tabled loop) launches nothing and returns 0.  Nothing is allocated or synchronised; no atomics. */
+
+#define NSA_FILL_AREA_FILLED 0
+#define NSA_FILL_AREA_TOO_MANY_EDGES 1
+#define NSA_FILL_AREA_NO_TRIANGULATION 2
+
+int nsa_mesh_fill_area_plan(const int64_t *loop_ints, const uint64_t *fill_totals, uint32_t n_faces, uint32_t n_boundary,
+                            uint32_t class_mask, uint32_t max_area_edges, int64_t *area_ints, uint64_t *plan_totals, nsa_stream_t stream);
+
+/* bytes of workspace (256-byte aligned, device); 0 for counts that cannot belong together */
+uint64_t nsa_mesh_fill_area_workspace(uint64_t n_cells, uint64_t n_rows);
+
+int nsa_mesh_fill_area_tables(const float *verts, uint32_t n_verts, const int32_t *faces, const int32_t *names, uint32_t n_faces,
+                              const int32_t *edges, const uint64_t *edge_totals, const int32_t *order, uint32_t n_boundary,
+                              const int64_t *loop_ints, const uint64_t *fill_totals, int64_t *area_ints, uint64_t n_cells, uint64_t n_rows,
+                              uint32_t max_n, uint64_t n_new_faces, double min_sin2, void *workspace, double *area, int32_t *new_faces,
+                              uint64_t *final_totals, nsa_stream_t stream);
+
+/* out[i] = the square root of x[i] exactly as the weights take it (float64, device arrays of n): the hook of the test that holds the
+ * device's root to IEEE rounding.  n = 0 launches nothing. */
+int nsa_mesh_fill_area_roots(const double *x, uint64_t n, double *out, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -463,3 +463,13 @@ lib.nsa_mesh_fill_emit.restype = _i
 lib.nsa_mesh_fill_emit.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p, _u64, _u64, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_fill_workspace", "nsa_mesh_fill_loops", "nsa_mesh_fill_emit"]
 FILL_CLASSES = ("filled", "nonfinite", "pinched", "too_many_edges", "too_large", "folded")         # NSA_FILL_* of header Section 23
+lib.nsa_mesh_fill_area_plan.restype = _i
+lib.nsa_mesh_fill_area_plan.argtypes = [_p, _p, _u32, _u32, _u32, _u32, _p, _p, _p]
+lib.nsa_mesh_fill_area_workspace.restype = _u64
+lib.nsa_mesh_fill_area_workspace.argtypes = [_u64, _u64]
+lib.nsa_mesh_fill_area_tables.restype = _i
+lib.nsa_mesh_fill_area_tables.argtypes = [_p, _u32, _p, _p, _u32, _p, _p, _p, _u32, _p, _p, _p, _u64, _u64, _u32, _u64, _f64, _p, _p, _p, _p, _p]
+lib.nsa_mesh_fill_area_roots.restype = _i
+lib.nsa_mesh_fill_area_roots.argtypes = [_p, _u64, _p, _p]
+EXPORTS += ["nsa_mesh_fill_area_plan", "nsa_mesh_fill_area_workspace", "nsa_mesh_fill_area_tables", "nsa_mesh_fill_area_roots"]
+FILL_AREA_CLASSES = ("area_filled", "area_too_many_edges", "no_triangulation")                      # NSA_FILL_AREA_* of header Section 24

@@ -5,7 +5,12 @@ included) and of the three native calls on their own (edge table, loops, emit); 
 back, the same call with skip_folded=False beside it.  There is no earlier version and no runnable
 reference program, so no time is gated; the table stands beside the host route, tests/fill_ref.py in numpy on the same machine (wall
 clock, one run).  The device result is compared with the host's bit for bit while at it.  Results go to profiles/mesh_fill_bench.json.
-usage: python tools/bench_mesh_fill.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
+With --method auto | min_area the same three meshes go through the minimum-area patches: the time of the call, of the
+plan and of the tables-and-emit entry point on their own, and of the numpy statement tests/fill_area_ref.py on the same machine; the
+device's faces are compared with the statement's; the room's row also says whether it is closed, which sign rule sign="auto" takes
+afterwards, and the patch area beside the polar patch's of skip_folded=False.  Results go to profiles/mesh_fill_area_bench.json
+(profiles/mesh_fill_area_bench_min_area.json for min_area).
+usage: python tools/bench_mesh_fill.py [--method polar|auto|min_area] [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
 import json
 import os
 import sys
@@ -21,6 +26,13 @@ import torch
 from nicer_slam_amd import inference, mesh_fill as M, mesh_topology
 from nicer_slam_amd._native import lib, check
 
+METHOD = "polar"
+if "--method" in sys.argv:                                        # (taken out: tools/bench_mesh_clean.py reads the same positions)
+    at = sys.argv.index("--method")
+    METHOD = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+if METHOD not in M.METHODS:
+    raise SystemExit(f"--method must be one of {M.METHODS}")
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
@@ -70,7 +82,73 @@ def native_calls(v, f):
     return out
 
 
+def patch_area(mesh, first_face):
+    """the area of the faces from first_face on, in float64"""
+    v, f = mesh["verts"].double(), mesh["faces"][first_face:].long()
+    n = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    return float(0.5 * n.norm(dim=1).sum())
+
+
+def area_case(name, mesh, out):
+    """one mesh through method=METHOD"""
+    import fill_area_ref
+    from nicer_slam_amd import mesh_sdf
+    v, f = mesh["verts"].float().contiguous(), mesh["faces"].to(torch.int32).contiguous()
+    mesh = {"verts": v, "faces": f}
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    got, rep = M.fill_holes(mesh, return_report=True, method=METHOD)
+    at = rep["area_totals"]
+    r = {"V": V, "F": F, "method": METHOD, "totals": rep["totals"], "area_totals": at,
+         "diagonal launches": max(at["max_n"] - 2, 0),
+         "loop edges": {"max": max(rep["n"], default=0), "median": float(np.median(rep["n"])) if rep["n"] else 0.0},
+         "area classes of the selected loops": {c: rep["area_class"].count(c) for c in M.AREA_CLASSES},
+         "patch area": float(sum(a for a, c in zip(rep["area"].cpu().tolist(), rep["area_class"]) if c == "area_filled")),
+         "fill_holes(method) ms": timed(lambda: M.fill_holes(mesh, method=METHOD)),
+         "fill_holes() ms, polar": timed(lambda: M.fill_holes(mesh))}
+    after = mesh_topology.topology(got)
+    r["after"] = {k: after[k] for k in ("n_boundary", "n_boundary_loops", "is_watertight", "is_oriented")}
+    r["sign rule of sign=auto, before -> after"] = [mesh_sdf.resolve_sign(mesh, "auto"), mesh_sdf.resolve_sign(got, "auto")]
+    if rep["totals"]["n_boundary"]:
+        lr = M._loops(v, f, None, None, None, V, F, None, None, 0, 64, True)
+        mask = 1 << 5 if METHOD == "auto" else 1 | 1 << 5
+        B, s = lr["B"], torch.cuda.current_stream(dev).cuda_stream
+        ints, plan = torch.zeros(B, 6, dtype=torch.int64, device=dev), torch.zeros(8, dtype=torch.int64, device=dev)
+        r["nsa_mesh_fill_area_plan ms"] = timed(lambda: check(lib.nsa_mesh_fill_area_plan(
+            lr["_ints"].data_ptr(), lr["_totals"].data_ptr(), F, B, mask, 2048, ints.data_ptr(), plan.data_ptr(), s)))
+        _, tabled, _, cells, max_n, plan_faces, rows, _ = (int(x) for x in plan.cpu())
+        if tabled:
+            nbytes = lib.nsa_mesh_fill_area_workspace(cells, rows)
+            r["workspace MB"] = nbytes / 1e6
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            area, faces = torch.zeros(B, dtype=torch.float64, device=dev), torch.full((plan_faces, 3), -1, dtype=torch.int32, device=dev)
+            final, t = torch.zeros(4, dtype=torch.int64, device=dev), lr["_edge"]
+
+            def tables():
+                check(lib.nsa_mesh_fill_area_plan(lr["_ints"].data_ptr(), lr["_totals"].data_ptr(), F, B, mask, 2048, ints.data_ptr(),
+                                                  plan.data_ptr(), s))                 # (the tables entry rewrites the classes)
+                check(lib.nsa_mesh_fill_area_tables(v.data_ptr(), V, f.data_ptr(), None, F, t["edges"].data_ptr(), t["_totals"].data_ptr(),
+                                                    lr["_order"].data_ptr(), B, lr["_ints"].data_ptr(), lr["_totals"].data_ptr(),
+                                                    ints.data_ptr(), cells, rows, max_n, plan_faces, 1e-12, ws.data_ptr(), area.data_ptr(),
+                                                    faces.data_ptr(), final.data_ptr(), s))
+
+            r["nsa_mesh_fill_area_plan + nsa_mesh_fill_area_tables ms"] = timed(tables)
+    if rep["totals"]["n_folded"]:                                 # the polar patch the star test would have refused, beside it
+        kept, rep2 = M.fill_holes(mesh, return_report=True, skip_folded=False)
+        r["skip_folded=False, polar"] = {"patch area": patch_area(kept, F), "new faces": rep2["totals"]["n_new_faces"]}
+    host = {"verts": v.cpu().numpy(), "faces": f.cpu().numpy()}
+    t0 = time.perf_counter()
+    ref = fill_area_ref.fill_holes(host, method=METHOD)
+    r["host route (numpy) ms"] = 1e3 * (time.perf_counter() - t0)
+    r["equals the host route"] = bool(ref["area_totals"] == at and np.array_equal(got["faces"].cpu().numpy(), ref["faces"]) and
+                                      got["verts"].cpu().numpy().tobytes() == ref["verts"].tobytes() and
+                                      np.array_equal(rep["area"].cpu().numpy().view(np.uint64), ref["area"].view(np.uint64)))
+    out[name] = r
+    print(name, json.dumps(r), flush=True)
+
+
 def case(name, mesh, out):
+    if METHOD != "polar":
+        return area_case(name, mesh, out)
     import fill_ref
     v, f = mesh["verts"].float().contiguous(), mesh["faces"].to(torch.int32).contiguous()
     mesh = {"verts": v, "faces": f}
@@ -109,7 +187,8 @@ def main():
     text = json.dumps(out, indent=1)
     print(text)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_fill_bench.json"), "w") as fh:
+    name = {"polar": "mesh_fill_bench.json", "auto": "mesh_fill_area_bench.json"}.get(METHOD, f"mesh_fill_area_bench_{METHOD}.json")
+    with open(os.path.join(ROOT, "profiles", name), "w") as fh:
         fh.write(text + "\n")
 
 
