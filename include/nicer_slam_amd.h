@@ -1819,6 +1819,66 @@ int nsa_mesh_fill_area_tables(const float *verts, uint32_t n_verts, const int32_
  * device's root to IEEE rounding.  n = 0 launches nothing. */
 int nsa_mesh_fill_area_roots(const double *x, uint64_t n, double *out, nsa_stream_t stream);
 
+/* ---- Section 25: self-intersections of a mesh, decided exactly (csrc/mesh_intersect.hip) ---- */
+
+/* Which pairs of faces of a mesh meet.  The vertices are fp32, every fp32 number is a rational, so for two faces A and B (closed
+ * triangles) the set I = A n B is defined over the reals and so is everything below: the answer is that real-number answer, for
+ * every pair, without a tolerance.  tests/intersect_ref.py constructs I in rationals and the device equals it element for element.
+ *
+ * Usable faces: Section 14's (cause 0), minus the faces whose three vertices are exactly collinear -- the float64 cross product of
+ * Section 14 is not exact, so 256-bit integers decide -- state 4, skipped and counted like causes 1 .. 3.  State 5: the exponents of
+ * the face's own nine coordinates span more than 102 binades; the device leaves the face out and the caller decides it.
+ *
+ * Candidates: the pairs i < j of usable faces whose exact boxes (the fp32 min / max of the nine coordinates, no pad) overlap as closed
+ * boxes on all three axes; with `side` (a byte per face) only those with side[i] != side[j].  Their number, and its split by s, are
+ * functions of the inputs.
+ *
+ * s = the number of vertex POSITIONS of A that are vertex positions of B (fp32 equality, -0 = +0), 0 .. 3: a seam with repeated
+ * vertices behaves like a welded one.  A candidate is REPORTED iff I contains a point outside the convex hull of the shared positions:
+ * s = 0: I is not empty; s = 1: I is more than the shared vertex; s = 2: I is more than the shared edge (the coplanar fold-over);
+ * s = 3: always (a duplicate, in either orientation).  Ordinary neighbours of a manifold mesh are never reported.
+ *
+ * code of a reported pair: bits 0-1 the kind -- NSA_ISECT_PROPER: the relative interiors of A and B meet (a transversal crossing, a
+ * coplanar overlap with area, a fold-over, a duplicate); NSA_ISECT_TOUCH: reported and not proper (a vertex on a face, an edge lying
+ * in a face, a T-junction along part of an edge, two edges crossing at a point); NSA_ISECT_UNRESOLVED: the exponents of the pair's 18
+ * coordinates span more than 59 binades, the 256-bit determinants could overflow, and the caller decides the pair --; bit 2
+ * NSA_ISECT_COPLANAR; bits 4-5 s.
+ *
+ * Stages.  1: orientation determinants of four points in float64 (+ - * one by one, nothing contracted) with the forward error bound
+ * 2^-49 * permanent derived in csrc/intersect_passes.hpp; a sign is certain when |det| > bound or bound == 0.  Stage 1 decides a pair
+ * only from signs that are certain and not zero: a pair with s = 0 and all signs generic, and any pair in which every vertex of one
+ * face that is no shared position lies strictly on one side of the other's plane (not reported).  2: the same determinants in 256-bit
+ * two's-complement integers on the coordinates scaled by a power of two, zeros included, and the closed-set decision of
+ * intersect_passes.hpp for every s, the coplanar case included.
+ *
+ * nsa_tri_isect_count, on the tree nsa_tri_ray_build made for the same arrays: state[F]; then one lane per sorted face walks the tree
+ * (its padded boxes are supersets of the exact ones; the exact-box clause is part of the pair test, so the walk and the brute force
+ * of NSA_ISECT_BRUTE agree by construction) and counts its records; then totals[16] (uint64, device): {records to emit, candidates
+ * with s = 0, 1, 2, 3, candidates decided by stage 1, by stage 2, left unresolved, faces of state 1, 2, 3, 4, 5, usable faces, 0, 0}.
+ * The caller reads totals back, sizes pairs[n, 2] (int64) and code[n] and calls nsa_tri_isect_emit with the same arguments, which
+ * writes the records (i, j), i < j, grouped by lane in walk order: sorting by i * F + j gives the canonical order.  No atomics; two
+ * runs write the same bytes.
+ *
+ * Workspace: count (uint32 per face), offset (uint64, F + 1), statistics (8 uint32 per face), each part rounded up to 256 bytes.
+ * A count above 2^31 - 1, an unknown flag, a NULL array (side excepted) with n_faces > 0: NSA_EBADARG before anything is launched.
+ * n_faces = 0 (and, for emit, n_pairs = 0) launches nothing and returns 0.  Nothing is allocated or synchronised. */
+
+#define NSA_ISECT_PROPER 1
+#define NSA_ISECT_TOUCH 2
+#define NSA_ISECT_UNRESOLVED 3
+#define NSA_ISECT_COPLANAR 4
+#define NSA_ISECT_BRUTE 1u /* flags: test all pairs of usable faces instead of walking the tree */
+
+/* bytes of workspace (256-byte aligned, device); 0 for n_faces = 0 or above 2^31 - 1 */
+uint64_t nsa_tri_isect_workspace(uint32_t n_faces);
+
+int nsa_tri_isect_count(const void *tree, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                        const uint8_t *side, uint32_t flags, void *workspace, uint8_t *state, uint64_t *totals, nsa_stream_t stream);
+
+int nsa_tri_isect_emit(const void *tree, const float *verts, uint32_t n_verts, const int32_t *faces, uint32_t n_faces,
+                       const uint8_t *side, uint32_t flags, const void *workspace, const uint8_t *state, uint64_t n_pairs,
+                       int64_t *pairs, uint8_t *code, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

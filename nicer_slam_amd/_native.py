@@ -473,3 +473,10 @@ lib.nsa_mesh_fill_area_roots.restype = _i
 lib.nsa_mesh_fill_area_roots.argtypes = [_p, _u64, _p, _p]
 EXPORTS += ["nsa_mesh_fill_area_plan", "nsa_mesh_fill_area_workspace", "nsa_mesh_fill_area_tables", "nsa_mesh_fill_area_roots"]
 FILL_AREA_CLASSES = ("area_filled", "area_too_many_edges", "no_triangulation")                      # NSA_FILL_AREA_* of header Section 24
+lib.nsa_tri_isect_workspace.restype = _u64
+lib.nsa_tri_isect_workspace.argtypes = [_u32]
+lib.nsa_tri_isect_count.restype = _i
+lib.nsa_tri_isect_count.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p, _p]
+lib.nsa_tri_isect_emit.restype = _i
+lib.nsa_tri_isect_emit.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _u64, _p, _p, _p]
+EXPORTS += ["nsa_tri_isect_workspace", "nsa_tri_isect_count", "nsa_tri_isect_emit"]

@@ -393,6 +393,14 @@ class TriIndex:
             return out + (n_nodes.long(), n_tested.long())
         return out[0] if any_hit else out
 
+    def self_intersections(self, kinds=("proper", "touch"), between=None, brute=False, return_report=False):
+        """(pairs int64 [n, 2], code uint8 [n], flags uint8 [F]) on the index's device: the pairs of faces that meet in more than the
+        positions they share, decided exactly (header Section 25; ``mesh_intersect.self_intersections`` describes the
+        arguments and the report).  Walks the ray-cast tree, built on first use and kept."""
+        from .mesh_intersect import _search
+        *out, report = _search(self, kinds, between, brute)
+        return tuple(out) + (report,) if return_report else tuple(out)
+
     def ray_layout(self):
         """dict(L, nodes, usable faces, bytes) of the ray-cast tree (a host copy: a synchronisation)"""
         buf, info = self._ray_tree()

@@ -222,8 +222,30 @@ def _area_report(out, r, a, give, method):
     return out
 
 
+def _patch_intersections(out_v, out_f, F, rep, method):
+    """per loop: the proper pairs of the filled mesh with exactly one face in the loop's patch"""
+    from .mesh_eval import TriIndex
+    L, FT = len(rep["n"]), out_f.shape[0]
+    if FT == 0 or out_v.shape[0] == 0:
+        return [0] * L
+    label = torch.full((FT,), -1, dtype=torch.int64, device=out_f.device)
+    n_polar = 0 if method == "min_area" else sum(rep["new_faces"])
+    for l in range(L):
+        if method != "min_area" and rep["new_faces"][l]:
+            a = F + rep["face_offset"][l]
+            label[a:a + rep["new_faces"][l]] = l
+        if method != "polar" and rep["area_faces"][l]:
+            a = F + n_polar + rep["area_face_offset"][l]
+            label[a:a + rep["area_faces"][l]] = l
+    pairs, _, _ = TriIndex(out_v.contiguous(), out_f.contiguous()).self_intersections(kinds=("proper",), between=None)
+    la, lb = label[pairs[:, 0]], label[pairs[:, 1]]
+    apart = la != lb
+    hits = torch.cat([la[apart], lb[apart]])
+    return torch.bincount(hits[hits >= 0], minlength=L).tolist()
+
+
 def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, skip_folded=True, fair=0, lam=0.5, normals="keep",
-               weld=False, return_report=False, device="cuda", method="polar", max_area_edges=2048, min_sin=1e-6):
+               weld=False, return_report=False, device="cuda", method="polar", max_area_edges=2048, min_sin=1e-6, intersections=None):
     """``mesh`` (a dict with ``verts`` [V, 3] and ``faces`` [F, 3], optionally ``colors`` and ``normals`` [V, 3]; numpy or torch) with
     its holes filled (header Section 23): a new dict of the same kind; the input's vertices and faces are a prefix of the result's.
       max_edges     fill only loops of at most this many edges (``too_many_edges`` otherwise); None: no limit.
@@ -248,6 +270,9 @@ def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, 
                     chord the mesh already has, is ``no_triangulation`` and stays open.
       weld          trace the loops on ``mesh_eval.welded_faces`` names, so that seams of repeated vertices are no boundary; the
                     patch names the duplicate its boundary half-edge names.
+      intersections None, or "report" (with ``return_report=True``): the report gains ``proper_pairs``, per loop the number of
+                    pairs of faces that meet properly (``mesh_intersect``, header Section 25) with one face in that loop's patch and
+                    the other anywhere else in the result, old or new.  The mesh is not changed by it.
     Colours of new vertices are interpolated like their positions, between the loop's vertices and its mean colour.
     ``return_report=True`` appends a dict: per loop (ascending smallest half-edge) ``leader``, ``n``, ``start``, ``class``, ``rings``,
     ``new_verts``, ``new_faces``, ``vert_offset``, ``face_offset``, ``centre``, ``color``, ``box_lo``, ``box_hi``, ``size2``,
@@ -257,10 +282,12 @@ def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, 
     (``area_filled``, ``area_too_many_edges``, ``no_triangulation`` or None), ``area`` (the patch area W[0][n-1]), ``area_faces``,
     ``area_face_offset``, the same as ``area_ints`` [L, 6], and ``area_totals``.  Not built: dihedral-angle weights (Liepa),
     advancing-front triangulations, refinement of a patch to the surrounding edge density, fairing of patches without interior
-    vertices, curvature-continuing fairing, a self-intersection test of a patch against the rest of the mesh.  Reads the edge table's
+    vertices, curvature-continuing fairing, the repair of a patch that ``intersections="report"`` finds crossing the mesh.  Reads the edge table's
     totals back once, to size the buffers of the B boundary half-edges and the round count, and this unit's twelve totals once (two
     synchronisations); Section 24 adds two more, the plan's totals and the final ones."""
     k_rings = _checked_args(max_edges, max_size, rings, max_rings, fair, lam, normals, method, max_area_edges, min_sin, skip_folded)
+    if intersections not in (None, "report") or (intersections and not return_report):
+        raise ValueError("fill_holes: intersections must be None or 'report', and 'report' needs return_report=True")
     v, f, names, mask, colors, V, F, give = _arrays(mesh, "fill_holes", weld, device)
     stored = mesh.get("normals")
     if normals == "keep" and stored is not None and tuple(stored.shape) != (V, 3):
@@ -294,7 +321,10 @@ def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, 
         result["normals"] = give(torch.cat([old, new]))
     if return_report:
         rep = _report(r, give, V, NV)
-        return result, rep if method == "polar" else _area_report(rep, r, area, give, method)
+        rep = rep if method == "polar" else _area_report(rep, r, area, give, method)
+        if intersections:
+            rep["proper_pairs"] = _patch_intersections(out_v, out_f, F, rep, method)
+        return result, rep
     return result
 
 

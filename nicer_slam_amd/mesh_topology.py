@@ -193,7 +193,7 @@ def _mesh_arrays(mesh, weld, device, name):
 
 
 @torch.no_grad()
-def topology(mesh, weld=False, device="cuda"):
+def topology(mesh, weld=False, device="cuda", intersections=False):
     """The topology report of ``mesh`` (a dict with ``verts`` and ``faces``, numpy or torch), a dict of ints and bools:
       n_faces, n_contributing, n_used_verts, n_edges, n_boundary, n_nonmanifold, n_inconsistent, n_boundary_loops (the holes),
       n_components (joined across edges), euler = used vertices - edges + contributing faces,
@@ -201,11 +201,18 @@ def topology(mesh, weld=False, device="cuda"):
       is_oriented    (watertight and no interior edge that its two faces traverse the same way).
     ``weld=True`` names every vertex by its fp32 coordinates as ``TriIndex.adjacency(weld=True)`` does
     (``mesh_eval.welded_faces``), so a mesh whose seams repeat vertices is connected across them, and masks out the faces that have
-    a non-finite vertex; the mesh itself is not rewritten."""
+    a non-finite vertex; the mesh itself is not rewritten.  ``intersections=True`` adds n_proper_pairs, the pairs of faces that
+    meet properly (``mesh_intersect``, header Section 25, on the positions as they are: it welds by position itself), and embedded
+    = there is none."""
     f, V, F, mask, _, _ = _mesh_arrays(mesh, weld, device, "topology")
     t, totals = _edge_table(f, V, F, mask)
     _, C = _face_components(t, F, f.device)
-    return _report(F, totals, C)
+    r = _report(F, totals, C)
+    if intersections:
+        from .mesh_intersect import self_intersections
+        r["n_proper_pairs"] = int(self_intersections(mesh, kinds=("proper",), device=device)[0].shape[0])
+        r["embedded"] = r["n_proper_pairs"] == 0
+    return r
 
 
 def split_faces(faces, face_label, n_verts):
@@ -462,6 +469,8 @@ def format_report(r):
              f"inconsistent edges {r['n_inconsistent']}",
              f"components (joined across edges) {r['n_components']}, Euler characteristic {r['euler']}",
              f"watertight: {'yes' if r['is_watertight'] else 'no'}   consistently oriented: {'yes' if r['is_oriented'] else 'no'}"]
+    if "embedded" in r:
+        lines.append(f"pairs of faces meeting properly {r['n_proper_pairs']}: {'embedded' if r['embedded'] else 'NOT embedded'}")
     return lines
 
 
@@ -478,6 +487,7 @@ def main(argv=None):
     ap.add_argument("mesh")
     ap.add_argument("--weld", action="store_true", help="name vertices by their coordinates: connect across repeated seam vertices")
     ap.add_argument("--json", action="store_true", help="print the report as one JSON object")
+    ap.add_argument("--intersections", action="store_true", help="add n_proper_pairs and embedded (mesh_intersect, DESIGN 4x)")
     ap.add_argument("--orient", metavar="OUT.ply", help="write the mesh with a consistent winding (DESIGN 4s) and print that report")
     ap.add_argument("--outward", choices=("volume", "views", "none"), default="volume",
                     help="with --orient: which of the two consistent windings a component gets")
@@ -491,7 +501,7 @@ def main(argv=None):
     try:
         mesh = read_ply(a.mesh)
         if a.orient is None:
-            r = topology(mesh, weld=a.weld)
+            r = topology(mesh, weld=a.weld, intersections=a.intersections)
         else:
             from .inference import write_ply
             poses = None
