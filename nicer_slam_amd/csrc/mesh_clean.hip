@@ -8,14 +8,15 @@
 // and the final root is the smallest index of the component whatever the interleaving: the atomics reach the fixed point, they
 // decide nothing in the output.  Every loop has a step cap that reports through totals[2] instead of spinning.
 //
-// Statistics: the roots, in index order, are the components (rank = exclusive count of the roots below: a block count, a scan
-// of the block counts, a ballot scan inside each block).  Counts and bounding boxes are integer atomics (add; min / max on an
+// Statistics: the roots, in index order, are the components (rank = exclusive count of the roots below: flag_scan inside each
+// block and k_offsets over the block counts, both block_scan.hpp's).  Counts and bounding boxes are integer atomics (add; min / max on an
 // order-preserving integer image of the fp32 value), which give the same result in any order.  Areas are summed in a fixed
 // order: the faces are argsorted stably by rank (radix_sort.hpp), each aligned block of 1024 sorted positions is cut at the
 // component boundaries and every piece summed left to right, and a component adds its pieces in block order.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "mesh_area.hpp"
 #include "radix_sort.hpp"
@@ -26,7 +27,7 @@ namespace nsa {
 constexpr uint32_t kCcMaxCount = 0x7FFFFFFFu;
 constexpr uint32_t kCcBlock = 1024;          // block of the rank scan and of the area pieces
 
-typedef unsigned long long ull;
+using scan::ull;
 
 __host__ __device__ inline uint64_t cc_align(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 
@@ -116,56 +117,18 @@ __device__ __forceinline__ bool is_root(const int32_t* __restrict__ vlabel, uint
 }
 
 __global__ __launch_bounds__(kCcBlock) void k_st_count(const int32_t* __restrict__ vlabel, uint32_t V, StatWork w) {
-    __shared__ uint32_t red[16];
-    const uint32_t v = blockIdx.x * kCcBlock + threadIdx.x;
-    const ull b = __ballot(is_root(vlabel, v, V));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (int k = 0; k < 16; ++k) s += red[k];
-        w.bcount[blockIdx.x] = s;
-    }
-}
-
-// one workgroup: bcount[0, nb) -> its exclusive scan (integers: any association gives the same values)
-__global__ __launch_bounds__(kCcBlock) void k_st_offsets(StatWork w, uint32_t nb) {
-    __shared__ uint32_t part[kCcBlock];
-    const uint32_t t = threadIdx.x, per = (nb + kCcBlock - 1) / kCcBlock;
-    const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += w.bcount[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t c = 0;
-        for (uint32_t k = 0; k < kCcBlock; ++k) {
-            const uint32_t x = part[k];
-            part[k] = c;
-            c += x;
-        }
-    }
-    __syncthreads();
-    uint32_t c = part[t];
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t x = w.bcount[i];
-        w.bcount[i] = c;
-        c += x;
-    }
+    uint32_t total;
+    scan::flag_scan<kCcBlock>(is_root(vlabel, blockIdx.x * kCcBlock + threadIdx.x, V), total);
+    if (threadIdx.x == 0) w.bcount[blockIdx.x] = total;
 }
 
 // rank of every root; label[], and the identities of the per-component accumulators
 __global__ __launch_bounds__(kCcBlock) void k_st_rank(const int32_t* __restrict__ vlabel, uint32_t V, uint32_t C, StatWork w,
                                                       int32_t* __restrict__ label, int32_t* __restrict__ n_verts) {
-    __shared__ uint32_t wsum[16];
-    const uint32_t t = threadIdx.x, v = blockIdx.x * kCcBlock + t, lane = t & 63, wave = t >> 6;
+    const uint32_t v = blockIdx.x * kCcBlock + threadIdx.x;
     const bool root = is_root(vlabel, v, V);
-    const ull b = __ballot(root);
-    if (lane == 0) wsum[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t r = w.bcount[blockIdx.x];
-    for (uint32_t k = 0; k < wave; ++k) r += wsum[k];
-    r += (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    uint32_t total;
+    const uint32_t r = w.bcount[blockIdx.x] + scan::flag_scan<kCcBlock>(root, total);
     if (!root || r >= C) return;         // (r >= C: a caller that passed another count than the labelling gave)
     w.rank[v] = (int32_t)r;
     label[r] = (int32_t)v;
@@ -362,7 +325,8 @@ int nsa_mesh_component_stats(const float* verts, uint32_t n_verts, const int32_t
     const uint32_t nbv = (V + kCcBlock - 1) / kCcBlock, nbf = (F + kCcBlock - 1) / kCcBlock;
     launch_begin();
     hipLaunchKernelGGL(k_st_count, dim3(nbv), dim3(kCcBlock), 0, (hipStream_t)stream, vertex_label, V, w);
-    hipLaunchKernelGGL(k_st_offsets, dim3(1), dim3(kCcBlock), 0, (hipStream_t)stream, w, nbv);
+    hipLaunchKernelGGL((scan::k_offsets<1, uint32_t, kCcBlock>), dim3(1), dim3(kCcBlock), 0, (hipStream_t)stream,
+                       (const uint32_t*)w.bcount, w.bcount, nbv, (ull*)nullptr);
     hipLaunchKernelGGL(k_st_rank, dim3(nbv), dim3(kCcBlock), 0, (hipStream_t)stream, vertex_label, V, C, w, label, n_verts_out);
     hipLaunchKernelGGL(k_st_verts, dim3((V + 255) / 256), dim3(256), 0, (hipStream_t)stream, verts, vertex_label, V, C, w,
                        vertex_comp, n_verts_out);

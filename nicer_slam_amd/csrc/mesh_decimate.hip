@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "corner_table.hpp"
 #include "grid_common.hpp"
 #include "radix_sort.hpp"
@@ -21,7 +22,7 @@ namespace decimate {
 constexpr uint32_t kMaxVerts = 0x7FFFFFFFu;
 constexpr uint32_t kMaxFaces = 0x7FFFFFFFu / 6u;        // ring offsets up to 6 F are int32
 
-typedef unsigned long long ull;
+using scan::ull;
 
 using bulk::up256;
 
@@ -98,8 +99,7 @@ __host__ __device__ inline uint64_t round_carve(void* ws, uint32_t V, uint32_t F
 }
 
 __device__ __forceinline__ uint32_t edges_on_device(const ull* __restrict__ edge_totals, uint32_t H) {
-    const ull E = edge_totals[0];
-    return E < H ? (uint32_t)E : H;
+    return scan::capped(edge_totals[0], H);
 }
 
 // ---- the initial state ----------------------------------------------------------------------------------------------------------------
@@ -182,22 +182,16 @@ __global__ __launch_bounds__(256) void k_dc_sort_perm(const uint32_t* __restrict
     next[p] = q < H ? cur[q] : H;
 }
 
-// one lane per edge slot: the block's counts of the five codes and of the selected edges (ballots; integers, no atomics)
+// one lane per edge slot: the block's counts of the five codes and of the selected edges (integers, no atomics)
 __global__ __launch_bounds__(256) void k_dc_count(RoundWork w, uint32_t H) {
-    __shared__ uint32_t ws[6][4];
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     const uint8_t c = i < H ? w.code[i] : (uint8_t)255;
-    const bool sel = i < H && w.skey[i] != kNoKey;
+    const bool flag[6] = {c == 0, c == 1, c == 2, c == 3, c == 4, i < H && w.skey[i] != kNoKey};
+    uint32_t pre[6], total[6];
+    scan::flag_scan<6, 256>(flag, pre, total);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const ull b = __ballot(k < 5 ? c == k : sel);
-        if (lane == 0) ws[k][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const uint32_t k = threadIdx.x;
-        w.partial[6ull * blockIdx.x + k] = (ws[k][0] + ws[k][1]) + (ws[k][2] + ws[k][3]);
-    }
+    for (int k = 0; k < 6; ++k)
+        if (threadIdx.x == k) w.partial[6ull * blockIdx.x + k] = total[k];
 }
 
 // one workgroup: the sums of the block counts, then the prefix rule over the selected edges in key order
@@ -205,7 +199,6 @@ __global__ __launch_bounds__(256) void k_dc_totals(RoundWork w, State st, const 
                                                    const ull* __restrict__ edge_totals, uint32_t H, uint32_t round, bool has_target,
                                                    ull target, ull* __restrict__ totals) {
     __shared__ uint32_t red[6][256];
-    __shared__ uint32_t scan[256];
     __shared__ uint32_t sums[8];
     const uint32_t t = threadIdx.x, nb = (H + 255) / 256;
     uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
@@ -231,21 +224,14 @@ __global__ __launch_bounds__(256) void k_dc_totals(RoundWork w, State st, const 
             if (i < H) ec = (uint32_t)edge_count[i];
             else bad = 1;
         }
-        scan[t] = ec;
-        __syncthreads();
-        for (uint32_t d = 1; d < 256; d <<= 1) {
-            const uint32_t add = t >= d ? scan[t - d] : 0u;
-            __syncthreads();
-            scan[t] += add;
-            __syncthreads();
-        }
-        const ull before = carry + scan[t] - ec;
-        if (p < n_sel && prefix_take(has_target, n_faces, before, target)) {
+        const uint32_t own[1] = {ec};
+        uint32_t excl[1], total[1];
+        scan::lds_scan<1, uint32_t, 256>(own, excl, total);
+        if (p < n_sel && prefix_take(has_target, n_faces, carry + excl[0], target)) {
             ++n_take;
             removed += ec;
         }
-        carry += scan[255];
-        __syncthreads();
+        carry += total[0];
     }
     red[0][t] = n_take;
     red[1][t] = removed;

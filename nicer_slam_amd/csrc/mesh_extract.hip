@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "mc_table.hpp"
 
 namespace nsa {
@@ -138,36 +139,13 @@ __global__ __launch_bounds__(256) void k_mc_count(const float* __restrict__ vol,
     }
 }
 
-// Exclusive scan of the per-block (vertex, triangle) sums in block order, 1024 at a time (the inclusive-scan-in-LDS pattern of
-// map_tail.hip's radix blocks), and the two totals.
+// one workgroup: boff = the exclusive scan of the per-block (vertex, triangle) sums bsum (block_scan.hpp), and the two totals
 __global__ __launch_bounds__(1024) void k_mc_scan(McWork w, uint32_t n_blocks, uint64_t* __restrict__ totals) {
-    __shared__ uint64_t sv[1024], st[1024];
-    const uint32_t t = threadIdx.x;
-    uint64_t carry_v = 0, carry_t = 0;
-    for (uint32_t base = 0; base < n_blocks; base += 1024) {
-        const uint32_t i = base + t;
-        const uint64_t v = i < n_blocks ? w.bsum[i * 2] : 0, tr = i < n_blocks ? w.bsum[i * 2 + 1] : 0;
-        sv[t] = v;
-        st[t] = tr;
-        __syncthreads();
-        for (uint32_t o = 1; o < 1024; o <<= 1) {
-            const uint64_t a = t >= o ? sv[t - o] : 0, b = t >= o ? st[t - o] : 0;
-            __syncthreads();
-            sv[t] += a;
-            st[t] += b;
-            __syncthreads();
-        }
-        if (i < n_blocks) {
-            w.boff[i * 2] = carry_v + sv[t] - v;
-            w.boff[i * 2 + 1] = carry_t + st[t] - tr;
-        }
-        carry_v += sv[1023];
-        carry_t += st[1023];
-        __syncthreads();
-    }
-    if (t == 0) {
-        totals[0] = carry_v;
-        totals[1] = carry_t;
+    uint64_t total[2];
+    scan::offsets<2, uint64_t, 1024>(w.bsum, w.boff, n_blocks, total);
+    if (threadIdx.x == 0) {
+        totals[0] = total[0];
+        totals[1] = total[1];
     }
 }
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "radix_sort.hpp"
 #include "fill_passes.hpp"
@@ -21,7 +22,8 @@ constexpr uint32_t kMaxVerts = 0x7FFFFFFFu;
 constexpr uint32_t kMaxHalfedges = 0x7FFFFFFFu;
 constexpr int kScanMax = 8;                              // the most channels of a scan
 
-typedef unsigned long long ull;
+using scan::capped;
+using scan::ull;
 
 using bulk::up256;
 
@@ -77,39 +79,12 @@ __host__ __device__ inline uint64_t carve(void* ws, uint32_t F, uint32_t B, Work
     return o;
 }
 
-__device__ __forceinline__ uint32_t capped(ull x, uint32_t cap) { return x < cap ? (uint32_t)x : cap; }
-
 __device__ __forceinline__ Topo on_device(Topo t, const ull* __restrict__ edge_totals) {
     t.E = capped(edge_totals[0], 3u * t.F);
     return t;
 }
 
-// ---- scans of up to kScanMax integer channels over n items: block sums, one workgroup over the blocks, then the prefixes -------------
-
-// exclusive prefix of v over the 256 lanes of the block (Hillis-Steele in LDS) and the block's sum
-template <int C>
-__device__ __forceinline__ void block_scan(const ull (&v)[C], ull (&excl)[C], ull (&total)[C]) {
-    __shared__ ull sh[C][256];
-    const uint32_t t = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < C; ++c) sh[c][t] = v[c];
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        ull add[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) add[c] = t >= d ? sh[c][t - d] : 0ull;
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < C; ++c) sh[c][t] += add[c];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        excl[c] = sh[c][t] - v[c];
-        total[c] = sh[c][255];
-    }
-    __syncthreads();
-}
+// ---- scans of up to kScanMax integer channels over n items: block sums, one workgroup over the blocks (block_scan.hpp), the prefixes --
 
 template <int C, class In>
 __global__ __launch_bounds__(256) void k_scan_count(In in, uint32_t n, ull* __restrict__ partial) {
@@ -118,34 +93,10 @@ __global__ __launch_bounds__(256) void k_scan_count(In in, uint32_t n, ull* __re
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = 0;
     if (i < n) in(i, v);
-    block_scan<C>(v, excl, total);
+    scan::lds_scan<C, ull, 256>(v, excl, total);
 #pragma unroll
     for (int c = 0; c < C; ++c)
         if (threadIdx.x == c) partial[(ull)C * blockIdx.x + c] = total[c];
-}
-
-// one workgroup: partial[nb][C] -> its exclusive scan in place; sums[C] = the grand totals
-template <int C>
-__global__ __launch_bounds__(256) void k_scan_offsets(ull* __restrict__ partial, uint32_t nb, ull* __restrict__ sums) {
-    const uint32_t t = threadIdx.x, per = (nb + 255) / 256;
-    const uint32_t j0 = t * per < nb ? t * per : nb, j1 = j0 + per < nb ? j0 + per : nb;
-    ull v[C], excl[C], total[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = 0;
-    for (uint32_t j = j0; j < j1; ++j)
-#pragma unroll
-        for (int c = 0; c < C; ++c) v[c] += partial[(ull)C * j + c];
-    block_scan<C>(v, excl, total);
-    for (uint32_t j = j0; j < j1; ++j)
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const ull own = partial[(ull)C * j + c];
-            partial[(ull)C * j + c] = excl[c];
-            excl[c] += own;
-        }
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-        if (t == c) sums[c] = total[c];
 }
 
 template <int C, class In, class Out>
@@ -155,7 +106,7 @@ __global__ __launch_bounds__(256) void k_scan_write(In in, Out out, uint32_t n, 
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = 0;
     if (i < n) in(i, v);
-    block_scan<C>(v, excl, total);
+    scan::lds_scan<C, ull, 256>(v, excl, total);
     if (i >= n) return;
 #pragma unroll
     for (int c = 0; c < C; ++c) excl[c] += partial[(ull)C * blockIdx.x + c];
@@ -163,10 +114,10 @@ __global__ __launch_bounds__(256) void k_scan_write(In in, Out out, uint32_t n, 
 }
 
 template <int C, class In, class Out>
-void scan(In in, Out out, uint32_t n, const Work& w, ull* sums, hipStream_t s) {
+void scan_items(In in, Out out, uint32_t n, const Work& w, ull* sums, hipStream_t s) {
     const uint32_t nb = (n + 255) / 256;
     hipLaunchKernelGGL((k_scan_count<C, In>), dim3(nb), dim3(256), 0, s, in, n, w.partial);
-    hipLaunchKernelGGL((k_scan_offsets<C>), dim3(1), dim3(256), 0, s, w.partial, nb, sums);
+    hipLaunchKernelGGL((scan::k_offsets<C, ull, 256>), dim3(1), dim3(256), 0, s, (const ull*)w.partial, w.partial, nb, sums);
     hipLaunchKernelGGL((k_scan_write<C, In, Out>), dim3(nb), dim3(256), 0, s, in, out, n, (const ull*)w.partial);
 }
 
@@ -360,7 +311,7 @@ int nsa_mesh_fill_loops(const float* verts, const float* colors, uint32_t n_vert
     const Limits lim{has_max_edges != 0, (uint64_t)max_edges, has_max_size != 0, max_size2, rings, max_rings, skip_folded != 0};
     hipStream_t s = (hipStream_t)stream;
     launch_begin();
-    scan<1>(BoundaryIn{t, etot}, BoundaryOut{w, B}, H, w, w.misc, s);
+    scan_items<1>(BoundaryIn{t, etot}, BoundaryOut{w, B}, H, w, w.misc, s);
     hipLaunchKernelGGL(k_fl_next, dim3(nbb), dim3(256), 0, s, w, t, etot, B);
     radix_argsort(w.keys, w.tmp, w.sorder, w.counts, B, 0, V < 0xFFu ? 1 : V < 0xFFFFu ? 2 : V < 0xFFFFFFu ? 3 : 4, stream);
     hipLaunchKernelGGL(k_fl_pinch, dim3(nbb), dim3(256), 0, s, w, t, B);
@@ -370,10 +321,10 @@ int nsa_mesh_fill_loops(const float* verts, const float* colors, uint32_t n_vert
     hipLaunchKernelGGL(k_fl_rank_init, dim3(nbb), dim3(256), 0, s, w, B, cur);
     cur ^= 1;
     for (uint32_t r = 0; r < R; ++r, cur ^= 1) hipLaunchKernelGGL(k_fl_rank, dim3(nbb), dim3(256), 0, s, w, B, cur);
-    scan<4>(LeaderIn{w, B, cur, term}, LeaderOut{w, B, loop_ints}, B, w, w.misc + 1, s);
+    scan_items<4>(LeaderIn{w, B, cur, term}, LeaderOut{w, B, loop_ints}, B, w, w.misc + 1, s);
     hipLaunchKernelGGL(k_fl_order, dim3(nbb), dim3(256), 0, s, w, B, cur, term, halfedges, next, flags, leader, rank, order);
     hipLaunchKernelGGL(k_fl_loop, dim3(nbb), dim3(256), 0, s, w, m, lim, B, loop_ints, loop_reals);
-    scan<8>(PatchIn{w, B, loop_ints}, PatchOut{w, B, loop_ints}, B, w, w.misc + 5, s);
+    scan_items<8>(PatchIn{w, B, loop_ints}, PatchOut{w, B, loop_ints}, B, w, w.misc + 5, s);
     hipLaunchKernelGGL(k_fl_totals, dim3(1), dim3(64), 0, s, w, B, reinterpret_cast<ull*>(totals));
     return launch_end();
 }

@@ -12,13 +12,15 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "fill_area_passes.hpp"
 
 namespace nsa {
 namespace fill_area {
 
-typedef unsigned long long ull;
+using scan::capped;
+using scan::ull;
 
 using bulk::up256;
 
@@ -51,33 +53,6 @@ __host__ __device__ inline uint64_t carve(void* ws, uint64_t C, uint64_t R, Work
     return o;
 }
 
-__device__ __forceinline__ uint32_t capped(ull x, uint32_t cap) { return x < cap ? (uint32_t)x : cap; }
-
-// exclusive prefix of v over the 256 lanes of the one workgroup (Hillis-Steele in LDS) and the sum
-template <int C>
-__device__ __forceinline__ void block_scan(const ull (&v)[C], ull (&excl)[C], ull (&total)[C]) {
-    __shared__ ull sh[C][256];
-    const uint32_t t = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < C; ++c) sh[c][t] = v[c];
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        ull add[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) add[c] = t >= d ? sh[c][t - d] : 0ull;
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < C; ++c) sh[c][t] += add[c];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        excl[c] = sh[c][t] - v[c];
-        total[c] = sh[c][255];
-    }
-    __syncthreads();
-}
-
 // channels: cells, plan faces, rows, selected, tabled, too many edges
 __device__ __forceinline__ int64_t plan_row(const int64_t* loop_ints, uint32_t l, uint32_t class_mask, uint32_t cap, uint32_t B,
                                             ull (&v)[kChannels], ull* n_all) {
@@ -108,7 +83,7 @@ __global__ __launch_bounds__(256) void k_fa_plan(const int64_t* __restrict__ loo
         for (int c = 0; c < kChannels; ++c) sum[c] += v[c];
         if (v[2] > big) big = v[2];
     }
-    block_scan<kChannels>(sum, excl, total);
+    scan::lds_scan<kChannels, ull, 256>(sum, excl, total);
     for (uint32_t l = l0; l < l1; ++l) {
         const int64_t cls = plan_row(loop_ints, l, class_mask, cap, B, v, &n_all);
         int64_t* a = area_ints + (ull)kAreaInts * l;
@@ -218,8 +193,7 @@ __global__ __launch_bounds__(256) void k_fa_finish(Work w, Args a, int64_t* area
 #pragma unroll
         for (int c = 0; c < 4; ++c) sum[c] += v[c];
     }
-    block_scan<4>(sum, excl, total);
-    __syncthreads();
+    scan::lds_scan<4, ull, 256>(sum, excl, total);
     for (uint32_t l = l0; l < l1; ++l) {
         const int64_t cls = row(l, v, &ar);
         area[l] = ar;

@@ -10,8 +10,9 @@
 // pre-order with `skip`, so the walk needs no path at all: overlap and inner node -> the next index, else -> skip.
 //
 // No atomics.  The count pass writes per lane how many records it will emit and its share of the statistics; one workgroup scans the
-// counts and sums the rest; the emit pass repeats the walk and writes each record at its slot.  The records of one run are grouped
+// counts and sums the rest (block_scan.hpp); the emit pass repeats the walk and writes each record at its slot.  The records of one run are grouped
 // by p in walk order; the caller sorts by (i, j).
+#include "block_scan.hpp"
 #include "intersect_passes.hpp"
 #include "ray_tree.hpp"
 
@@ -218,42 +219,23 @@ __global__ __launch_bounds__(kBlock) void k_isect_brute(rc::Tree t, Mesh m, Work
     if (live) end_lane<kEmit>(ln, w, p);
 }
 
-__device__ __forceinline__ uint64_t block_sum(uint64_t x, uint64_t* s_sum) {
-    const uint32_t tid = threadIdx.x;
-    __syncthreads();
-    s_sum[tid] = x;
-    __syncthreads();
-    for (uint32_t wd = 512; wd > 0; wd >>= 1) {
-        if (tid < wd) s_sum[tid] += s_sum[tid + wd];
-        __syncthreads();
-    }
-    return s_sum[0];
+// the sum of x over the workgroup of 1024
+__device__ __forceinline__ uint64_t block_sum(uint64_t x) {
+    const uint64_t v[1] = {x};
+    uint64_t excl[1], total[1];
+    scan::lds_scan<1, uint64_t, 1024>(v, excl, total);
+    return total[0];
 }
 
 // one workgroup of 1024: offset = the exclusive prefix sum of count, and the totals
 __global__ __launch_bounds__(1024) void k_isect_totals(uint32_t F, Work w, const uint8_t* __restrict__ state,
                                                        uint64_t* __restrict__ totals) {
-    __shared__ uint64_t s_sum[1024];
     const uint32_t tid = threadIdx.x;
     const uint64_t n = F, chunk = (n + 1023) / 1024;
     const uint64_t lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    uint64_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += w.count[i];
-    s_sum[tid] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {                // Hillis-Steele, inclusive
-        const uint64_t add = tid >= off ? s_sum[tid - off] : 0;
-        __syncthreads();
-        s_sum[tid] += add;
-        __syncthreads();
-    }
-    uint64_t run = s_sum[tid] - sum;
-    const uint64_t n_emit = s_sum[1023];
-    for (uint64_t i = lo; i < hi; ++i) {
-        w.offset[i] = run;
-        run += w.count[i];
-    }
-    if (tid == 1023) w.offset[F] = n_emit;
+    uint64_t n_emit[1];
+    scan::offsets<1, uint64_t, 1024>(w.count, w.offset, n, n_emit);
+    if (tid == 1023) w.offset[F] = n_emit[0];
     uint64_t part[kStats - 1 + 6];
     for (int k = 0; k < kStats - 1 + 6; ++k) part[k] = 0;
     for (uint64_t i = lo; i < hi; ++i) {
@@ -263,10 +245,10 @@ __global__ __launch_bounds__(1024) void k_isect_totals(uint32_t F, Work w, const
     }
     uint64_t out[kTotals];
     for (int k = 0; k < kTotals; ++k) out[k] = 0;
-    out[0] = n_emit;
-    for (int k = 0; k < kStats - 1; ++k) out[1 + k] = block_sum(part[k], s_sum);                 // 1 .. 4 candidates by s, 5 .. 7 stages
-    for (int c = 1; c < 6; ++c) out[7 + c] = block_sum(part[kStats - 1 + c], s_sum);             // 8 .. 12 faces by state 1 .. 5
-    out[13] = block_sum(part[kStats - 1], s_sum);                                                // usable faces
+    out[0] = n_emit[0];
+    for (int k = 0; k < kStats - 1; ++k) out[1 + k] = block_sum(part[k]);                        // 1 .. 4 candidates by s, 5 .. 7 stages
+    for (int c = 1; c < 6; ++c) out[7 + c] = block_sum(part[kStats - 1 + c]);                    // 8 .. 12 faces by state 1 .. 5
+    out[13] = block_sum(part[kStats - 1]);                                                       // usable faces
     if (tid == 0)
         for (int k = 0; k < kTotals; ++k) totals[k] = out[k];
 }

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "orient_passes.hpp"
 #include "radix_sort.hpp"
@@ -30,61 +31,10 @@ constexpr uint32_t kOrBlock = 1024;                     // block of the partial 
 constexpr uint32_t kOrSpan = 256;                       // workgroup that adds the per-block partials of a run across blocks
 constexpr uint32_t kOrBadOrder = 4u;                    // status: a sort order or a run start outside its range
 
-typedef unsigned long long ull;
+using scan::ull;
 
 __host__ __device__ inline uint64_t or_align(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 __host__ __device__ inline uint64_t or_blocks(uint64_t n) { return (n + kOrBlock - 1) / kOrBlock; }
-
-// sums N per-lane flags over the block (1024 lanes); the sums are returned in out[] to thread 0 only
-template <int N>
-__device__ __forceinline__ void or_block_counts(const bool (&flag)[N], uint32_t (&out)[N]) {
-    __shared__ uint32_t ws[N][16];
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const ull b = __ballot(flag[k]);
-        if (lane == 0) ws[k][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        uint32_t s = 0;
-        if (t == 0)
-            for (int j = 0; j < 16; ++j) s += ws[k][j];
-        out[k] = s;
-    }
-}
-
-// one workgroup: N - 1 columns of per-block counts added and one column of status words or-ed, into totals[0, N)
-template <int N>
-__device__ __forceinline__ void or_totals(const uint32_t* __restrict__ part, uint32_t nb, uint32_t extra_status, ull* __restrict__ totals) {
-    __shared__ ull acc[N][kOrBlock];
-    const uint32_t t = threadIdx.x;
-    ull s[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = 0;
-    for (uint32_t b = t; b < nb; b += kOrBlock) {
-#pragma unroll
-        for (int k = 0; k < N - 1; ++k) s[k] += part[(ull)N * b + k];
-        s[N - 1] |= part[(ull)N * b + N - 1];
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc[k][t] = s[k];
-    __syncthreads();
-    for (uint32_t o = kOrBlock / 2; o > 0; o >>= 1) {
-        if (t < o) {
-#pragma unroll
-            for (int k = 0; k < N - 1; ++k) acc[k][t] += acc[k][t + o];
-            acc[N - 1][t] |= acc[N - 1][t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-#pragma unroll
-        for (int k = 0; k < N - 1; ++k) totals[k] = acc[k][0];
-        totals[N - 1] = acc[N - 1][0] | extra_status;
-    }
-}
 
 // ---- consistent winding ---------------------------------------------------------------------------------------------------------------
 
@@ -116,8 +66,7 @@ __global__ __launch_bounds__(256) void k_or_unite(OrientWork w, uint32_t F, cons
                                                   const int32_t* __restrict__ edge_start, const int32_t* __restrict__ edge_halfedges,
                                                   const ull* __restrict__ edge_totals) {
     const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-    const ull E64 = edge_totals[0];
-    const uint32_t E = E64 < 3ull * F ? (uint32_t)E64 : 3u * F;
+    const uint32_t E = scan::capped(edge_totals[0], 3u * F);
     uint32_t status = 0;
     orient_pass_join(w.parent, F, faces, edge_start, edge_halfedges, e, E, &status);
     if (status) atomicOr(w.status, status);             // (the union-find's own cap report)
@@ -140,8 +89,8 @@ __global__ __launch_bounds__(kOrBlock) void k_or_label(OrientWork w, uint32_t F,
         flag[2] = fl != 0;
         flag[3] = status != 0;
     }
-    uint32_t out[4];
-    or_block_counts<4>(flag, out);
+    uint32_t pre[4], out[4];
+    scan::flag_scan<4, kOrBlock>(flag, pre, out);
     if (threadIdx.x == 0) {
         w.part[4ull * blockIdx.x] = out[0];
         w.part[4ull * blockIdx.x + 1] = out[1];
@@ -151,7 +100,13 @@ __global__ __launch_bounds__(kOrBlock) void k_or_label(OrientWork w, uint32_t F,
 }
 
 __global__ __launch_bounds__(kOrBlock) void k_or_totals(OrientWork w, uint32_t nbf, ull* __restrict__ totals) {
-    or_totals<4>(w.part, nbf, *w.status, totals);
+    ull t[4];
+    scan::block_totals<3, 1, kOrBlock>(w.part, nbf, t);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) totals[k] = t[k];
+        totals[3] = t[3] | *w.status;
+    }
 }
 
 // ---- outward by volume ----------------------------------------------------------------------------------------------------------------
@@ -372,8 +327,8 @@ __global__ __launch_bounds__(kOrBlock) void k_ov_apply(VolumeWork w, uint32_t F,
         flag[2] = l == f && (c & 4);
         flag[3] = out != 0;
     }
-    uint32_t out[5];
-    or_block_counts<5>(flag, out);
+    uint32_t pre[5], out[5];
+    scan::flag_scan<5, kOrBlock>(flag, pre, out);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) w.part[5ull * blockIdx.x + k] = out[k];
@@ -382,7 +337,12 @@ __global__ __launch_bounds__(kOrBlock) void k_ov_apply(VolumeWork w, uint32_t F,
 }
 
 __global__ __launch_bounds__(kOrBlock) void k_ov_totals(VolumeWork w, uint32_t nbf, ull* __restrict__ totals) {
-    or_totals<5>(w.part, nbf, 0u, totals);
+    ull t[5];
+    scan::block_totals<4, 1, kOrBlock>(w.part, nbf, t);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) totals[k] = t[k];
+    }
 }
 
 }  // namespace nsa

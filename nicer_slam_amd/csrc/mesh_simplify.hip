@@ -14,11 +14,12 @@
 // fixed order and the result is bit-reproducible.
 //
 // Counts are per-wave popcounts added with integer atomics (sums of integers: any order gives the same); no floating-point atomic
-// exists in this file.
+// exists in this file.  The three scans are block_scan.hpp's: flag_scan inside a block of kMsBlock, k_offsets over the block counts.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "radix_sort.hpp"
 
@@ -31,7 +32,7 @@ constexpr uint32_t kMsBlock = 1024;                     // block of the scans
 constexpr uint64_t kMsNoKey = ~0ull;                    // a vertex that is not in the grid
 constexpr uint32_t kMsBadOrder = 1u;                    // status: a sort order named an element outside its range
 
-typedef unsigned long long ull;
+using scan::ull;
 
 enum { kTotK = 0, kTotContrib, kTotUsed, kTotOutside, kTotCollapsed, kTotDuplicate, kTotVerts, kTotFaces, kTotStatus, kTotWords };
 
@@ -131,23 +132,6 @@ __device__ __forceinline__ void ms_count(ull* dst, bool flag) {
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(dst, (ull)__popcll(b));
 }
 
-// the flags of a block of kMsBlock lanes: this lane's exclusive prefix, and the block's sum
-__device__ __forceinline__ uint32_t ms_block_scan(bool flag, uint32_t* total) {
-    __shared__ uint32_t wc[16];
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const ull b = __ballot(flag);
-    if (lane == 0) wc[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) {
-        pre += k < wave ? wc[k] : 0u;
-        tot += wc[k];
-    }
-    *total = tot;
-    return pre + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-}
-
 // the cell of vertex v: 0 in the grid (c filled), 1 finite but outside, 2 a non-finite coordinate
 __device__ __forceinline__ int ms_cell(const float* __restrict__ verts, uint32_t v, const MsGrid& g, uint32_t (&c)[3]) {
 #pragma clang fp contract(off)
@@ -179,35 +163,8 @@ __global__ void k_ms_zero(ull* __restrict__ totals) {
 __global__ __launch_bounds__(kMsBlock) void k_ms_scan_count(const uint32_t* __restrict__ flag, uint32_t N, uint32_t* __restrict__ bcount) {
     const uint32_t i = blockIdx.x * kMsBlock + threadIdx.x;
     uint32_t tot;
-    ms_block_scan(i < N && flag[i] != 0, &tot);
+    scan::flag_scan<kMsBlock>(i < N && flag[i] != 0, tot);
     if (threadIdx.x == 0) bcount[blockIdx.x] = tot;
-}
-
-// one workgroup: bcount[0, nb) -> its exclusive scan; the grand total (integers: any association gives the same)
-__global__ __launch_bounds__(kMsBlock) void k_ms_scan_offsets(uint32_t* __restrict__ bcount, uint32_t nb, ull* __restrict__ total) {
-    __shared__ uint32_t part[kMsBlock];
-    const uint32_t t = threadIdx.x, per = (nb + kMsBlock - 1) / kMsBlock;
-    const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += bcount[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t c = 0;
-        for (uint32_t k = 0; k < kMsBlock; ++k) {
-            const uint32_t x = part[k];
-            part[k] = c;
-            c += x;
-        }
-        *total = c;
-    }
-    __syncthreads();
-    uint32_t c = part[t];
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t x = bcount[i];
-        bcount[i] = c;
-        c += x;
-    }
 }
 
 // ---- clusters: keys, used marks, the two-word sort, numbers --------------------------------------------------------------------------------
@@ -283,7 +240,7 @@ __global__ __launch_bounds__(kMsBlock) void k_ms_vrank(uint32_t V, ClusterWork w
     const uint32_t i = blockIdx.x * kMsBlock + threadIdx.x;
     const bool head = i < V && w.flag[i] != 0;
     uint32_t tot;
-    const uint32_t pre = ms_block_scan(head, &tot);
+    const uint32_t pre = scan::flag_scan<kMsBlock>(head, tot);
     if (i >= V) return;
     const uint32_t v = w.oc[i];
     if (v >= V) return;                                  // (never; reported by k_ms_vsort)
@@ -364,7 +321,7 @@ __global__ __launch_bounds__(kMsBlock) void k_ms_fcompact(uint32_t F, uint32_t V
     const uint32_t f = blockIdx.x * kMsBlock + threadIdx.x;
     const bool keep = f < F && w.flag[f] != 0;
     uint32_t tot;
-    const uint32_t o = w.bcount[blockIdx.x] + ms_block_scan(keep, &tot);
+    const uint32_t o = w.bcount[blockIdx.x] + scan::flag_scan<kMsBlock>(keep, tot);
     if (!keep || o >= F) return;
     face_origin[o] = (int32_t)f;
 #pragma unroll
@@ -380,7 +337,7 @@ __global__ __launch_bounds__(kMsBlock) void k_ms_crank(uint32_t V, ClusterWork w
     const uint32_t k = blockIdx.x * kMsBlock + threadIdx.x;
     const bool named = k < V && w.cmark[k] != 0;
     uint32_t tot;
-    const uint32_t o = w.bcount[blockIdx.x] + ms_block_scan(named, &tot);
+    const uint32_t o = w.bcount[blockIdx.x] + scan::flag_scan<kMsBlock>(named, tot);
     if (k >= V) return;
     cluster_vertex[k] = named ? (int32_t)o : -1;
     if (named && o < V) out_cluster[o] = (int32_t)k;
@@ -572,6 +529,8 @@ __global__ __launch_bounds__(256) void k_mp_place(PlaceArgs a, MsGrid g, PlaceWo
     }
 }
 
+constexpr auto k_ms_offsets = scan::k_offsets<1, uint32_t, kMsBlock>;
+
 static bool ms_grid(const double* origin, double h, uint32_t n_cells, MsGrid* g) {
     if (!origin || !std::isfinite(h) || !(h > 0.0) || n_cells == 0 || n_cells > kMsMaxCells) return false;
     for (int k = 0; k < 3; ++k) {
@@ -622,7 +581,7 @@ int nsa_mesh_cluster(const float* verts, uint32_t n_verts, const int32_t* faces,
     radix_argsort(w.keys, w.tmp, w.ob, w.counts, V, 0, passes_hi, stream);
     hipLaunchKernelGGL(k_ms_vsort, dim3(gv), dim3(256), 0, s, V, w, tot);
     hipLaunchKernelGGL(k_ms_scan_count, dim3(nbv), dim3(kMsBlock), 0, s, w.flag, V, w.bcount);
-    hipLaunchKernelGGL(k_ms_scan_offsets, dim3(1), dim3(kMsBlock), 0, s, w.bcount, nbv, tot + kTotK);
+    hipLaunchKernelGGL(k_ms_offsets, dim3(1), dim3(kMsBlock), 0, s, (const uint32_t*)w.bcount, w.bcount, nbv, tot + kTotK);
     hipLaunchKernelGGL(k_ms_vrank, dim3(nbv), dim3(kMsBlock), 0, s, V, w, vertex_cluster);
     hipLaunchKernelGGL(k_ms_triple, dim3(gf), dim3(256), 0, s, faces, F, V, w, vertex_cluster, tot);
     radix_argsort(w.keys, w.tmp, w.oa, w.counts, F, 0, passes_c, stream);
@@ -632,10 +591,10 @@ int nsa_mesh_cluster(const float* verts, uint32_t n_verts, const int32_t* faces,
     radix_argsort(w.keys, w.tmp, w.oc, w.counts, F, 0, passes_c, stream);
     hipLaunchKernelGGL(k_ms_fsort, dim3(gf), dim3(256), 0, s, F, V, w, tot);
     hipLaunchKernelGGL(k_ms_scan_count, dim3(nbf), dim3(kMsBlock), 0, s, w.flag, F, w.bcount);
-    hipLaunchKernelGGL(k_ms_scan_offsets, dim3(1), dim3(kMsBlock), 0, s, w.bcount, nbf, tot + kTotFaces);
+    hipLaunchKernelGGL(k_ms_offsets, dim3(1), dim3(kMsBlock), 0, s, (const uint32_t*)w.bcount, w.bcount, nbf, tot + kTotFaces);
     hipLaunchKernelGGL(k_ms_fcompact, dim3(nbf), dim3(kMsBlock), 0, s, F, V, w, out_faces, face_origin);
     hipLaunchKernelGGL(k_ms_scan_count, dim3(nbv), dim3(kMsBlock), 0, s, w.cmark, V, w.bcount);
-    hipLaunchKernelGGL(k_ms_scan_offsets, dim3(1), dim3(kMsBlock), 0, s, w.bcount, nbv, tot + kTotVerts);
+    hipLaunchKernelGGL(k_ms_offsets, dim3(1), dim3(kMsBlock), 0, s, (const uint32_t*)w.bcount, w.bcount, nbv, tot + kTotVerts);
     hipLaunchKernelGGL(k_ms_crank, dim3(nbv), dim3(kMsBlock), 0, s, V, w, cluster_vertex, out_cluster);
     hipLaunchKernelGGL(k_ms_remap, dim3(gf), dim3(256), 0, s, F, V, tot, cluster_vertex, out_faces);
     return launch_end();

@@ -5,9 +5,9 @@
 // Edge table: one key per half-edge h = 3f + k, (lo, hi) of its two vertices, V for both when the face does not contribute.  The
 // 64-bit order lo << 32 | hi is two stable radix argsorts (radix_sort.hpp), hi then lo, each with only the 8-bit passes V needs; the
 // second sorts positions of the first, so the half-edges of an edge stay in ascending id.  Run heads come from comparing neighbours
-// in the sorted order, edge ids and forward counts from one exclusive scan of (head, forward) flags (block counts, a scan of the
-// block counts, ballots inside a block), counts from the difference of consecutive run starts.  Every total is a sum of per-block
-// partial counts added by one workgroup: integers throughout, no floating point, and no atomics except inside the union-find.
+// in the sorted order, edge ids and forward counts from one exclusive scan of (head, forward) flags, counts from the difference of
+// consecutive run starts.  Every total is a sum of per-block partial counts added by one workgroup.  The scan, the counts and the
+// totals are block_scan.hpp's: integers throughout, no floating point, and no atomics except inside the union-find.
 //
 // Boundary loops: the vertex union-find of uf_passes.hpp with the boundary edges in place of faces; a loop is a root that some
 // boundary edge marked.  Face components: the same uf_find / uf_unite with faces as nodes -- every half-edge of a run after the
@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/nicer_slam_amd.h"
+#include "block_scan.hpp"
 #include "grid_common.hpp"
 #include "radix_sort.hpp"
 #include "topo_passes.hpp"
@@ -29,7 +30,7 @@ constexpr uint32_t kTopoMaxFaces = 0x7FFFFFFFu / 3u;    // H = 3 F < 2^31
 constexpr uint32_t kTopoBlock = 1024;                   // block of the scans and of the partial counts
 constexpr uint32_t kFwdBit = 0x80000000u;               // in the sorted hi word: the half-edge runs lo -> hi
 
-typedef unsigned long long ull;
+using scan::ull;
 
 __host__ __device__ inline uint64_t topo_align(uint64_t b) { return (b + 255) & ~uint64_t(255); }
 __host__ __device__ inline uint64_t topo_blocks(uint64_t n) { return (n + kTopoBlock - 1) / kTopoBlock; }
@@ -161,77 +162,25 @@ __device__ __forceinline__ bool te_head(const EdgeWork& w, uint32_t i, uint32_t 
     return w.keys[0][i - 1] != lo || ((w.keys[1][i - 1] ^ w.keys[1][i]) & ~kFwdBit) != 0;
 }
 
-// the (head, forward) flags of this lane summed over the block: per-wave counts in LDS, returns this lane's exclusive prefixes
-__device__ __forceinline__ void te_block_scan(bool head, bool fwd, uint32_t* pre_head, uint32_t* pre_fwd, uint32_t* tot_head,
-                                              uint32_t* tot_fwd) {
-    __shared__ uint32_t wh[16], wf[16];
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const ull bh = __ballot(head), bf = __ballot(fwd);
-    if (lane == 0) {
-        wh[wave] = (uint32_t)__popcll(bh);
-        wf[wave] = (uint32_t)__popcll(bf);
-    }
-    __syncthreads();
-    uint32_t ph = 0, pf = 0, th = 0, tf = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) {
-        ph += k < wave ? wh[k] : 0u;
-        pf += k < wave ? wf[k] : 0u;
-        th += wh[k];
-        tf += wf[k];
-    }
-    const ull below = (1ull << lane) - 1ull;
-    *pre_head = ph + (uint32_t)__popcll(bh & below);
-    *pre_fwd = pf + (uint32_t)__popcll(bf & below);
-    *tot_head = th;
-    *tot_fwd = tf;
-}
-
 __global__ __launch_bounds__(kTopoBlock) void k_te_count(EdgeWork w, uint32_t H, uint32_t V) {
     const uint32_t i = blockIdx.x * kTopoBlock + threadIdx.x;
     const bool in = i < H;
-    const bool head = in && te_head(w, i, V), fwd = in && te_contrib(w, i, V) && (w.keys[1][i] & kFwdBit);
-    uint32_t ph, pf, th, tf;
-    te_block_scan(head, fwd, &ph, &pf, &th, &tf);
+    const bool flag[2] = {in && te_head(w, i, V), in && te_contrib(w, i, V) && (w.keys[1][i] & kFwdBit)};      // head, forward
+    uint32_t pre[2], total[2];
+    scan::flag_scan<2, kTopoBlock>(flag, pre, total);
     if (threadIdx.x == 0) {
-        w.bcount[2ull * blockIdx.x] = th;
-        w.bcount[2ull * blockIdx.x + 1] = tf;
+        w.bcount[2ull * blockIdx.x] = total[0];
+        w.bcount[2ull * blockIdx.x + 1] = total[1];
     }
 }
 
-// one workgroup: bcount[0, nb) pairs -> their exclusive scans; the two grand totals (integers: any association gives the same)
-__global__ __launch_bounds__(kTopoBlock) void k_te_offsets(EdgeWork w, uint32_t nb, ull* __restrict__ totals) {
-    __shared__ uint32_t part[2][kTopoBlock];
-    const uint32_t t = threadIdx.x, per = (nb + kTopoBlock - 1) / kTopoBlock;
-    const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
-    uint32_t s0 = 0, s1 = 0;
-    for (uint32_t i = lo; i < hi; ++i) {
-        s0 += w.bcount[2ull * i];
-        s1 += w.bcount[2ull * i + 1];
-    }
-    part[0][t] = s0;
-    part[1][t] = s1;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t c0 = 0, c1 = 0;
-        for (uint32_t k = 0; k < kTopoBlock; ++k) {
-            const uint32_t x0 = part[0][k], x1 = part[1][k];
-            part[0][k] = c0;
-            part[1][k] = c1;
-            c0 += x0;
-            c1 += x1;
-        }
-        totals[0] = c0;                                   // E
-        *w.fwd_total = c1;
-    }
-    __syncthreads();
-    uint32_t c0 = part[0][t], c1 = part[1][t];
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t x0 = w.bcount[2ull * i], x1 = w.bcount[2ull * i + 1];
-        w.bcount[2ull * i] = c0;
-        w.bcount[2ull * i + 1] = c1;
-        c0 += x0;
-        c1 += x1;
+// one workgroup: bcount[0, nb) pairs -> their exclusive scans; the two grand totals
+__global__ __launch_bounds__(kTopoBlock) void k_te_scan(EdgeWork w, uint32_t nb, ull* __restrict__ totals) {
+    uint32_t total[2];
+    scan::offsets<2, uint32_t, kTopoBlock>(w.bcount, w.bcount, nb, total);
+    if (threadIdx.x == 0) {
+        totals[0] = total[0];                             // E
+        *w.fwd_total = total[1];
     }
 }
 
@@ -243,9 +192,10 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_rank(EdgeWork w, uint32_t H, 
     const uint32_t i = blockIdx.x * kTopoBlock + threadIdx.x;
     const bool in = i < H;
     const bool contrib = in && te_contrib(w, i, V);
-    const bool head = in && te_head(w, i, V), fwd = contrib && (w.keys[1][i] & kFwdBit);
-    uint32_t ph, pf, th, tf;
-    te_block_scan(head, fwd, &ph, &pf, &th, &tf);
+    const bool head = in && te_head(w, i, V);
+    const bool flag[2] = {head, contrib && (w.keys[1][i] & kFwdBit)};
+    uint32_t pre[2], total[2];
+    scan::flag_scan<2, kTopoBlock>(flag, pre, total);
     if (!in) return;
     const uint32_t E = (uint32_t)totals[0];
     // the end of the contributing half-edges: the first position that does not contribute, or H
@@ -259,7 +209,7 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_rank(EdgeWork w, uint32_t H, 
         totals[1] = Hc / 3u;                              // F_c
     }
     if (!contrib) return;
-    const uint32_t e = w.bcount[2ull * blockIdx.x] + ph + (head ? 1u : 0u) - 1u;
+    const uint32_t e = w.bcount[2ull * blockIdx.x] + pre[0] + (head ? 1u : 0u) - 1u;
     if (e >= H) return;                                   // (never: a contributing position has a head at or before it)
     const int32_t h = edge_halfedges[i];
     if (h >= 0 && (uint32_t)h < H) face_edges[h] = (int32_t)e;
@@ -267,31 +217,11 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_rank(EdgeWork w, uint32_t H, 
         edges[2ull * e] = (int32_t)w.keys[0][i];
         edges[2ull * e + 1] = (int32_t)(w.keys[1][i] & ~kFwdBit);
         edge_start[e] = (int32_t)i;
-        w.tmp[e] = w.bcount[2ull * blockIdx.x + 1] + pf;
+        w.tmp[e] = w.bcount[2ull * blockIdx.x + 1] + pre[1];
     }
 }
 
 // ---- classes, boundary loops, totals ------------------------------------------------------------------------------------------------
-
-// sums N per-lane flags over the block; the sums are returned in out[] to thread 0 only
-template <int N>
-__device__ __forceinline__ void te_block_counts(const bool (&flag)[N], uint32_t (&out)[N]) {
-    __shared__ uint32_t ws[N][16];
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const ull b = __ballot(flag[k]);
-        if (lane == 0) ws[k][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        uint32_t s = 0;
-        if (t == 0)
-            for (int j = 0; j < 16; ++j) s += ws[k][j];
-        out[k] = s;
-    }
-}
 
 // one lane per edge: count and forward count from the offsets of its run and of the next; a boundary edge marks and joins its ends
 __global__ __launch_bounds__(kTopoBlock) void k_te_classify(EdgeWork w, uint32_t H, uint32_t V, const ull* __restrict__ totals,
@@ -312,8 +242,8 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_classify(EdgeWork w, uint32_t
     }
     flag[3] = (status & kUfCapFind) != 0;
     flag[4] = (status & kUfCapHook) != 0;
-    uint32_t out[5];
-    te_block_counts<5>(flag, out);
+    uint32_t pre[5], out[5];
+    scan::flag_scan<5, kTopoBlock>(flag, pre, out);
     if (threadIdx.x == 0) {
         w.part_e[4ull * blockIdx.x] = out[0];
         w.part_e[4ull * blockIdx.x + 1] = out[1];
@@ -330,8 +260,8 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_verts(EdgeWork w, uint32_t V)
         flag[0] = w.used[v] != 0;
         flag[1] = w.bmark[v] == 0 && w.parent[v] == (int32_t)v;
     }
-    uint32_t out[2];
-    te_block_counts<2>(flag, out);
+    uint32_t pre[2], out[2];
+    scan::flag_scan<2, kTopoBlock>(flag, pre, out);
     if (threadIdx.x == 0) {
         w.part_v[2ull * blockIdx.x] = out[0];
         w.part_v[2ull * blockIdx.x + 1] = out[1];
@@ -340,37 +270,16 @@ __global__ __launch_bounds__(kTopoBlock) void k_te_verts(EdgeWork w, uint32_t V)
 
 // one workgroup: the partial counts of every block, added
 __global__ __launch_bounds__(kTopoBlock) void k_te_totals(EdgeWork w, uint32_t nbe, uint32_t nbv, ull* __restrict__ totals) {
-    __shared__ ull acc[6][kTopoBlock];
-    const uint32_t t = threadIdx.x;
-    ull s[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t b = t; b < nbe; b += kTopoBlock) {
-        s[0] += w.part_e[4ull * b];
-        s[1] += w.part_e[4ull * b + 1];
-        s[2] += w.part_e[4ull * b + 2];
-        s[5] |= w.part_e[4ull * b + 3];
-    }
-    for (uint32_t b = t; b < nbv; b += kTopoBlock) {
-        s[3] += w.part_v[2ull * b];
-        s[4] += w.part_v[2ull * b + 1];
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k][t] = s[k];
-    __syncthreads();
-    for (uint32_t o = kTopoBlock / 2; o > 0; o >>= 1) {
-        if (t < o) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) acc[k][t] += acc[k][t + o];
-            acc[5][t] |= acc[5][t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        totals[2] = acc[3][0];                            // used vertices
-        totals[3] = acc[0][0];                            // boundary edges
-        totals[4] = acc[1][0];                            // non-manifold edges
-        totals[5] = acc[2][0];                            // inconsistent edges
-        totals[6] = acc[4][0];                            // boundary loops
-        totals[7] = acc[5][0];                            // status
+    ull e[4], v[2];
+    scan::block_totals<3, 1, kTopoBlock>(w.part_e, nbe, e);
+    scan::block_totals<2, 0, kTopoBlock>(w.part_v, nbv, v);
+    if (threadIdx.x == 0) {
+        totals[2] = v[0];                                 // used vertices
+        totals[3] = e[0];                                 // boundary edges
+        totals[4] = e[1];                                 // non-manifold edges
+        totals[5] = e[2];                                 // inconsistent edges
+        totals[6] = v[1];                                 // boundary loops
+        totals[7] = e[3];                                 // status
     }
 }
 
@@ -419,8 +328,8 @@ __global__ __launch_bounds__(kTopoBlock) void k_fc_label(FaceWork w, uint32_t F,
         flag[0] = l == (int32_t)f;
         flag[1] = (status & kUfCapFind) != 0;
     }
-    uint32_t out[2];
-    te_block_counts<2>(flag, out);
+    uint32_t pre[2], out[2];
+    scan::flag_scan<2, kTopoBlock>(flag, pre, out);
     if (threadIdx.x == 0) {
         w.part[2ull * blockIdx.x] = out[0];
         w.part[2ull * blockIdx.x + 1] = out[1] ? kUfCapFind : 0u;
@@ -428,26 +337,11 @@ __global__ __launch_bounds__(kTopoBlock) void k_fc_label(FaceWork w, uint32_t F,
 }
 
 __global__ __launch_bounds__(kTopoBlock) void k_fc_totals(FaceWork w, uint32_t nbf, ull* __restrict__ totals) {
-    __shared__ ull acc[2][kTopoBlock];
-    const uint32_t t = threadIdx.x;
-    ull s0 = 0, s1 = 0;
-    for (uint32_t b = t; b < nbf; b += kTopoBlock) {
-        s0 += w.part[2ull * b];
-        s1 |= w.part[2ull * b + 1];
-    }
-    acc[0][t] = s0;
-    acc[1][t] = s1;
-    __syncthreads();
-    for (uint32_t o = kTopoBlock / 2; o > 0; o >>= 1) {
-        if (t < o) {
-            acc[0][t] += acc[0][t + o];
-            acc[1][t] |= acc[1][t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        totals[0] = acc[0][0];
-        totals[1] = acc[1][0] | *w.status;
+    ull t[2];
+    scan::block_totals<1, 1, kTopoBlock>(w.part, nbf, t);
+    if (threadIdx.x == 0) {
+        totals[0] = t[0];
+        totals[1] = t[1] | *w.status;
     }
 }
 
@@ -485,7 +379,7 @@ int nsa_mesh_edges(const int32_t* faces, uint32_t n_faces, uint32_t n_verts, con
     radix_argsort(w.keys, w.tmp, w.order2, w.counts, H, 0, passes, stream);
     hipLaunchKernelGGL(k_te_gather, dim3((H + 255) / 256), dim3(256), 0, s, faces, face_mask, H, V, w, edge_halfedges, face_edges);
     hipLaunchKernelGGL(k_te_count, dim3(nbh), dim3(kTopoBlock), 0, s, w, H, V);
-    hipLaunchKernelGGL(k_te_offsets, dim3(1), dim3(kTopoBlock), 0, s, w, nbh, tot);
+    hipLaunchKernelGGL(k_te_scan, dim3(1), dim3(kTopoBlock), 0, s, w, nbh, tot);
     hipLaunchKernelGGL(k_te_rank, dim3(nbh), dim3(kTopoBlock), 0, s, w, H, V, edge_halfedges, edges, edge_start, face_edges, tot);
     hipLaunchKernelGGL(k_te_classify, dim3(nbh), dim3(kTopoBlock), 0, s, w, H, V, tot, edges, edge_start, edge_count, edge_forward);
     if (V) hipLaunchKernelGGL(k_te_verts, dim3(nbv), dim3(kTopoBlock), 0, s, w, V);

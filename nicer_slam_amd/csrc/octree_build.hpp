@@ -24,6 +24,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
+#include "block_scan.hpp"
 #include "tri_common.hpp"
 #define NSA_OCTREE_FN __host__ __device__ inline
 #else
@@ -188,30 +189,12 @@ __global__ __launch_bounds__(256) void k_heads(const float* __restrict__ v, uint
     t.base[i] = n;
 }
 
-// one workgroup of 1024: base[0 .. F] becomes its exclusive prefix sum; the total is the node count
+// one workgroup of 1024: base[0 .. F] becomes its exclusive prefix sum (block_scan.hpp); the total is the node count
 template <typename Tree>
 __global__ __launch_bounds__(1024) void k_scan(uint32_t F, Tree t) {
-    __shared__ uint32_t s_sum[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n = (uint64_t)F + 1, chunk = (n + 1023) / 1024;
-    const uint64_t lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += t.base[i];
-    s_sum[tid] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {                // Hillis-Steele, inclusive
-        const uint32_t add = tid >= off ? s_sum[tid - off] : 0;
-        __syncthreads();
-        s_sum[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = s_sum[tid] - sum;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const uint32_t x = t.base[i];
-        t.base[i] = run;
-        run += x;
-    }
-    if (tid == 1023) t.head->n_nodes = s_sum[1023];
+    uint32_t total[1];
+    scan::offsets<1, uint32_t, 1024>(t.base, t.base, (uint64_t)F + 1, total);
+    if (threadIdx.x == 1023) t.head->n_nodes = total[0];
 }
 
 // one lane per sorted position: the nodes that begin there, their ranges and skip indices

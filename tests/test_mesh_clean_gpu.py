@@ -162,6 +162,30 @@ def test_stats_on_index_orders_and_nonfinite_vertices():
         _check_stats(v, f)
 
 
+@pytest.mark.parametrize("n,V", [(341, 1023), (341, 1024), (342, 1026), (349526, 1048578)])
+def test_stats_soup_at_the_seams_of_the_rank_scan(n, V):
+    """a soup of n disjoint triangles, triangle r on the vertices 3 r, 3 r + 1, 3 r + 2: V just below, at (one vertex unused) and just
+    above the 1024 lanes of a block of the rank scan (csrc/block_scan.hpp), and V = 1 048 578 > 1024 * 1024, where a lane of the one
+    workgroup that scans the block counts owns more than one block.  In closed form: n components, label[r] = 3 r, three vertices
+    and one face each"""
+    from nicer_slam_amd.mesh_clean import component_stats
+    r = torch.arange(n, device="cuda")
+    f = (3 * r[:, None] + torch.arange(3, device="cuda")).to(torch.int32)
+    v = torch.zeros(V, 3, device="cuda")
+    v[:3 * n, 0] = r.repeat_interleave(3).float()
+    v[1:3 * n:3, 0] += 0.5
+    v[2:3 * n:3, 1] = 0.5
+    st = component_stats(v, f)
+    assert st["n_components"] == n
+    r32 = r.to(torch.int32)
+    assert torch.equal(st["label"], 3 * r32) and torch.equal(st["face_comp"], r32)
+    assert torch.equal(st["vertex_comp"][:3 * n], r32.repeat_interleave(3)) and bool((st["vertex_comp"][3 * n:] == -1).all())
+    assert bool((st["n_verts"] == 3).all()) and bool((st["n_faces"] == 1).all())
+    assert bool(((st["area"] - 0.125).abs() <= 0.125 * 2.0 ** -50).all())      # 1/8 each, exactly representable inputs
+    lo = torch.stack([r.float(), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")], 1)
+    assert torch.equal(st["lo"], lo) and torch.equal(st["hi"], lo + torch.tensor([0.5, 0.5, 0.0], device="cuda"))
+
+
 def test_stats_area_agrees_with_the_surface_sampler_total():
     from nicer_slam_amd._native import lib, check
     from test_mesh_eval_gpu import _blob_mesh

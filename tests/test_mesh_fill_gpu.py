@@ -96,6 +96,35 @@ def test_a_loop_over_several_blocks(skip_folded):
     assert rep["rank"].max() == 5001 and len(got["faces"]) == (5000 if skip_folded else 5000 + 5002 * (2 * rep["rings"][0] - 1))
 
 
+@pytest.mark.parametrize("method", ["polar", "min_area"])
+def test_a_scan_over_more_blocks_than_the_offsets_workgroup_has_lanes(method):
+    """a flat 128 x 128 quad sheet (topology_ref.quad_sheet) without the quads (4 a + 1, 4 b + 1), a, b < 32: 3 F = 92 160 half-edges are
+    360 scan blocks of 256 for the 256 lanes of the one workgroup that scans the block sums (csrc/block_scan.hpp), so a lane owns two
+    blocks.  In closed form: 1024 loops of four edges and the outer loop of 512, which max_edges leaves open; a polar patch of a
+    square is four faces about a new vertex, a minimum-area patch two faces and no vertex, and either gives back a sheet with
+    the edges of the full one and one boundary loop"""
+    from nicer_slam_amd import mesh_fill as M, mesh_topology
+    a = 128
+    f, V = T.quad_sheet(a, a)
+    quad = torch.arange(a * a, device="cuda")
+    hole = ((quad // a) % 4 == 1) & ((quad % a) % 4 == 1)
+    f = f.reshape(a * a, 2, 3)[~hole].reshape(-1, 3).contiguous()
+    k, F = int(hole.sum()), f.shape[0]
+    assert k == 1024 and 3 * F == 92160 > 256 * 256
+    i = torch.arange(V, device="cuda")
+    v = torch.stack([i // (a + 1), i % (a + 1), torch.zeros_like(i)], 1).float()
+    got, rep = M.fill_holes(dict(verts=v, faces=f), max_edges=4, method=method, return_report=True)
+    assert sorted(rep["n"]) == [4] * k + [4 * a] and rep["totals"]["n_too_many_edges"] == 1 and rep["totals"]["n_filled"] == k
+    per_hole = 4 if method == "polar" else 2
+    assert torch.equal(got["faces"][:F], f) and got["faces"].shape[0] == F + per_hole * k
+    assert got["verts"].shape[0] == V + (k if method == "polar" else 0)
+    if method == "min_area":
+        assert rep["area_class"].count("area_filled") == k and rep["area_totals"]["n_area_filled"] == k
+    t = mesh_topology.edge_table(got["faces"], got["verts"].shape[0])
+    E = 3 * a * a + 2 * a + (3 * k if method == "polar" else 0)          # a polar patch: four spokes for one diagonal
+    assert [t[key] for key in ("n_edges", "n_boundary", "n_nonmanifold", "n_inconsistent", "n_boundary_loops")] == [E, 4 * a, 0, 0, 1]
+
+
 def _grid65(both_diagonals):
     cells = [(4 * a + 1, 4 * b + 1) for a in range(16) for b in range(16)]
     if both_diagonals:

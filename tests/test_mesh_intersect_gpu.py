@@ -104,6 +104,18 @@ def test_face_counts(n):
     _check(f"count {n}")
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025])
+def test_face_counts_at_the_seams_of_the_scans(n):
+    """F just below, at and just above the 1024 lanes of the one workgroup that scans the tree's node counts (F + 1 items) and the
+    records per face (F items; csrc/block_scan.hpp): the walk over the tree against the on-device brute force, byte for byte"""
+    mesh = R.random_soup(n, 21)
+    pairs, code, flags, rep = _run(mesh)
+    brute = _run(mesh, brute=True)
+    assert rep["n_candidates"] > n and len(pairs) > 100 and len(np.unique(pairs, axis=0)) == len(pairs)
+    assert (pairs[:, 0] < pairs[:, 1]).all() and pairs.min() >= 0 and pairs.max() < n and (code != 0).all()
+    assert all(x.tobytes() == y.tobytes() for x, y in zip((pairs, code, flags), brute[:3])) and brute[3] == rep
+
+
 def test_between():
     mesh, _ = _case("lattice")
     mask = np.arange(len(mesh["faces"])) % 3 == 0

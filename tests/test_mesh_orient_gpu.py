@@ -152,6 +152,25 @@ def test_strip_across_workgroups():
     assert got["n_components"] == 1 and got["n_nonorientable"] == 0
 
 
+@pytest.mark.parametrize("a,b", [(7, 73), (16, 32), (19, 27), (419, 419)])
+def test_sheets_at_the_seams_of_the_counts(a, b):
+    """a consistently wound a x b quad sheet (topology_ref.quad_sheet) of F = 1022, 1024, 1026 faces -- just below, at and just above
+    the 1024 lanes of a block of the per-block counts -- and of F = 351 122, 343 blocks for the one workgroup that adds them: one
+    orientable component, nothing flipped; flat and open, so the volume rule decides nothing"""
+    from nicer_slam_amd import mesh_topology as M
+    f, V = T.quad_sheet(a, b)
+    F = 2 * a * b
+    t, _ = M._edge_table(f, V, F, None)
+    label, orientable, flip, totals = M._orientation(f, t, F)
+    assert totals == dict(n_components=1, n_nonorientable=0, n_flipped=0)
+    assert int(label.abs().max()) == 0 and bool((orientable == 1).all()) and not bool(flip.any())
+    i = torch.arange(V, device="cuda")
+    v = torch.stack([i // (b + 1), i % (b + 1), torch.zeros_like(i)], 1).float()
+    out, vol = M._orient_volume(v, f, V, F, t, label, orientable, flip)
+    assert [vol[k] for k in ("n_closed", "n_decided", "n_toggled", "n_flipped")] == [0, 0, 0, 0] and not bool(out.any())
+    assert vol["n"][0].item() == F and vol["flags"][0].item() == 0
+
+
 def test_many_segments_and_one_across_blocks():
     """1500 tetrahedra (segments of four faces that cross the blocks of the reduction) and one component of 5000 faces, their faces in
     a seeded order and half of them reversed: every one is wound outward"""

@@ -137,6 +137,27 @@ def test_adversarial_face_lists():
         _check_simplify(_with_attributes(v, f, 1), 0.3, placements=("quadric",))
 
 
+@pytest.mark.parametrize("a,b", [(32, 30), (31, 31), (24, 40), (7, 73), (16, 32), (19, 27), (1024, 1024)])
+def test_sheets_at_the_seams_of_the_scans(a, b):
+    """a flat a x b quad sheet (topology_ref.quad_sheet), one vertex to a cell, so nothing merges: V' = V, F' = F and the output faces
+    are the input faces under the returned vertex map.  V = 1023, 1024, 1025 and F = 1022, 1024, 1026 sit just below, at and just
+    above the 1024 lanes of a block of the three rank scans (csrc/block_scan.hpp); the 1024 x 1024 sheet (V = 1 050 625, F = 2 097 152)
+    has more blocks than the one workgroup that scans the block counts has lanes"""
+    from nicer_slam_amd import mesh_simplify as M
+    f, V = T.quad_sheet(a, b)
+    F = 2 * a * b
+    i = torch.arange(V, device="cuda")
+    v = torch.stack([i // (b + 1), i % (b + 1), torch.zeros_like(i)], 1).float() + 0.5          # the centre of cell (i, j, 0)
+    got = M.cluster(f, v, 1.0, (0.0, 0.0, 0.0))
+    assert [got[k] for k in TOTALS] == [V, F, V, 0, 0, 0, V, F]
+    vmap = torch.empty(V, dtype=torch.int64, device="cuda")
+    vmap[got["out_cluster"].long()] = torch.arange(V, device="cuda")                             # cluster -> output vertex
+    vmap = vmap[got["vertex_cluster"].long()]                                                    # vertex -> output vertex
+    assert torch.equal(got["faces"].long(), vmap[f.long()])                   # (every sheet face already starts at its smallest vertex)
+    assert torch.equal(got["face_origin"].long(), torch.arange(F, device="cuda"))
+    assert torch.equal(vmap, torch.arange(V, device="cuda"))                  # cell keys ascend with the row-major vertex index
+
+
 def test_cube():
     v, f = S.cube(8)
     for h in (0.21, 0.3, 0.77):

@@ -98,6 +98,36 @@ def test_runs_across_workgroup_boundaries():
     assert (t["n_edges"], t["n_boundary"], t["n_inconsistent"], t["n_boundary_loops"], n) == (10001, 5002, 0, 1, 1)
 
 
+# a x b quad sheets whose counts sit at the seams of the scans (csrc/block_scan.hpp): B = 1024 lanes to a block of the rank and count
+# kernels, W = 1024 lanes in the one workgroup that scans the block counts.  3 F = 1020 and 1026 half-edges (3 F = 1024 does not
+# exist); V = 1023, 1024, 1025 vertices; F = 1022, 1024, 1026 faces; and 3 F = 1 053 366 > W B, where a lane of the offsets scan owns
+# more than one block.
+SEAM_SHEETS = [(10, 17), (9, 19), (32, 30), (31, 31), (24, 40), (7, 73), (16, 32), (19, 27), (419, 419)]
+
+
+@pytest.mark.parametrize("a,b", SEAM_SHEETS)
+def test_sheets_at_the_seams_of_the_scans(a, b):
+    """the sheet's table in closed form (topology_ref.quad_sheet), checked on the device; the small ones against the oracle as well"""
+    from nicer_slam_amd import mesh_topology as M
+    f, V = T.quad_sheet(a, b)
+    F, E = 2 * a * b, 3 * a * b + a + b
+    if F < 5000:
+        _check(f.cpu().numpy(), V)
+    t = M.edge_table(f, V)
+    label, n = M.face_components(f, V)
+    assert [t[k] for k in TOTALS] == [E, F, V, 2 * (a + b), 0, 0, 1]
+    assert n == 1 and int(label.abs().max()) == 0
+    lo, hi = t["edges"][:, 0].long(), t["edges"][:, 1].long()
+    key = lo * V + hi
+    assert bool((lo < hi).all()) and bool((key[1:] > key[:-1]).all())                  # every edge once, in (lo, hi) order
+    count, start = t["edge_count"].long(), t["edge_start"].long()
+    assert start[0].item() == 0 and start[E].item() == 3 * F and torch.equal(start[1:] - start[:-1], count)
+    assert int((count == 1).sum()) == 2 * (a + b) and int((count == 2).sum()) == E - 2 * (a + b)
+    assert bool((t["edge_forward"][count == 2] == 1).all())
+    ends = torch.stack([f.long(), f.long().roll(-1, 1)], 2).reshape(-1, 2)            # half-edge 3 f + k runs from corner k to k + 1
+    assert torch.equal(t["edges"].long()[t["face_edges"].reshape(-1).long()], ends.sort(1).values)
+
+
 def test_face_mask(cases):
     f, V, _ = cases["mc sphere"]
     mask = (np.arange(len(f)) % 7 != 0).astype(np.uint8)

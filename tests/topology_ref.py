@@ -142,6 +142,18 @@ def strip(n=5000, seed=3):
     return perm[f[::-1]].astype(np.int32), n + 2
 
 
+def quad_sheet(a, b, device="cuda"):
+    """(faces int32 [2 a b, 3] as a torch tensor on ``device``, V): an a x b sheet of quads over (a + 1)(b + 1) vertices in row-major
+    order, quad (i, j) cut into faces 2 (i b + j) and 2 (i b + j) + 1 along the same diagonal and all wound alike.  In closed form:
+    E = 3 a b + a + b, 2 (a + b) boundary edges in one loop, one component, no inconsistent edge"""
+    import torch
+    i, j = torch.meshgrid(torch.arange(a, device=device), torch.arange(b, device=device), indexing="ij")
+    v00 = (i * (b + 1) + j).reshape(-1)
+    v01, v10, v11 = v00 + 1, v00 + b + 1, v00 + b + 2
+    f = torch.stack([torch.stack([v00, v10, v11], 1), torch.stack([v00, v11, v01], 1)], 1)
+    return f.reshape(-1, 3).to(torch.int32).contiguous(), (a + 1) * (b + 1)
+
+
 def high_index_faces(V):
     """four faces of a tetrahedron on the four highest indices of V vertices"""
     return (TET + (V - 4)).astype(np.int32), V
