@@ -1879,6 +1879,69 @@ int nsa_tri_isect_emit(const void *tree, const float *verts, uint32_t n_verts, c
                        const uint8_t *side, uint32_t flags, const void *workspace, const uint8_t *state, uint64_t n_pairs,
                        int64_t *pairs, uint8_t *code, nsa_stream_t stream);
 
+/* ---- Section 26: one vertex per fan of faces -- cutting a mesh into a 2-manifold (csrc/mesh_manifold.hip) ---- */
+
+/* The "cutting" step of Gueziec et al.: every vertex is duplicated once per FAN of faces around it, the fans found through regular
+ * edges only.  After nsa_mesh_edges (Section 18) on the same faces (and the same mask), from the arrays it wrote and its totals as
+ * they lie on the device.  Everything is by index: coordinates play no part.  Integer work, exact and bit-reproducible.
+ * tests/manifold_ref.py restates this statement sequentially.  n_verts + 3 * n_faces < 2^31 (V below is n_verts, F n_faces).
+ *
+ * Corners.  Corner c = 3 f + k of a contributing face f (Section 18's rule: face_edges[3 f] >= 0) sits at vertex faces[f][k].
+ *
+ * Regular edge.  edge_count == 2; with NSA_SPLIT_CUT_INCONSISTENT in flags, edge_forward == 1 as well; with face_label (int32 [F],
+ * NULL = none) given, both faces carry the same label (so a caller can cut seams between labelled patches).  Every other edge with
+ * edge_count >= 2 is CUT.
+ *
+ * Fans.  Two corners at the same vertex are joined when their faces share a regular edge incident to that vertex; the fans are
+ * the classes of the transitive closure.  The LEADER of a fan is its smallest corner id.  One union-find over the 3 F corners with
+ * Section 11's uf_find / uf_unite unchanged, one pass over the edges: a regular edge (lo, hi) unites its two faces' corners at lo,
+ * and their corners at hi.  parent[x] <= x, so the root is the leader whatever the interleaving and the atomics decide nothing.
+ *
+ * Naming.  The leaders in ascending corner order, stably argsorted by vertex: ascending (vertex, leader).  The first fan of vertex v
+ * keeps the name v; every further fan gets V + r, r its rank among all further fans in that order (one exclusive scan of the "not
+ * head of its run" flags).
+ *
+ * Outputs.
+ *   corner_fan[3 F] int32    the leader of the corner's fan, -1 for a corner of a face that does not contribute
+ *   vertex_fans[V] int32     the number of fans of each vertex, 0 for an unused one
+ *   faces_out[F, 3] int32    contributing faces renamed by fan; another face is copied, except that an index >= V is written as -1,
+ *                            so that no such face reaches a new vertex by accident
+ *   new_source[3 F] int32    the first n_new entries are valid: entry r is the vertex that new vertex V + r copies
+ *   totals[8] (uint64, device; the caller reads them once):
+ *     {contributing faces, fans, singular vertices (more than one fan), of those the ones with no cut edge incident (a pinch only),
+ *      cut edges, n_new, the most fans at one vertex, status}
+ * status: Section 11's bits from the union-find; 0 unless the implementation is wrong.
+ *
+ * Properties (proved in DESIGN 4y).  The link of a vertex v is the graph whose nodes are the edges at v and whose arcs are the
+ * corners at v, each joining its face's two edges at v.  A node of degree above two is an edge with more than two faces, which is
+ * cut; so cutting the link at every node whose edge is not regular leaves nodes of degree <= 2 only: paths and cycles.  Hence (a) a
+ * fan holds at most two faces on any input edge, (b) every edge of the output has edge_count <= 2, (c) every output vertex has
+ * exactly one fan, and the operation is idempotent: on its own output it finds no cut edge, n_new = 0 and faces_out = faces.  Old
+ * vertices and every face index keep their place (a face's k-th index stays its k-th).  The result is a function of (faces, n_verts,
+ * face_mask, flags, face_label) alone.
+ *
+ * Kernel shape: the join over the edges; the leader pass over the corners, which also gives every corner its key -- its vertex when
+ * it leads, n_verts otherwise, which sorts last; one stable radix argsort (Section 4's) of the 3 F keys with only the 8-bit passes
+ * n_verts needs; run heads by comparing neighbours in the sorted order; one exclusive scan; the face rewrite.  Totals are sums, ORs and
+ * one maximum of per-block integers; there are no atomics outside the union-find.  No attribute is touched: the caller gathers rows
+ * by new_source.
+ *
+ * NULL faces, table array, workspace, totals or output array (vertex_fans may be NULL when n_verts = 0), an unknown flag, or
+ * n_verts + 3 * n_faces >= 2^31: NSA_EBADARG before anything is launched.  n_faces = 0 launches nothing, writes nothing and returns
+ * 0.  Arrays that nsa_mesh_edges did not write for these faces give meaningless fans, never an access out of bounds.  Nothing is
+ * allocated or synchronised. */
+
+#define NSA_SPLIT_CUT_INCONSISTENT 1u /* flags: an edge whose two faces traverse it the same way is cut as well */
+
+/* bytes of workspace (256-byte aligned, device); 0 for an invalid count (n_faces = 0 or n_verts + 3 * n_faces >= 2^31) */
+uint64_t nsa_mesh_split_fans_workspace(uint32_t n_verts, uint32_t n_faces);
+
+int nsa_mesh_split_fans(const int32_t *faces, uint32_t n_faces, uint32_t n_verts, const int32_t *face_label, uint32_t flags,
+                        const int32_t *edges, const int32_t *edge_count, const int32_t *edge_forward, const int32_t *edge_start,
+                        const int32_t *edge_halfedges, const int32_t *face_edges, const uint64_t *edge_totals, void *workspace,
+                        int32_t *corner_fan, int32_t *vertex_fans, int32_t *faces_out, int32_t *new_source, uint64_t *totals,
+                        nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -480,3 +480,9 @@ lib.nsa_tri_isect_count.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _p
 lib.nsa_tri_isect_emit.restype = _i
 lib.nsa_tri_isect_emit.argtypes = [_p, _p, _u32, _p, _u32, _p, _u32, _p, _p, _u64, _p, _p, _p]
 EXPORTS += ["nsa_tri_isect_workspace", "nsa_tri_isect_count", "nsa_tri_isect_emit"]
+lib.nsa_mesh_split_fans_workspace.restype = _u64
+lib.nsa_mesh_split_fans_workspace.argtypes = [_u32, _u32]
+lib.nsa_mesh_split_fans.restype = _i
+lib.nsa_mesh_split_fans.argtypes = [_p, _u32, _u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+EXPORTS += ["nsa_mesh_split_fans_workspace", "nsa_mesh_split_fans"]
+SPLIT_CUT_INCONSISTENT = 1                                                  # NSA_SPLIT_* of header Section 26

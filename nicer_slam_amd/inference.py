@@ -182,7 +182,7 @@ def vertex_colours(model, verts, normals, chunk=1 << 20):
 
 @torch.no_grad()
 def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage="fine", color=True, chunk=1 << 22, simplify=None,
-                 smooth=None, decimate=None, fill_holes=None):
+                 smooth=None, decimate=None, fill_holes=None, split=None):
     """get_surface_trace on the device (plots.py:87-155): ``sdf_grid`` -> ``marching_cubes`` with the grid's spacing and origin
     -> (``color``) ``vertex_colours``.  Returns the marching_cubes dict, plus ``colors`` [V,3] in [0,1] when ``color`` is set.
     A level outside the volume's range gives empty tensors (the reference prints "NO MESH" and writes nothing).
@@ -193,7 +193,11 @@ def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage=
     ``decimate``: a dict of ``mesh_decimate.decimate`` keywords (``target_faces=`` or ``max_error=``, ...), applied last, after
     ``simplify``; None collapses nothing.
     ``fill_holes``: a dict of ``mesh_fill.fill_holes`` keywords (``max_edges=``, ``max_size=``, ...), applied after the colouring
-    and before ``smooth``, ``simplify`` and ``decimate`` -- a mesh cut by the grid's box is closed there; None fills nothing."""
+    and before ``smooth``, ``simplify`` and ``decimate`` -- a mesh cut by the grid's box is closed there; None fills nothing.
+    ``split``: True or a dict of ``mesh_repair.split_nonmanifold`` keywords, applied after ``simplify`` and before ``decimate`` -- the
+    edges with more than two faces that clustering makes are cut there, so that ``decimate`` need not lock them; None cuts nothing."""
+    if split is not None and not isinstance(split, (bool, dict)):
+        raise ValueError("extract_mesh: split must be None, a bool or a dict of mesh_repair.split_nonmanifold keywords")
     if fill_holes is not None and not isinstance(fill_holes, dict):
         raise ValueError("extract_mesh: fill_holes must be None or a dict of mesh_fill.fill_holes keywords")
     if decimate is not None and not isinstance(decimate, dict):
@@ -217,6 +221,9 @@ def extract_mesh(model, resolution, grid_boundary=(-2.0, 2.0), level=0.0, stage=
     if simplify is not None:
         from .mesh_simplify import simplify as simplify_mesh
         mesh = simplify_mesh(mesh, **simplify)
+    if split:
+        from .mesh_repair import split_nonmanifold
+        mesh = split_nonmanifold(mesh, **(split if isinstance(split, dict) else {}))
     if decimate is not None:
         from .mesh_decimate import decimate as decimate_mesh
         mesh = decimate_mesh(mesh, **decimate)

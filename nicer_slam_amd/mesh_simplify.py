@@ -179,7 +179,7 @@ def _search(v, f, origin, lo3, hi3, target):
     return hi
 
 
-def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=None, eps=1e-3, return_map=False):
+def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=None, eps=1e-3, return_map=False, split=None):
     """Simplify ``mesh`` (a dict with ``verts`` [V, 3] and ``faces`` [F, 3], optionally ``normals`` and ``colors`` [V, 3]; numpy or
     torch) by vertex clustering (header Section 19): the same kind of dict with one vertex per occupied grid cell that a surviving
     face names, for ``write_ply``, ``TriIndex``, ``mesh_clean`` and ``mesh_topology`` as it is.
@@ -192,6 +192,10 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
     outside [0, V) is dropped.  A sheet that collapses to zero thickness keeps its two sides (a triple and its reverse are different
     faces).  ``return_map=True`` adds ``vertex_cluster`` [V] (the cluster of each input vertex, -1 if unused), ``face_origin`` [F']
     (the input face of each output face), ``vertex_cell`` [V', 3], ``totals`` (a dict of ints) and ``cell`` (the cell size used).
+    ``split``: None (default) leaves the result as clustering made it -- sheets closer than a cell merge, so it may have edges with
+    more than two faces --; True or a dict of ``mesh_repair.split_nonmanifold`` keywords cuts it into a 2-manifold: the
+    faces keep their place, the new vertices follow the clusters' (with ``return_map``, ``vertex_source`` [V''] names the cluster
+    vertex each one copies and ``vertex_cell`` has their rows too).
 
     Synchronises for the extent of the vertices and once for the totals (``target_faces``: once per probe as well)."""
     name = "simplify"
@@ -204,6 +208,8 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
     eps = float(eps)
     if not (math.isfinite(eps) and eps >= 0.0):
         raise ValueError("simplify: eps must be finite and >= 0")
+    if split is not None and not isinstance(split, (bool, dict)):
+        raise ValueError("simplify: split must be None, a bool or a dict of mesh_repair.split_nonmanifold keywords")
     if cell is not None:
         h = _checked_cell(cell, name)
     elif int(target_faces) != target_faces or target_faces < 0:
@@ -228,6 +234,12 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
     if return_map:
         out.update(vertex_cluster=restore(t["vertex_cluster"]), face_origin=restore(t["face_origin"][:totals["n_faces"]]),
                    vertex_cell=restore(p["vertex_cell"]), totals=totals, cell=h)
+    if split:
+        from .mesh_repair import split_nonmanifold
+        out = split_nonmanifold(out, **dict(split if isinstance(split, dict) else {}, return_report=False, return_map=return_map))
+        if return_map:
+            src = out["vertex_source"]
+            out["vertex_cell"] = out["vertex_cell"][src.long() if torch.is_tensor(src) else src.astype(np.int64)]
     return out
 
 

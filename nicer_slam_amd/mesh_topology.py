@@ -12,7 +12,9 @@ csrc/mesh_topology.hip).
 * ``orientation(mesh)`` / ``orient(mesh, outward=...)``: the faces to reverse for a consistent winding, whether that exists, and the
   re-wound mesh with its normals outward by signed volume or towards the cameras (C ABI Section 20, csrc/mesh_orient.hip).
 * ``python -m nicer_slam_amd.mesh_topology MESH.ply [--weld] [--json]`` prints the report; ``--orient OUT.ply [--outward
-  volume|views|none] [--poses P --intrinsics fx fy cx cy --size H W]`` writes the re-wound mesh and prints its report instead.
+  volume|views|none] [--poses P --intrinsics fx fy cx cy --size H W]`` writes the re-wound mesh and prints its report instead;
+  ``--split`` cuts the mesh into a 2-manifold first (``mesh_repair.split_nonmanifold``), so that the winding can be
+  carried across what were edges with more than two faces.
 
 Everything is integer work and exact.  numpy in, numpy out; torch in, torch out.  There is no CPU path: a missing GPU is an error.
 """
@@ -488,6 +490,8 @@ def main(argv=None):
     ap.add_argument("--weld", action="store_true", help="name vertices by their coordinates: connect across repeated seam vertices")
     ap.add_argument("--json", action="store_true", help="print the report as one JSON object")
     ap.add_argument("--intersections", action="store_true", help="add n_proper_pairs and embedded (mesh_intersect, DESIGN 4x)")
+    ap.add_argument("--split", action="store_true",
+                    help="cut the mesh into a 2-manifold first: one vertex per fan of faces (mesh_repair, DESIGN 4y)")
     ap.add_argument("--orient", metavar="OUT.ply", help="write the mesh with a consistent winding (DESIGN 4s) and print that report")
     ap.add_argument("--outward", choices=("volume", "views", "none"), default="volume",
                     help="with --orient: which of the two consistent windings a component gets")
@@ -497,9 +501,14 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.orient is not None and a.outward == "views" and (a.poses is None or a.intrinsics is None or a.size is None):
         ap.error("--outward views needs --poses, --intrinsics and --size")
+    if a.split and a.weld:
+        ap.error("--split and --weld undo each other: the welded names join the vertices that the split made")
     _need_gpu("mesh_topology")
     try:
         mesh = read_ply(a.mesh)
+        if a.split:
+            from .mesh_repair import split_nonmanifold
+            mesh = split_nonmanifold(mesh)
         if a.orient is None:
             r = topology(mesh, weld=a.weld, intersections=a.intersections)
         else:

@@ -201,13 +201,17 @@ class TSDFVolume:
         return out
 
     @torch.no_grad()
-    def extract_mesh(self, min_weight=1, smooth=None, decimate=None, fill_holes=None):
+    def extract_mesh(self, min_weight=1, smooth=None, decimate=None, fill_holes=None, split=None):
         """The zero level of the observed volume: the ``inference.marching_cubes`` dict (verts, normals, faces), plus ``colors`` when
         the volume has colour -- what ``inference.write_ply`` and ``mesh_eval.mesh_metrics`` take.  ``smooth``: a dict of
         ``mesh_smooth.smooth`` keywords, applied after the colours are sampled on the true level set (the depth noise of the
         frames is on that surface); None leaves the mesh as marching cubes made it.  ``decimate``: a dict of
         ``mesh_decimate.decimate`` keywords, applied last; None collapses nothing.  ``fill_holes``: a dict of
-        ``mesh_fill.fill_holes`` keywords, applied after the colours and before ``smooth`` and ``decimate``; None fills nothing."""
+        ``mesh_fill.fill_holes`` keywords, applied after the colours and before ``smooth`` and ``decimate``; None fills nothing.
+        ``split``: True or a dict of ``mesh_repair.split_nonmanifold`` keywords, applied before ``decimate``: the mesh is cut into a
+        2-manifold there (thin structures give marching cubes edges with four faces); None cuts nothing."""
+        if split is not None and not isinstance(split, (bool, dict)):
+            raise ValueError("extract_mesh: split must be None, a bool or a dict of mesh_repair.split_nonmanifold keywords")
         if fill_holes is not None and not isinstance(fill_holes, dict):
             raise ValueError("extract_mesh: fill_holes must be None or a dict of mesh_fill.fill_holes keywords")
         if decimate is not None and not isinstance(decimate, dict):
@@ -224,6 +228,9 @@ class TSDFVolume:
         if smooth is not None:
             from .mesh_smooth import smooth as smooth_mesh
             mesh = smooth_mesh(mesh, **smooth)
+        if split:
+            from .mesh_repair import split_nonmanifold
+            mesh = split_nonmanifold(mesh, **(split if isinstance(split, dict) else {}))
         if decimate is not None:
             from .mesh_decimate import decimate as decimate_mesh
             mesh = decimate_mesh(mesh, **decimate)
