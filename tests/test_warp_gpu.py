@@ -2,7 +2,11 @@
 csrc/warp_terms.hip, fused/warp.py) against (i) the function-level golden captured from the reference's forward
 (reproj_blocks.npz: forward tensors, d/d depth and direct d/d pose of every term, total camera gradient through the fused
 engine), (ii) the golden-pinned torch restatement (model/warp.py) at the shipped image size, patch sizes 1 / 5 / 11, with and
-without bundle adjustment, with a resident frame store."""
+without bundle adjustment, with a resident frame store.
+
+The same kernels are held to float64 row by row, with a K per frame, skew, w2c as an independent input and the shapes and edges this
+file does not reach, by tests/test_warp_float64_gpu.py (reference tests/warp_ref64.py, inputs tests/warp_cases.py; the reference itself
+is pinned without a GPU by tests/test_warp_ref64_cpu.py)."""
 from types import SimpleNamespace
 
 import numpy as np
