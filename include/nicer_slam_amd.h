@@ -1942,6 +1942,59 @@ int nsa_mesh_split_fans(const int32_t *faces, uint32_t n_faces, uint32_t n_verts
                         int32_t *corner_fan, int32_t *vertex_fans, int32_t *faces_out, int32_t *new_source, uint64_t *totals,
                         nsa_stream_t stream);
 
+/* ---- Section 27: point-to-plane registration -- the moved source and the 6x6 normal equations (csrc/mesh_register.hip) ---- */
+
+/* One iteration of point-to-plane ICP (Chen & Medioni 1992; open3d's TransformationEstimationPointToPlane with a RobustKernel) is:
+ * move the float64 source, query its correspondences with Section 8's or Section 15's query, and sum the rows of the linearised
+ * problem.  This section is the first and the last of the three; the 6x6 solve is the caller's (nicer_slam_amd/mesh_register.py states
+ * it).  Everything is float64 with every operation rounded on its own (no fused multiply-add), and the order of every sum is a function
+ * of n alone: the results are the same bits on every run and every device, and tests/register_ref.py restates them in numpy.
+ *
+ * nsa_icp_transform.  cur [n, 3] float64 is moved in place by the row-major 4x4 upd (16 doubles in HOST memory, read before the call
+ * returns): y_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k.  cur32 [n, 3] receives the fp32 rounding of the result, which the queries take.
+ *
+ * nsa_icp_plane_system.  One row per source point i, p = cur[i].  corr [n] int32 names the row's correspondence:
+ *   NSA_ICP_CLOUD    corr = idx of nsa_nn_query.  With 0 <= corr < n_targets: q = targets[corr] and nrm = normals[corr] (fp32 [n_targets, 3],
+ *                    widened), and dd = d * d with d = dist[i] (the query's fp32 distance, widened).
+ *   NSA_ICP_SURFACE  corr = face of nsa_tri_query_bounded.  With 0 <= corr < n_faces and the face's three indices in [0, n_verts):
+ *                    q = closest[i] (the query's fp32 closest point, widened), dd = d2[i] (the query's float64 squared distance), and
+ *                    nrm = c / sqrt((c_x c_x + c_y c_y) + c_z c_z) with c = ab x ac in float64 from the face's fp32 vertices
+ *                    (c_x = ab_y ac_z - ab_z ac_y and so on; the root and the quotients correctly rounded).
+ * Any other corr: the row has no correspondence.  A row with one is USED when nrm is finite and not (0, 0, 0).  Per used row:
+ *   d = p - q;  r = (n_x d_x + n_y d_y) + n_z d_z;  a = (p_y n_z - p_z n_y, p_z n_x - p_x n_z, p_x n_y - p_y n_x);  J = (a, nrm)
+ *   w = 1 (NSA_ICP_KERNEL_L2);  1 if |r| <= k else k / |r| (HUBER);  v v with u = r / k, v = 1 - u u if |r| <= k else 0 (TUKEY)
+ *   g_i = w J_i
+ * sums [30] (float64, device):  [0..20] g_i J_j for i <= j, the upper triangle row by row;  [21..26] g_i r;  [27] r r;  [28] (w r) r;
+ * [29] dd, over the rows with a correspondence, used or not.  counts [2] (uint64, device): rows with a correspondence, rows used.
+ * r and J change sign together with nrm, so none of the sums depends on the side the normals point to.
+ *
+ * Order.  Tiles of 4096 consecutive rows.  Lane l of 256 adds the rows l, l + 256, ... of its tile in ascending order onto +0.0; a row
+ * that is past n, has no correspondence or is not used adds +0.0 in its place, so the order does not depend on which rows matched.  A
+ * binary tree over the 256 lanes, s[i] = s[2 i] + s[2 i + 1], eight levels, gives the tile's total.  While more than one value is left,
+ * the values go in groups of 256 consecutive ones, the last group padded with +0.0, through the same tree.  No floating-point atomic
+ * takes part and nothing depends on the launch geometry or on the order in which workgroups finish.
+ *
+ * n >= 2^31, an unknown mode or kernel, k not positive and finite for HUBER or TUKEY, or (for n > 0) a NULL array of the mode, NULL
+ * workspace, sums or counts: NSA_EBADARG before the device is touched.  n = 0 launches nothing, writes nothing and returns 0.  Nothing
+ * is allocated or synchronised; the workspace is a function of n.  An index outside its range makes a row without a correspondence,
+ * never an access out of bounds. */
+
+#define NSA_ICP_CLOUD 0
+#define NSA_ICP_SURFACE 1
+#define NSA_ICP_KERNEL_L2 0
+#define NSA_ICP_KERNEL_HUBER 1
+#define NSA_ICP_KERNEL_TUKEY 2
+
+int nsa_icp_transform(double *cur, uint32_t n, const double *upd, float *cur32, nsa_stream_t stream);
+
+/* bytes of workspace (256-byte aligned, device); 0 for n = 0 or n >= 2^31 */
+uint64_t nsa_icp_plane_system_workspace(uint32_t n);
+
+int nsa_icp_plane_system(const double *cur, uint32_t n, int mode, const int32_t *corr, const float *dist, const float *targets,
+                         const float *normals, uint32_t n_targets, const double *d2, const float *closest, const float *verts,
+                         uint32_t n_verts, const int32_t *faces, uint32_t n_faces, int kernel, double k, void *workspace, double *sums,
+                         uint64_t *counts, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

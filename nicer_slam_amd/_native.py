@@ -486,3 +486,12 @@ lib.nsa_mesh_split_fans.restype = _i
 lib.nsa_mesh_split_fans.argtypes = [_p, _u32, _u32, _p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
 EXPORTS += ["nsa_mesh_split_fans_workspace", "nsa_mesh_split_fans"]
 SPLIT_CUT_INCONSISTENT = 1                                                  # NSA_SPLIT_* of header Section 26
+lib.nsa_icp_transform.restype = _i
+lib.nsa_icp_transform.argtypes = [_p, _u32, ctypes.POINTER(_f64), _p, _p]
+lib.nsa_icp_plane_system_workspace.restype = _u64
+lib.nsa_icp_plane_system_workspace.argtypes = [_u32]
+lib.nsa_icp_plane_system.restype = _i
+lib.nsa_icp_plane_system.argtypes = [_p, _u32, _i, _p, _p, _p, _p, _u32, _p, _p, _p, _u32, _p, _u32, _i, _f64, _p, _p, _p, _p]
+EXPORTS += ["nsa_icp_transform", "nsa_icp_plane_system_workspace", "nsa_icp_plane_system"]
+ICP_CLOUD, ICP_SURFACE = 0, 1                                               # NSA_ICP_* of header Section 27
+ICP_KERNELS = ("l2", "huber", "tukey")                                      # NSA_ICP_KERNEL_*

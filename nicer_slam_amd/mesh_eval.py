@@ -15,8 +15,10 @@ trimesh's surface sampling.
   rays against the mesh (C ABI Section 17, csrc/mesh_raycast.hip; nicer_slam_amd/mesh_raycast.py renders depth with it).
 * ``mesh_metrics(..., surface="mesh")``: the same metrics from the distance of each sample to the other mesh's SURFACE, which a
   perfect reconstruction scores 0 on; the default ``surface="samples"`` is the reference's sample-to-sample form.
-* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale] [--surface mesh]``: the
-  reference's printout.
+* ``mesh_metrics(..., icp="plane" | "surface")``: the alignment by point-to-plane ICP against the ground truth's vertices and normals
+  or against its surface (nicer_slam_amd/mesh_register.py); the default ``icp="point"`` is the reference's.
+* ``python -m nicer_slam_amd.mesh_eval REC.ply GT.ply [--sim3 T.npy] [--clean largest] [--adjust-scale] [--surface mesh]
+  [--icp point|plane|surface]``: the reference's printout.
 
 Reductions over the distance arrays (means, counts, ICP's centroids and cross-covariance) run in torch float64: they are small
 and deterministic.  There is no CPU path: a missing GPU is an error.
@@ -541,7 +543,7 @@ def _as_cuda_mesh(m, device):
 
 @torch.no_grad()
 def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device="cuda", pre_transform=None, clean=None,
-                 region=None, adjust_scale=False, cull=None, surface="samples", connectivity="vertex"):
+                 region=None, adjust_scale=False, cull=None, surface="samples", connectivity="vertex", icp="point"):
     """calc_3d_metric + calc_normal_consistency of eval_rec.py on the device.  ``rec`` / ``gt``: dicts with ``verts`` [V,3] and
     ``faces`` [F,3] (numpy or torch; what read_ply / marching_cubes return).  Both are divided by ``scale``; with ``align`` the
     reconstruction is moved by ICP of its vertices onto the ground truth's (max_corr 0.1).  n_points samples per surface (seeds
@@ -565,9 +567,17 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     (not a step of the reference, which carries distance_p2m unused) measures it against the other MESH: the same samples from
     the same seeds, accuracy = mean distance of the reconstruction's samples to the ground-truth mesh, completion = mean distance
     of the ground truth's samples to the reconstruction's mesh, the normals term against the closest face's normal, everything
-    else from those two distance arrays (metrics_from_surfaces); the result then carries "surface": "mesh"."""
+    else from those two distance arrays (metrics_from_surfaces); the result then carries "surface": "mesh".
+    ``icp``: what the alignment minimises.  "point" (the default, the reference's): icp_point_to_point.
+    "plane": mesh_register.icp_point_to_plane of the reconstruction's vertices against the ground truth's vertices with
+    mesh_smooth.vertex_normals(gt, "angle"); "surface": against the ground-truth MESH itself.  Both are rigid, so either
+    with ``adjust_scale`` raises ValueError; the result then carries "icp": the metric, and "icp degenerate"."""
     if surface not in ("samples", "mesh"):
         raise ValueError(f"mesh_metrics: surface must be 'samples' or 'mesh', got {surface!r}")
+    if icp not in ("point", "plane", "surface"):
+        raise ValueError(f"mesh_metrics: icp must be 'point', 'plane' or 'surface', got {icp!r}")
+    if icp != "point" and adjust_scale:
+        raise ValueError(f"mesh_metrics: icp={icp!r} is rigid; adjust_scale goes with icp='point' only")
     if not torch.cuda.is_available():
         raise RuntimeError("mesh_metrics: needs a GPU")
     rv, rf = _as_cuda_mesh(rec, device)
@@ -597,8 +607,17 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
         extra["culled face fraction"] = 1.0 - rf.shape[0] / n_before
     T, fit, rmse = np.eye(4), None, None
     if align:
-        icp = icp_point_to_point(rv, gv, 0.1, with_scaling=adjust_scale)
-        T, fit, rmse = icp["transformation"], icp["fitness"], icp["inlier_rmse"]
+        if icp == "point":
+            res = icp_point_to_point(rv, gv, 0.1, with_scaling=adjust_scale)
+        else:
+            from . import mesh_register, mesh_smooth
+            if icp == "plane":
+                gn = mesh_smooth.vertex_normals({"verts": gv, "faces": gf.to(torch.int32)}, "angle")
+                res = mesh_register.icp_point_to_plane(rv, gv, gn, 0.1)
+            else:
+                res = mesh_register.icp_point_to_plane(rv, (gv, gf), None, 0.1)
+            extra.update({"icp": icp, "icp degenerate": res["degenerate"]})
+        T, fit, rmse = res["transformation"], res["fitness"], res["inlier_rmse"]
         rv = _transform(rv.double(), torch.from_numpy(T).to(rv.device)).float()
     rp, ri = sample_surface(rv, rf, n_points, seed)
     gp, gi = sample_surface(gv, gf, n_points, seed + 1)
@@ -684,7 +703,12 @@ def main(argv=None):
     ap.add_argument("--cull-raycast", action="store_true", help="decide visibility by casting rays (mesh_render method='raycast')")
     ap.add_argument("--surface", choices=("samples", "mesh"), default="samples",
                     help="measure each sample against the other surface's samples (the reference) or against the other mesh itself")
+    ap.add_argument("--icp", choices=("point", "plane", "surface"), default="point",
+                    help="what the alignment minimises: point to point (the reference), point to plane against GT's vertices and "
+                    "normals, or point to plane against GT's surface itself")
     a = ap.parse_args(argv)
+    if a.icp != "point" and a.adjust_scale:
+        ap.error("--adjust-scale goes with --icp point only")
     if a.cull_poses and not (a.cull_intrinsics and a.cull_size):
         ap.error("--cull-poses needs --cull-intrinsics and --cull-size")
     if not a.cull_poses and (a.cull_intrinsics or a.cull_size):
@@ -700,7 +724,7 @@ def main(argv=None):
     m = mesh_metrics(read_ply(a.rec), read_ply(a.gt), a.points, a.seed, not a.no_align, a.scale,
                      pre_transform=np.load(a.sim3) if a.sim3 else None, clean=a.clean,
                      region=(a.region[:3], a.region[3:]) if a.region else None, adjust_scale=a.adjust_scale, cull=cull,
-                     surface=a.surface, connectivity=a.connectivity)
+                     surface=a.surface, connectivity=a.connectivity, icp=a.icp)
     if a.surface == "mesh":
         print("surface: mesh (each sample against the other mesh's surface)")
     print("accuracy: ", m["accuracy"] * 100, "cm")
