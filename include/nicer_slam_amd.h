@@ -1995,6 +1995,47 @@ int nsa_icp_plane_system(const double *cur, uint32_t n, int mode, const int32_t 
                          uint32_t n_verts, const int32_t *faces, uint32_t n_faces, int kernel, double k, void *workspace, double *sums,
                          uint64_t *counts, nsa_stream_t stream);
 
+/* ---- Section 28: k nearest neighbours and normals of raw clouds (csrc/mesh_eval.hip, csrc/cloud_normals.hip) ---- */
+
+/* nsa_nn_query_k.  index: one built by nsa_nn_build over n_targets targets (Section 8).  With the fp32 d2 of Section 8,
+ * (dx * dx + dy * dy) + dz * dz with every operation rounded on its own, row j of idx / dist [n_queries, k] receives the k smallest
+ * targets of query j under the total order (d2, target index), in that order: an exact tie goes to the lower index, at the k-th
+ * place too, and neither the set nor the order depends on the order the index's cells are read in.  dist is the correctly rounded
+ * fp32 root of d2.  With a finite max_dist only targets with d2 < (float)(max_dist * max_dist) count (strict, as nsa_nn_query).
+ * count [n_queries] receives the number found, min(k, accepted targets); the slots behind it hold (-1, +inf).  Targets with a
+ * non-finite coordinate are never returned.  A non-finite query gives count 0 and (-1, NaN) in every slot.  k = 1 writes what
+ * nsa_nn_query writes.
+ *
+ * 1 <= k <= 64 and max_dist > 0, else NSA_EBADARG; n_queries > 0 with a NULL queries, idx, dist or count: NSA_EBADARG before anything
+ * is launched; n_queries = 0 launches nothing and returns 0.  Nothing is allocated or synchronised. */
+int nsa_nn_query_k(const void *index, uint32_t n_targets, const float *queries, uint32_t n_queries, uint32_t k, double max_dist,
+                   int32_t *idx, float *dist, uint32_t *count, nsa_stream_t stream);
+
+/* nsa_cloud_normals.  One row per neighbourhood i < m: the first c = count[i] slots of idx[i] ([m, k] int32) name points of the cloud
+ * points [n, 3], in the order nsa_nn_query_k wrote them.  All in float64 from the fp32 coordinates, every operation rounded on its own:
+ *   mu_a = ((((+0 + p_0a) + p_1a) + p_2a) + ...) / c;  d_j = p_j - mu;  S_ab = ((+0 + d_0a d_0b) + d_1a d_1b) + ...   (two passes)
+ *   cyclic Jacobi on S with V = I: pivots (p, q) = (0, 1), (0, 2), (1, 2) per sweep, g = a_pq.  g == 0: skipped.
+ *   |a_pp| + |g| == |a_pp| and |a_qq| + |g| == |a_qq|: a_pq = 0 without a rotation.  Else theta = (a_qq - a_pp) / (2 g),
+ *   t = 1 / (|theta| + sqrt(theta theta + 1)) (1 / (|theta| + |theta|) when |theta| > 2^500), negated when theta < 0,
+ *   c = 1 / sqrt(t t + 1), s = t c, h = t g;  a_pp -= h, a_qq += h, a_pq = 0;  with r the third index (a_rp, a_rq) = (c a_rp - s a_rq,
+ *   s a_rp + c a_rq);  for each row i of V (v_ip, v_iq) = (c v_ip - s v_iq, s v_ip + c v_iq).  The sweeps end with the first one that
+ *   finds the three off-diagonals zero, or after 16.
+ *   eigenvalues [m, 3] (may be NULL): the diagonal, ascending; equal values keep the order of their columns; a NaN is the quiet NaN
+ *   0x7FF8000000000000.  The normal is the column v of the smallest, v / sqrt((v_x v_x + v_y v_y) + v_z v_z), negated when
+ *   viewpoint_rows = 0 and its component of largest magnitude (ties: the lowest axis) is negative, or when viewpoint_rows > 0 and
+ *   ((n_x e_x + n_y e_y) + n_z e_z) < 0 with e = w - origin[i] and w = viewpoint[0] (viewpoint_rows = 1) or viewpoint[i]
+ *   (viewpoint_rows = m); then rounded once to fp32.
+ * valid [m] = 1 when 3 <= c <= k, every one of the c indices lies in [0, n), the three eigenvalues are finite and the middle one is
+ * > 0; otherwise 0 and the normal is (0, 0, 0), which nsa_icp_plane_system does not use.  A row with c = 0, c > k or an index outside
+ * [0, n) reads no point and has NaN eigenvalues.  tests/normals_ref.py restates all of it in numpy.
+ *
+ * k outside [1, 64], n or m >= 2^31, viewpoint_rows not 0, 1 or m: NSA_EBADARG.  m = 0 launches nothing and returns 0.  For m > 0 a NULL
+ * idx, count, origin, normals or valid, a NULL points with n > 0 or a NULL viewpoint with viewpoint_rows > 0: NSA_EBADARG before
+ * anything is launched. */
+int nsa_cloud_normals(const float *points, uint32_t n, const int32_t *idx, const uint32_t *count, uint32_t m, uint32_t k,
+                      const float *origin, const float *viewpoint, uint32_t viewpoint_rows, float *normals, double *eigenvalues,
+                      uint8_t *valid, nsa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

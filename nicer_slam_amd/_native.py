@@ -495,3 +495,9 @@ lib.nsa_icp_plane_system.argtypes = [_p, _u32, _i, _p, _p, _p, _p, _u32, _p, _p,
 EXPORTS += ["nsa_icp_transform", "nsa_icp_plane_system_workspace", "nsa_icp_plane_system"]
 ICP_CLOUD, ICP_SURFACE = 0, 1                                               # NSA_ICP_* of header Section 27
 ICP_KERNELS = ("l2", "huber", "tukey")                                      # NSA_ICP_KERNEL_*
+lib.nsa_nn_query_k.restype = _i
+lib.nsa_nn_query_k.argtypes = [_p, _u32, _p, _u32, _u32, _f64, _p, _p, _p, _p]
+lib.nsa_cloud_normals.restype = _i
+lib.nsa_cloud_normals.argtypes = [_p, _u32, _p, _p, _u32, _u32, _p, _p, _u32, _p, _p, _p, _p]
+EXPORTS += ["nsa_nn_query_k", "nsa_cloud_normals"]
+KNN_MAX_K = 64                                                              # header Section 28

@@ -24,6 +24,7 @@
 // margin of 2^-9 cell (the fp32 cell index is off by less than 2^-12 cell), combined with the query's distance to the targets'
 // bounding box on the other axes.  Clamped targets only lie beyond the border planes, so the bound holds for them too.
 // Worst case: every target in one cell (exact duplicates) -- each query reads all n points.
+// k_nn_query_k (C ABI Section 28) walks the same rings for the k smallest under the total order (d2, index).
 //
 // Surface sampling (trimesh.sample.sample_surface): areas 0.5 |(v1 - v0) x (v2 - v0)| in float64; a sequential inclusive scan
 // in LDS per block of 1024 faces (k_area_scan; the blocks in parallel) and a sequential carry over the blocks (k_area_offsets)
@@ -37,6 +38,7 @@
 #include "draw_common.hpp"
 #include "grid_common.hpp"
 #include "mesh_area.hpp"
+#include "normals_passes.hpp"
 #include "radix_sort.hpp"
 
 namespace nsa {
@@ -287,6 +289,105 @@ __global__ __launch_bounds__(256) void k_nn_query(NnIndex ix, const float* __res
     out_dist[j] = b.idx >= 0 ? sqrt_rn(b.d2) : INFINITY;
 }
 
+// ---- k nearest neighbours (header Section 28) ---------------------------------------------------------------------------
+// The ring walk of k_nn_query with the k-th best in the place of the best: until k candidates are held the bound is r2.  Each lane keeps
+// its candidates as 64-bit keys (normals_passes.hpp), ascending, in LDS: slot-major, s_keys[slot][lane], one wave per workgroup, so the
+// lanes of a wave touch 64 different columns whatever slot each of them is at.  CAP slots: 8 bytes * 64 lanes * CAP per workgroup.
+
+__device__ __forceinline__ void nn_visit_k(const NnIndex& ix, uint32_t c, float qx, float qy, float qz, uint64_t* keys, uint32_t k,
+                                           uint32_t& held, uint64_t& worst, float r2, bool strict) {
+#pragma clang fp contract(off)
+    const uint32_t s = ix.start[c], e = ix.start[c + 1];
+    if (s == e) return;
+    const float* bx = ix.box + 6ull * c;
+    const float gx = box_gap(qx, bx[0], bx[3]), gy = box_gap(qy, bx[1], bx[4]), gz = box_gap(qz, bx[2], bx[5]);
+    if ((gx * gx + gy * gy) + gz * gz > cn::knn_bound(held, k, worst, r2)) return;
+    for (uint32_t i = s; i < e; ++i) {
+        const float4 p = ix.spts[i];
+        cn::knn_offer(keys, 64, k, held, worst, sq_dist(p.x, p.y, p.z, qx, qy, qz), __float_as_uint(p.w), r2, strict);
+    }
+}
+
+template <uint32_t CAP>
+__global__ __launch_bounds__(64) void k_nn_query_k(NnIndex ix, const float* __restrict__ q, uint32_t m, uint32_t k, float r2, bool strict,
+                                                   int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                                                   uint32_t* __restrict__ out_count) {
+    __shared__ uint64_t s_keys[CAP * 64];
+    const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= m) return;
+    uint64_t* keys = s_keys + threadIdx.x;
+    const float qx = q[3ull * j], qy = q[3ull * j + 1], qz = q[3ull * j + 2];
+    const NnGrid g = *ix.grid;
+    int32_t* oi = out_idx + (uint64_t)j * k;
+    float* od = out_dist + (uint64_t)j * k;
+    if (!finite3(qx, qy, qz)) {
+        for (uint32_t s = 0; s < k; ++s) {
+            oi[s] = -1;
+            od[s] = __builtin_nanf("");
+        }
+        out_count[j] = 0;
+        return;
+    }
+    uint32_t held = 0;
+    uint64_t worst = 0;
+    if (ix.start[g.ncells] > 0) {                      // some target is finite
+        const float qv[3] = {qx, qy, qz};
+        int c0[3];
+        double out2[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            c0[a] = (int)axis_cell(qv[a], g.lo[a], g.inv_h[a], g.R[a]);
+            const double o = fmax(fmax((double)g.gmin[a] - qv[a], (double)qv[a] - g.gmax[a]), 0.0);
+            out2[a] = o * o;
+        }
+        const int R0 = (int)g.R[0], R1 = (int)g.R[1], R2 = (int)g.R[2];
+        for (int r = 0;; ++r) {
+            if (r > 0) {                                // lower bound over every cell at index distance >= r (as k_nn_query)
+                double lb2 = INFINITY;
+                bool any = false;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const double h = g.h[a], margin = h * 0x1p-9, lo = g.lo[a], qk = qv[a];
+                    const double rest = out2[0] + out2[1] + out2[2] - out2[a];
+                    const double ok = sqrt(out2[a]);
+                    if (c0[a] + r <= (int)g.R[a] - 1) {
+                        const double gap = fmax(fmax(lo + (double)(c0[a] + r) * h - qk - margin, ok), 0.0);
+                        lb2 = fmin(lb2, gap * gap + rest);
+                        any = true;
+                    }
+                    if (c0[a] - r >= 0) {
+                        const double gap = fmax(fmax(qk - (lo + (double)(c0[a] - r + 1) * h) - margin, ok), 0.0);
+                        lb2 = fmin(lb2, gap * gap + rest);
+                        any = true;
+                    }
+                }
+                if (!any || lb2 > (double)cn::knn_bound(held, k, worst, r2) * (1.0 + 0x1p-18)) break;
+            }
+            const int x0 = max(c0[0] - r, 0), x1 = min(c0[0] + r, R0 - 1);
+            const int y0 = max(c0[1] - r, 0), y1 = min(c0[1] + r, R1 - 1);
+            const int z0 = max(c0[2] - r, 0), z1 = min(c0[2] + r, R2 - 1);
+            for (int x = x0; x <= x1; ++x) {
+                const bool ex = x == c0[0] - r || x == c0[0] + r;
+                for (int y = y0; y <= y1; ++y) {
+                    const uint32_t row = ((uint32_t)x * g.R[1] + (uint32_t)y) * g.R[2];
+                    if (ex || y == c0[1] - r || y == c0[1] + r) {
+                        for (int z = z0; z <= z1; ++z) nn_visit_k(ix, row + z, qx, qy, qz, keys, k, held, worst, r2, strict);
+                    } else {
+                        if (c0[2] - r >= 0) nn_visit_k(ix, row + (c0[2] - r), qx, qy, qz, keys, k, held, worst, r2, strict);
+                        if (r > 0 && c0[2] + r < R2) nn_visit_k(ix, row + (c0[2] + r), qx, qy, qz, keys, k, held, worst, r2, strict);
+                    }
+                }
+            }
+        }
+    }
+    for (uint32_t s = 0; s < k; ++s) {
+        const uint64_t key = s < held ? keys[s * 64] : 0;
+        oi[s] = s < held ? (int32_t)(uint32_t)key : -1;
+        od[s] = s < held ? cn::knn_root(__uint_as_float((uint32_t)(key >> 32))) : INFINITY;
+    }
+    out_count[j] = held;
+}
+
 // ---- surface sampling ---------------------------------------------------------------------------------------------------------
 
 constexpr uint32_t kAreaBlock = 1024;
@@ -421,6 +522,27 @@ int nsa_nn_query(const void* index, uint32_t n_targets, const float* queries, ui
     launch_begin();
     hipLaunchKernelGGL(k_nn_query, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream, ix, queries, n_queries, r2,
                        strict, idx, dist);
+    return launch_end();
+}
+
+int nsa_nn_query_k(const void* index, uint32_t n_targets, const float* queries, uint32_t n_queries, uint32_t k, double max_dist,
+                   int32_t* idx, float* dist, uint32_t* count, nsa_stream_t stream) {
+    using namespace nsa;
+    if (!index || n_targets == 0 || n_targets > kMaxCount || n_queries > kMaxCount || !(max_dist > 0.0)) return NSA_EBADARG;
+    if (k < 1 || k > cn::kMaxK) return NSA_EBADARG;
+    if (n_queries && (!queries || !idx || !dist || !count)) return NSA_EBADARG;
+    if (n_queries == 0) return NSA_OK;
+    NnIndex ix;
+    nn_carve(const_cast<void*>(index), n_targets, &ix);
+    const bool strict = max_dist < INFINITY;
+    const float r2 = strict ? (float)(max_dist * max_dist) : INFINITY;
+    const dim3 grid((n_queries + 63) / 64), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    launch_begin();
+    if (k <= 8) hipLaunchKernelGGL(k_nn_query_k<8>, grid, block, 0, s, ix, queries, n_queries, k, r2, strict, idx, dist, count);
+    else if (k <= 16) hipLaunchKernelGGL(k_nn_query_k<16>, grid, block, 0, s, ix, queries, n_queries, k, r2, strict, idx, dist, count);
+    else if (k <= 32) hipLaunchKernelGGL(k_nn_query_k<32>, grid, block, 0, s, ix, queries, n_queries, k, r2, strict, idx, dist, count);
+    else hipLaunchKernelGGL(k_nn_query_k<64>, grid, block, 0, s, ix, queries, n_queries, k, r2, strict, idx, dist, count);
     return launch_end();
 }
 

@@ -2,6 +2,7 @@
 trimesh's surface sampling.
 
 * ``NNIndex`` / ``nearest``: exact fp32 nearest neighbours (C ABI Section 8, csrc/mesh_eval.hip), ties to the lowest index.
+  ``NNIndex.knn`` / ``nearest_k``: the k nearest under the total order (d2, index) (C ABI Section 28).
 * ``sample_surface``: area-weighted surface samples from the engine's Philox stream (trimesh.sample.sample_surface).
 * ``icp_point_to_point``: open3d's registration_icp with TransformationEstimationPointToPoint and default criteria;
   ``with_scaling`` estimates a scale as well (CloudCompare's -ICP -ADJUST_SCALE, eval_rec.py:274).
@@ -29,7 +30,7 @@ import math
 import numpy as np
 import torch
 
-from ._native import RAY_ANY_HIT, RAY_BRUTE, RAY_CULL_BACK, RAY_CULL_FRONT, check, lib
+from ._native import KNN_MAX_K, RAY_ANY_HIT, RAY_BRUTE, RAY_CULL_BACK, RAY_CULL_FRONT, check, lib
 
 F_THRESHOLDS = (0.010, 0.015, 0.020)       # np.linspace(1/1000, 1, 1000)[[9, 14, 19]] of eval_pointcloud
 COMPLETION_RATIO_THRESHOLD = 0.05          # completion_ratio's dist_th (eval_rec.py:168)
@@ -77,6 +78,32 @@ class NNIndex:
                                    torch.cuda.current_stream(q.device).cuda_stream))
         return dist, idx.long()
 
+    @torch.no_grad()
+    def _knn(self, q, k, max_dist, name="NNIndex.knn"):
+        """nsa_nn_query_k on checked fp32 queries: (dist [m, k] fp32, idx [m, k] int32, count [m] int32 holding the uint32 counts)"""
+        if q.device != self.device:
+            raise ValueError(f"{name}: queries on another device than the index")
+        if not (isinstance(k, int) and 1 <= k <= KNN_MAX_K):
+            raise ValueError(f"{name}: k must be an integer in [1, {KNN_MAX_K}], got {k!r}")
+        if not max_dist > 0:
+            raise ValueError(f"{name}: max_dist must be > 0")
+        m = q.shape[0]
+        idx = torch.empty(m, k, dtype=torch.int32, device=q.device)
+        dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
+        count = torch.empty(m, dtype=torch.int32, device=q.device)
+        if m:
+            check(lib.nsa_nn_query_k(self.buf.data_ptr(), self.n, q.data_ptr(), m, k, float(max_dist), idx.data_ptr(), dist.data_ptr(),
+                                     count.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
+        return dist, idx, count
+
+    def knn(self, queries, k, max_dist=math.inf):
+        """(dist [m, k] fp32, idx [m, k] int64, count [m] int64): the ``k`` (1 .. 64) nearest targets of each query under the total
+        order (d2, target index), in that order (C ABI Section 28): exact ties go to the lower index, at the k-th place too.  With a
+        finite ``max_dist`` only targets with d2 < fp32(max_dist^2) count.  ``count`` is the number found; the slots behind it hold
+        (+inf, -1).  A non-finite query gives count 0 and (NaN, -1).  ``knn(q, 1)`` is ``query(q)`` with a column axis."""
+        dist, idx, count = self._knn(_points(queries, "NNIndex.knn"), k, max_dist)
+        return dist, idx.long(), count.long()
+
     def grid(self):
         """(lo [3], cell size [3], cells per axis [3], per-cell point counts [Rx, Ry, Rz]) of the built grid (host copies;
         a synchronisation -- for measurements, not for the query path)."""
@@ -93,6 +120,12 @@ class NNIndex:
 def nearest(queries, targets, max_dist=math.inf):
     """(dist, idx) of the nearest target of each query (``NNIndex(targets).query(queries, max_dist)``)."""
     return NNIndex(targets).query(queries, max_dist)
+
+
+@torch.no_grad()
+def nearest_k(queries, targets, k, max_dist=math.inf):
+    """(dist, idx, count) of the ``k`` nearest targets of each query (``NNIndex(targets).knn(queries, k, max_dist)``)."""
+    return NNIndex(targets).knn(queries, k, max_dist)
 
 
 @torch.no_grad()

@@ -9,7 +9,7 @@ Section 27, csrc/mesh_register.hip).
 * ``plane_system(cur, ...)``: one iteration's 6x6 normal equations from given correspondences -- the thirty float64 sums and two counts
   of header Section 27.
 * ``python -m nicer_slam_amd.mesh_register SRC.ply TGT.ply [--metric plane|surface] [--max-corr D] [--kernel l2|huber:K|tukey:K]
-  [--init T.npy] [--out-transform T.npy] [--out MOVED.ply] [--json]``
+  [--estimate-normals [K]] [--init T.npy] [--out-transform T.npy] [--out MOVED.ply] [--json]``
 
 Every sum runs in float64 in an order that depends on the number of rows alone, every operation rounded on its own; the 6x6 solve
 is plain float64 arithmetic on the host in a stated order.  The result is the same bits on every run and equals the numpy statement in
@@ -17,8 +17,8 @@ tests/register_ref.py bit for bit.  Per iteration: one launch that moves the sou
 above 2^20 rows) and one readback of 32 words.
 
 Not built: a scale together with point-to-plane (``mesh_eval.icp_point_to_point(with_scaling=True)`` estimates one), symmetric and
-coloured ICP, and normal estimation for raw clouds (``mesh_smooth.vertex_normals`` gives a mesh's).  There is no CPU path: a missing
-GPU is an error.
+coloured ICP.  A raw cloud's normals come from ``cloud_normals.estimate_normals`` (``normals="estimate"``, ``--estimate-normals``), a
+mesh's from ``mesh_smooth.vertex_normals``.  There is no CPU path: a missing GPU is an error.
 """
 import argparse
 import ctypes
@@ -198,6 +198,8 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
     (the nearest target with d2 < fp32(max_corr^2)) -- or a mesh dict, a ``(verts, faces)`` pair or a ``TriIndex`` -- SURFACE mode: each
     source point's closest point ON the mesh and that face's normal, accepted by ``TriIndex.query(points, max_dist=max_corr)``'s rule
     (d2 <= max_corr^2).  ``index``: a prebuilt NNIndex (cloud) or TriIndex (surface) of the target.
+    ``normals="estimate"`` or ``normals=dict(k=..., max_dist=..., viewpoint=...)``: a raw cloud target; its normals are estimated once, on
+    the NNIndex the loop queries, by ``cloud_normals.estimate_normals``.  Targets without a valid normal are matched but not used.
     Each iteration minimises sum w(r) r^2 over the linearised motion, r = n . (p - q): the 6x6 system of header Section 27, solved by
     ``ldlt_solve``; the update ``update_matrix(x)`` is left-multiplied onto the transformation and moves the float64 source.  Residual
     and Jacobian change sign together with the normal, so neither the winding of the mesh nor the side the cloud's normals point to
@@ -231,12 +233,21 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
         if not torch.is_tensor(target):
             target = torch.as_tensor(np.asarray(target, np.float32)).reshape(-1, 3).to(dev)
         tgt = _points(target, "icp_point_to_plane")
-        nrm = _cuda(normals, torch.float32, dev)
-        if nrm.shape != tgt.shape:
-            raise ValueError(f"icp_point_to_plane: {tuple(nrm.shape)} normals for {tuple(tgt.shape)} targets")
+        if isinstance(normals, str) and normals != "estimate":
+            raise ValueError(f"icp_point_to_plane: normals must be [m, 3], 'estimate' or dict(k=, max_dist=, viewpoint=), got {normals!r}")
+        estimate = normals if isinstance(normals, dict) else ({} if isinstance(normals, str) else None)
+        if estimate is None:
+            nrm = _cuda(normals, torch.float32, dev)
+            if nrm.shape != tgt.shape:
+                raise ValueError(f"icp_point_to_plane: {tuple(nrm.shape)} normals for {tuple(tgt.shape)} targets")
+        elif not set(estimate) <= {"k", "max_dist", "viewpoint"}:
+            raise ValueError(f"icp_point_to_plane: normals=dict(...) takes k, max_dist and viewpoint, got {sorted(estimate)}")
         index = index if index is not None else NNIndex(tgt)
         if not isinstance(index, NNIndex) or index.n != tgt.shape[0]:
             raise ValueError("icp_point_to_plane: a cloud target takes an NNIndex of the same targets")
+        if estimate is not None:                       # once, on the index the loop queries anyway
+            from .cloud_normals import estimate_normals
+            nrm = estimate_normals(tgt, index=index, **estimate)
         if not float(max_corr) > 0:
             raise ValueError("icp_point_to_plane: max_corr must be > 0")
     if index.device != dev:
@@ -310,6 +321,8 @@ def main(argv=None):
                     help="plane: SRC's vertices against TGT's vertices and their angle-weighted normals; surface: against TGT's faces")
     ap.add_argument("--max-corr", type=float, default=0.1)
     ap.add_argument("--kernel", type=_parse_kernel, default="l2", metavar="l2|huber:K|tukey:K")
+    ap.add_argument("--estimate-normals", type=int, nargs="?", const=30, default=None, metavar="K",
+                    help="TGT is a cloud without nx ny nz: point-to-plane against its vertices with normals estimated from K neighbours")
     ap.add_argument("--init", metavar="T.npy", help="4x4 applied to SRC first")
     ap.add_argument("--out-transform", metavar="T.npy")
     ap.add_argument("--out", metavar="MOVED.ply", help="SRC moved by the result")
@@ -322,7 +335,10 @@ def main(argv=None):
         src, tgt = read_ply(a.source), read_ply(a.target)
         init = np.load(a.init) if a.init else None
         sv = torch.as_tensor(np.asarray(src["verts"]), dtype=torch.float32).cuda()
-        if a.metric == "plane":
+        if a.estimate_normals is not None:
+            r = icp_point_to_plane(sv, torch.as_tensor(np.asarray(tgt["verts"]), dtype=torch.float32).cuda(),
+                                   dict(k=a.estimate_normals), a.max_corr, init, kernel=a.kernel)
+        elif a.metric == "plane":
             r = icp_point_to_plane(sv, torch.as_tensor(np.asarray(tgt["verts"]), dtype=torch.float32).cuda(),
                                    torch.as_tensor(np.asarray(vertex_normals(tgt, "angle"))), a.max_corr, init, kernel=a.kernel)
         else:
