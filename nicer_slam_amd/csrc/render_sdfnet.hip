@@ -211,11 +211,20 @@ __global__ __launch_bounds__(256, (NH == 1 ? 2 : NSA_OCC_FWD_FINE)) void k_sdfne
     // outputs: sdf (row 0, VALU dot) and the 64 features (rows 1..64)
     f32x16 ws[2], fo[2];
     load_vec<2>(a.wp + P::kWSDF, h, ws);
+#if NSA_PIECES == 1     // (bf16-operand build: four chains of eight added pairwise, see render_sdfnet4.hip::sdf_row_dot4)
+    float p4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) p4[r & 3] = fmaf(hl[16 * t + r], ws[t][r], p4[r & 3]);
+    const float part = (p4[0] + p4[1]) + (p4[2] + p4[3]);
+#else
     float part = 0.0f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) part = fmaf(hl[16 * t + r], ws[t][r], part);
+#endif
     float sdf = xhalf_sum(part) + a.wp[P::kBSDF];
     load_vec<2>(a.wp + P::kBFEAT, h, fo);
     gemm_staged<Seq, HS, 2>(stage, a.wp, NH, lane, hl, fo);

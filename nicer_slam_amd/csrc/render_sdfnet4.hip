@@ -29,6 +29,23 @@ namespace nsa {
 #endif
 constexpr int stage_floats4(int nw) { return nw >= 8 ? 9216 : 6144; }
 
+// The sdf row of the last layer: this lane's 16 products of the VALU dot.  The fp32 build sums them in one fmaf chain.  In the
+// bf16-operand build the GEMMs in front of it are exact products of rounded operands, so the chain's own rounding is what is left of
+// the sdf's error (tests/test_gemm_bf16_gpu.py: 1.2-1.55 x the fp32 emulation's rms); four chains of four, added pairwise, halve it.
+__device__ __forceinline__ float sdf_row_dot4(const float (&hl)[QHS], const f32x4v (&ws)[4]) {
+#if NSA_PIECES == 1
+    float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < QHS; ++s) p[s & 3] = fmaf(hl[s], ws[s >> 2][s & 3], p[s & 3]);
+    return (p[0] + p[1]) + (p[2] + p[3]);
+#else
+    float part = 0.0f;
+#pragma unroll
+    for (int s = 0; s < QHS; ++s) part = fmaf(hl[s], ws[s >> 2][s & 3], part);
+    return part;
+#endif
+}
+
 struct SdfNet4Args {
     PointSrc src;
     const float* table;
@@ -257,9 +274,7 @@ __global__ __launch_bounds__(64 * NSA_NW4_FWD, NSA_OCC4_FWD) void k_sdfnet4_fwd(
     // outputs: sdf (row 0, VALU dot) and the 64 features (rows 1..64)
     f32x4v ws[4], fo[4];
     load_vec16(a.wp + P::kWSDF, q, ws);
-    float part = 0.0f;
-#pragma unroll
-    for (int s = 0; s < QHS; ++s) part = fmaf(hl[s], ws[s >> 2][s & 3], part);
+    const float part = sdf_row_dot4(hl, ws);
     float sdf = quad_sum(part) + a.wp[P::kBSDF];
     load_vec16(a.wp + P::kBFEAT, q, fo);
     gemm16_staged<Seq, Seq::NW, Seq::BUF, 2, 4>(stage, a.wp, NH, lane, hl, fo);
@@ -306,9 +321,7 @@ __device__ __forceinline__ void net_forward4(float* stage, int op0, const float*
     hidden_forward4<NH, Seq>(stage, op0, wp, lane, q, in, sg, hl, nullptr, s0, s1);
     f32x4v ws[4];
     load_vec16(wp + P::kWSDF, q, ws);
-    float part = 0.0f;
-#pragma unroll
-    for (int s = 0; s < QHS; ++s) part = fmaf(hl[s], ws[s >> 2][s & 3], part);
+    const float part = sdf_row_dot4(hl, ws);
     sdf = quad_sum(part) + wp[P::kBSDF];
     load_vec16(wp + P::kBFEAT, q, fo);
     gemm16_staged<Seq, Seq::NW, Seq::BUF, 2, 4>(stage, s0, op0 + NH, lane, hl, fo, s1);

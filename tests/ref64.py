@@ -14,7 +14,21 @@ colour_table_grad give the table gradients the mapping kernels accumulate -- the
 share of the double backward through grad sdf.  The default stays the linearisation.
 
 Inputs are the explicit fp32 tensors the kernels see; ``dtype=torch.float32`` evaluates the same graph in fp32 (tests/test_ref64_cpu.py
-holds that to oracle/render_ref.py)."""
+holds that to oracle/render_ref.py).
+
+``quant=Quant(...)`` is the bf16-operand mode (what csrc/*_bf16.hip computes, NSA_PIECES == 1; the same dataflow as
+oracle/render_ref.py::_LinQ, in any dtype): both operands of every matrix-core GEMM are rounded to bfloat16, round to nearest even,
+products are exact, accumulation is in the working dtype; every derivative GEMM rounds the vector it multiplies, recursively (the
+second-order sweeps through grad sdf included); the rounding has derivative 1.  Unrounded stay the sdf row of an SDF network's last
+layer, the colour network's 64 -> 3 layer and everything the kernels do on the vector ALU.  The weights are the effective FP32
+matrices (``Quant.weights``: what fused/pack.py::flat_params gives on the device, copied to the host; default: the oracle's fp32
+weight norm), rounded once -- never a float64 weight norm: one weight that rounds the other way moves every point.
+While it rounds, a Quant records every operand matrix (activations, cotangents, tangents: the forward graph and every backward
+through it), from which ``Margin`` forms the per-point ROUNDING MARGIN: how far every rounded operand of the point lies from the
+nearest rounding boundary (the midpoint of two neighbouring bf16 values), in units of the measured fp32 noise of the vector the
+operand belongs to (class Margin states the unit).  On a point that is kept, two correct implementations take the same rounding
+decisions and agree to working-precision noise; the others may flip (tests/bf16_gate.py).  ``Quant.margin`` is the same distance
+in units of the operand's own bf16 spacing (no knowledge of the noise), kept for the report."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -67,16 +81,180 @@ def _pe(x, n_freq):
     return torch.cat(parts, -1)
 
 
-def _lin(params, prefix, h, dtype):
-    g, v, b = (params[f"{prefix}.{k}"].to(dtype) for k in ("weight_g", "weight_v", "bias"))
-    return F.linear(h, v * (g / v.norm(2, dim=1, keepdim=True)), b)
+def rne_bf16(x):
+    """x (any float dtype) -> the nearest bfloat16 value, ties to even, in x's dtype, in ONE rounding (a float64 value must not pass
+    through fp32 on its way), and the distance of x to the nearest rounding boundary in units of x's bf16 spacing."""
+    m, e = torch.frexp(x)                                  # |m| in [0.5, 1): m * 256 has 8 bits in front of the binary point
+    t = m * 256
+    r = torch.round(t)                                     # half to even
+    return torch.ldexp(r, e - 8), 0.5 - (t - r).abs()
 
 
-def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None):
+FAULTS = ("truncated weights", "unrounded cotangents", "neighbour's operand group", "rounded sdf row")
+
+
+class Quant:
+    """The bf16-operand mode of this module (module docstring) and the per-point rounding margin of the last call.
+    weights: {"<network>.lin<l>": (W fp32 [out, in], b fp32 [out])} -- the effective matrices the pack takes (weights_of_model);
+    None: the oracle's fp32 weight norm of ``params`` on the host.
+    order: "natural" | "permuted" | ("permuted", seed) -- the k order of every GEMM's sum (correct emulations in fp32).
+    fault: None, or one of FAULTS: a deliberately WRONG emulation (tests/test_ref64_bf16_cpu.py: the gate must refuse each)."""
+
+    def __init__(self, weights=None, order="natural", fault=None):
+        assert (order in ("natural", "permuted") or order[0] == "permuted") and (fault is None or fault in FAULTS), (order, fault)
+        self.weights, self.order, self.fault = weights, order, fault
+        self._w, self._perm = {}, {}
+        self.trace = []                     # every operand matrix [P, K] as it reached a rounding, in order (Margin)
+        self.margin = None                  # [P] smallest distance to a boundary in units of the operand's OWN bf16 spacing
+        self.relu_margin = None             # [P] colour network: min |pre-activation| of its ReLU units
+
+    def reset(self, P):
+        """called where a graph is built; a Quant that serves several graphs of the same points keeps accumulating"""
+        if self.margin is None:
+            self.margin = torch.full((P,), 0.5, dtype=F64)
+            self.relu_margin = torch.full((P,), float("inf"), dtype=F64)
+        assert self.margin.shape[0] == P
+
+    def weight(self, params, prefix, dtype):
+        key = (prefix, dtype)
+        if key not in self._w:
+            if self.weights is not None:
+                w, b = self.weights[prefix]
+            else:
+                g, v, b = (params[f"{prefix}.{k}"].float() for k in ("weight_g", "weight_v", "bias"))
+                w = v * (g / v.norm(2, dim=1, keepdim=True))
+            assert w.dtype == torch.float32 and b.dtype == torch.float32
+            w = w.detach().cpu().to(dtype)
+            if self.fault == "truncated weights":
+                m, e = torch.frexp(w)
+                wr = torch.ldexp(torch.trunc(m * 256), e - 8)
+            else:
+                wr = rne_bf16(w)[0]
+            self._w[key] = (w, wr, b.detach().cpu().to(dtype))
+        return self._w[key]
+
+    def round(self, x, cotangent):
+        if cotangent and self.fault == "unrounded cotangents":
+            return x
+        r, margin = rne_bf16(x)
+        self.margin = torch.minimum(self.margin, margin.reshape(margin.shape[0], -1).amin(1).double())
+        self.trace.append(x.detach())
+        if not cotangent and self.fault == "neighbour's operand group" and x.shape[1] == 64:
+            p = torch.arange(0, x.shape[0] - 1, 16)
+            r = r.clone()
+            r[p, 8:16] = r[p + 1, 8:16]
+        return r
+
+    def matmul(self, xr, wr):
+        if self.order != "natural":
+            K = wr.shape[1]
+            if K not in self._perm:
+                seed = 0 if self.order == "permuted" else int(self.order[1])
+                self._perm[K] = torch.randperm(K, generator=torch.Generator().manual_seed(K + 1000 * seed))
+            return xr[:, self._perm[K]] @ wr[:, self._perm[K]].t()
+        return xr @ wr.t()
+
+
+class Margin:
+    """The per-point ROUNDING MARGIN of one reference call, from the Quant of its float64-accumulating evaluation (q64) and the Quants
+    of fp32-accumulating evaluations of it (q32s: natural and permuted summation order) -- the same graph, so the same operand
+    matrices in the same order.
+
+    UNIT: the operand's own fp32 noise, measured: nu = the largest |fp32 - float64| difference of that operand before rounding over
+    the fp32 evaluations (floor: half an fp32 spacing of the operand).  An operand's bf16 spacing does not know that noise: an entry
+    that is small beside the sums it came out of (a Softplus output near ln 2 / 100, a cancelled sum, beta = 100 times the noise of a
+    pre-activation) carries many of its own fp32 spacings of noise and flips at margins of 1e-3 of its bf16 spacing, while an entry
+    with noise of its own size is safe at 1e-5 of it.  In this unit one threshold fits both.
+    A point is KEPT at threshold t when every rounded operand x of it either lies at least t nu from the nearest rounding boundary, or
+    is so noisy that a flip moves it by no more than 2 t nu (bf16 spacing of x <= 2 t nu: such an operand can never be t nu from a
+    boundary, and its flip is of the size of the noise that the threshold tolerates anyway).  A point where an fp32 evaluation itself
+    flipped has a large nu downstream and drops out.  kept(t) is computed for the thresholds given at construction."""
+
+    def __init__(self, q64, q32s, thresholds):
+        assert q32s and all(len(q64.trace) == len(q.trace) for q in q32s) and len(q64.trace) > 0
+        self.own, self.relu_margin, self.n_operands = q64.margin, q64.relu_margin, len(q64.trace)
+        self._kept = {t: torch.ones(q64.margin.shape[0], dtype=torch.bool) for t in thresholds}
+        for i, x64 in enumerate(q64.trace):
+            assert x64.dtype == F64
+            nu = 2.0 ** -24 * x64.abs()
+            for q in q32s:
+                nu = torch.maximum(nu, (q.trace[i].double() - x64).abs())
+            m, e = torch.frexp(x64)
+            t = m * 256
+            spacing = torch.ldexp(torch.ones_like(x64), e - 8)
+            dist = (0.5 - (t - torch.round(t)).abs()) * spacing
+            for thr, kept in self._kept.items():
+                kept &= ((dist >= thr * nu) | (spacing <= 2 * thr * nu)).all(1)
+
+    def kept(self, threshold):
+        return self._kept[threshold]
+
+
+class _RoundQ(torch.autograd.Function):
+    """x -> bf16(x), derivative 1 (the rounding of a GEMM operand is not part of the differentiated graph)"""
+
+    @staticmethod
+    def forward(ctx, x, q, cotangent):
+        return q.round(x, cotangent)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None
+
+
+class _LinQ(torch.autograd.Function):
+    """y = xr wr^T on rounded operands; every derivative GEMM rounds the vector it multiplies, recursively"""
+
+    @staticmethod
+    def forward(ctx, xr, wr, q):
+        ctx.wr, ctx.q = wr, q
+        return q.matmul(xr, wr)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _LinQ.apply(_RoundQ.apply(g, ctx.q, True), ctx.wr.t().contiguous(), ctx.q), None, None
+
+
+def _lin(params, prefix, h, dtype, quant=None, exact_rows=0):
+    """quant: rows [exact_rows:] are matrix-core rows (bf16 operands), rows [:exact_rows] vector-ALU rows (unrounded)"""
+    if quant is None:
+        g, v, b = (params[f"{prefix}.{k}"].to(dtype) for k in ("weight_g", "weight_v", "bias"))
+        return F.linear(h, v * (g / v.norm(2, dim=1, keepdim=True)), b)
+    w, wr, b = quant.weight(params, prefix, dtype)
+    if quant.fault == "rounded sdf row" and exact_rows < w.shape[0]:
+        exact_rows = 0
+    parts = []
+    if exact_rows:
+        parts.append(F.linear(h, w[:exact_rows], b[:exact_rows]))
+    if exact_rows < w.shape[0]:
+        parts.append(_LinQ.apply(_RoundQ.apply(h, quant, False), wr[exact_rows:], quant) + b[exact_rows:])
+    return torch.cat(parts, dim=-1)
+
+
+def weights_of_model(model):
+    """Quant.weights of a SLAMNetwork on the GPU: the effective fp32 matrices exactly as the packs take them
+    (fused/pack.py::flat_params, computed on the device), split per layer and copied to the host."""
+    from nicer_slam_amd.fused import pack
+    out = {}
+    nets = {"implicit_network.coarse": model.implicit_network.coarse, "implicit_network.fine": model.implicit_network.fine,
+            "rendering_network": model.rendering_network}
+    for prefix, net in nets.items():
+        with torch.no_grad():
+            flat = pack.flat_params(net).detach().cpu()
+        o = 0
+        for l in range(net.num_layers - 1):
+            rows, cols = getattr(net, f"lin{l}").weight_v.shape
+            out[f"{prefix}.lin{l}"] = (flat[o:o + rows * cols].view(rows, cols).clone(), flat[o + rows * cols:o + rows * cols + rows].clone())
+            o += rows * cols + rows
+        assert o + 1 == flat.numel(), (prefix, o, flat.numel())
+    return out
+
+
+def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None, quant=None):
     feat = _grid(exact, prefix, x, x0, params[prefix + ".encoding.embeddings"], spec.grid, spec.divide_factor, dtype)
     h = torch.cat((_pe(x, spec.multires), feat), dim=-1)
     for l in range(spec.n_linear):
-        h = _lin(params, f"{prefix}.lin{l}", h, dtype)
+        h = _lin(params, f"{prefix}.lin{l}", h, dtype, quant, exact_rows=1 if l == spec.n_linear - 1 else 0)
         if l < spec.n_linear - 1:
             h = F.softplus(h, beta=100)
     return h
@@ -85,11 +263,14 @@ def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None):
 NETS = {"coarse": "implicit_network.coarse", "fine": "implicit_network.fine"}
 
 
-def _sdf_graph(params, cfg, x0, nets, dtype, exact=None):
+def _sdf_graph(params, cfg, x0, nets, dtype, exact=None, quant=None):
+    assert quant is None or exact is None, "quant: linearised grids only"
+    if quant is not None:
+        quant.reset(x0.shape[0])
     x = x0.detach().to(dtype).requires_grad_(True)
     sdf, feat, grad = 0, 0, 0
     for which in nets:
-        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype, exact)
+        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype, exact, quant)
         s = out[:, 0]
         (g,) = torch.autograd.grad(s, x, torch.ones_like(s), create_graph=True)
         sdf, feat, grad = sdf + s, feat + out[:, 1:], grad + g
@@ -101,9 +282,9 @@ def _exact(grid):
     return ExactGrids() if grid == "exact" else None
 
 
-def sdf_forward(params, cfg, x0, nets=("coarse", "fine"), dtype=F64, grid="linear"):
+def sdf_forward(params, cfg, x0, nets=("coarse", "fine"), dtype=F64, grid="linear", quant=None):
     """-> sdf [P], grad sdf [P,3], feature [P,64] of the networks in ``nets`` (summed: the COMBINE for both)."""
-    _x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid))
+    _x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid), quant)
     return sdf.detach(), grad.detach(), feat.detach()
 
 
@@ -115,9 +296,9 @@ def _sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype):
     return obj
 
 
-def sdf_backward(params, cfg, x0, g_sdf=None, g_feat=None, g_grad=None, nets=("coarse", "fine"), dtype=F64, grid="linear"):
+def sdf_backward(params, cfg, x0, g_sdf=None, g_feat=None, g_grad=None, nets=("coarse", "fine"), dtype=F64, grid="linear", quant=None):
     """d/dx of  g_sdf . sdf + g_feat . feature + g_grad . grad sdf  (any cotangent may be None = absent) -> [P,3]."""
-    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid))
+    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, nets, dtype, _exact(grid), quant)
     obj = _sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype)
     if not torch.is_tensor(obj):
         return torch.zeros_like(x).detach()
@@ -140,28 +321,33 @@ def sdf_table_grad(params, cfg, x0, which, g_sdf=None, g_feat=None, g_grad=None,
     return gx, gt, plan
 
 
-def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact=None):
+def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact=None, quant=None):
+    assert quant is None or exact is None, "quant: linearised grids only"
+    if quant is not None:
+        quant.reset(x0.shape[0])
     x, n, d, f = (t.detach().to(dtype).requires_grad_(True) for t in (x0, normals, dirs, feats))
     gf = _grid(exact, "colour", x, x0, params["rendering_network.encoding.embeddings"], cfg.colour_grid, cfg.colour_divide_factor, dtype)
     if not grid_grad:                     # color_stage == "base": the colour grid feature is detached (base_networks.py:337-339)
         gf = gf.detach()
     h = torch.cat([x, _pe(d, cfg.multires_view), n, f, gf], dim=-1)
     for l in range(cfg.colour_n_linear):
-        h = _lin(params, f"rendering_network.lin{l}", h, dtype)
+        h = _lin(params, f"rendering_network.lin{l}", h, dtype, quant, exact_rows=3 if l == cfg.colour_n_linear - 1 else 0)
         if l < cfg.colour_n_linear - 1:
+            if quant is not None:         # the ReLU kinks of THIS graph (its pre-activations differ from the unrounded ones by a bf16 effect)
+                quant.relu_margin = torch.minimum(quant.relu_margin, h.detach().abs().amin(1).double())
             h = torch.relu(h)
     return (x, n, d, f), torch.sigmoid(h)
 
 
-def colour_forward(params, cfg, x0, normals, dirs, feats, dtype=F64):
+def colour_forward(params, cfg, x0, normals, dirs, feats, dtype=F64, quant=None):
     """-> rgb [P,3]."""
     with torch.no_grad():
-        return _colour_graph(params, cfg, x0, normals, dirs, feats, False, dtype)[1]
+        return _colour_graph(params, cfg, x0, normals, dirs, feats, False, dtype, quant=quant)[1]
 
 
-def colour_backward(params, cfg, x0, normals, dirs, feats, g_rgb, grid_grad=1, dtype=F64):
+def colour_backward(params, cfg, x0, normals, dirs, feats, g_rgb, grid_grad=1, dtype=F64, quant=None):
     """-> dict(x, normals, dirs, feat) of d(g_rgb . rgb); grid_grad = 0 is color_stage "base"."""
-    ins, rgb = _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype)
+    ins, rgb = _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, quant=quant)
     gs = torch.autograd.grad((g_rgb.to(dtype) * rgb).sum(), ins)
     return dict(zip(("x", "normals", "dirs", "feat"), gs))
 

@@ -38,24 +38,45 @@ def _ptr(t):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the network
+def perturbed(name="full_vis_eval", edit=None, seed=0):
+    """-> (fixture, oracle config, parameters) of a golden model with every weight_v perturbed, optionally edited (CPU only)"""
+    fx = dict(load(name))
+    g = torch.Generator().manual_seed(seed)
+    for k in sorted(fx):
+        if k.startswith("param_") and k.endswith("weight_v"):
+            v = torch.from_numpy(np.array(fx[k]))
+            fx[k] = (v + 0.05 * torch.randn(v.shape, generator=g)).numpy()
+    if edit:
+        edit(fx, g)
+    return fx, oracle_config(fx), params_of(fx)
+
+
+def _fn(net, name):
+    """the entry point ``name`` for ``net``: the public one, or (Net(precision="bf16")) its bf16-operand twin, called directly"""
+    from nicer_slam_amd._native import lib
+    base = getattr(lib, name)
+    if not net.suffix:
+        return base
+    twin = getattr(lib, name + net.suffix)
+    twin.restype, twin.argtypes = base.restype, base.argtypes
+    return twin
+
+
 class Net:
     """A golden model's parameters with every weight_v perturbed (so that all input columns matter), optionally edited, on the CPU
     (references) and the GPU (kernels)."""
 
-    def __init__(self, name="full_vis_eval", edit=None, seed=0):
+    def __init__(self, name="full_vis_eval", edit=None, seed=0, precision="fp32"):
         from test_model_cpu import build_model
-        fx = dict(load(name))
-        g = torch.Generator().manual_seed(seed)
-        for k in sorted(fx):
-            if k.startswith("param_") and k.endswith("weight_v"):
-                v = torch.from_numpy(np.array(fx[k]))
-                fx[k] = (v + 0.05 * torch.randn(v.shape, generator=g)).numpy()
-        if edit:
-            edit(fx, g)
-        self.fx, self.cfg, self.params = fx, oracle_config(fx), params_of(fx)
+        fx, self.cfg, self.params = perturbed(name, edit, seed)
+        self.fx = fx
         self.model = build_model(fx).cuda().eval()
         for p in self.model.parameters():
             p.requires_grad_(False)
+        # "bf16": the grid descriptors say precision 1 and every k_* helper below calls the nsa_*_bf16 entry point itself
+        assert precision in ("fp32", "bf16"), precision
+        self.model.mlp_precision = precision
+        self.suffix = "_bf16" if precision == "bf16" else ""
 
     def sdf(self, which, tile):
         from nicer_slam_amd.fused import sampler as fs
@@ -66,7 +87,7 @@ class Net:
     def colour(self):
         from nicer_slam_amd.fused import render as fr, sampler as fs
         m = self.model
-        gd, keep = fs.grid_desc(m.rendering_network.encoding, m.rendering_network.divide_factor, 2, 0)
+        gd, keep = fs.grid_desc(m.rendering_network.encoding, m.rendering_network.divide_factor, 2, fs.precision_of(m, "colour"))
         return gd, keep, fr.packed_colour(m)
 
 
@@ -105,7 +126,7 @@ def k_sdf_forward(net, which, tile, x, accumulate=0, init=None):
     grad = torch.zeros(P, 3, device="cuda") if init is None else init[1].cuda().clone()
     feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda") if init is None else _to_hl(init[2])
     pts = _explicit(xd)
-    check(lib.nsa_sdfnet_forward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), accumulate, sdf.data_ptr(), grad.data_ptr(),
+    check(_fn(net, "nsa_sdfnet_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), accumulate, sdf.data_ptr(), grad.data_ptr(),
                                  feat.data_ptr(), _st()))
     torch.cuda.synchronize()
     return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
@@ -123,7 +144,7 @@ def k_sdf_pair(net, x):
     sdf, grad = torch.full((P,), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
     feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda")
     pts = _explicit(xd)
-    check(lib.nsa_sdfnet_forward_pair(ctypes.byref(pts), ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
+    check(_fn(net, "nsa_sdfnet_forward_pair")(ctypes.byref(pts), ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
                                       sdf.data_ptr(), grad.data_ptr(), feat.data_ptr(), _st()))
     torch.cuda.synchronize()
     return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
@@ -141,14 +162,14 @@ def k_sdf_backward(net, which, tile, x, g_sdf=None, g_feat=None, g_grad=None, ac
     g_x = torch.zeros(P, 3, device="cuda") if init is None else init.cuda().clone()
     pts = _explicit(xd)
     if not params:
-        check(lib.nsa_sdfnet_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
+        check(_fn(net, "nsa_sdfnet_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
                                       g_x.data_ptr(), _st()))
         torch.cuda.synchronize()
         return dict(x=g_x.cpu())
-    rows = lib.nsa_sdfnet_emit_rows_tile(gd.n_hidden, tile)
+    rows = _fn(net, "nsa_sdfnet_emit_rows_tile")(gd.n_hidden, tile)
     assert rows > 0
     emit = torch.full((rows, mapping.emit_ld(P)), float("nan"), device="cuda")
-    check(lib.nsa_sdfnet_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
+    check(_fn(net, "nsa_sdfnet_backward_params")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
                                          g_x.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
     torch.cuda.synchronize()
     return dict(x=g_x.cpu()), emit
@@ -164,7 +185,7 @@ def k_colour_forward(net, x, d, normals, feat):
     grad, fh = normals.cuda().contiguous(), _to_hl(feat)
     rgb = torch.full((P, 3), float("nan"), device="cuda")
     save = torch.zeros(fr.save_size(P), device="cuda")
-    check(lib.nsa_colour_forward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), rgb.data_ptr(),
+    check(_fn(net, "nsa_colour_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), rgb.data_ptr(),
                                  save.data_ptr(), _st()))
     torch.cuda.synchronize()
     return rgb.cpu(), (o, dd, _z, grad, fh, save)
@@ -185,18 +206,18 @@ def k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="plain", 
     g_x, g_dir = torch.full((P, 3), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
     emit = None
     if kind == "plain":
-        check(lib.nsa_colour_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), save.data_ptr(),
+        check(_fn(net, "nsa_colour_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), save.data_ptr(),
                                       gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(), g_x.data_ptr(), g_dir.data_ptr(),
                                       _st()))
     elif kind == "params":
-        emit = torch.full((lib.nsa_colour_emit_rows(), mapping.emit_ld(P)), float("nan"), device="cuda")
-        check(lib.nsa_colour_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
+        emit = torch.full((_fn(net, "nsa_colour_emit_rows")(), mapping.emit_ld(P)), float("nan"), device="cuda")
+        check(_fn(net, "nsa_colour_backward_params")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
                                              save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
                                              g_x.data_ptr(), g_dir.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
     else:
         gc, _kc, pc = net.sdf("coarse", coarse_tile)
         gs = g_sdf.cuda().contiguous()
-        check(lib.nsa_colour_coarse_backward(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
+        check(_fn(net, "nsa_colour_coarse_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
                                              save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
                                              g_x.data_ptr(), g_dir.data_ptr(), ctypes.byref(gc), pc.data_ptr(), gs.data_ptr(), _st()))
     torch.cuda.synchronize()
