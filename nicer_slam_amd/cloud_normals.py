@@ -21,15 +21,18 @@ import numpy as np
 import torch
 
 from ._native import check, lib
-from .mesh_eval import NNIndex, _points
+from .mesh_args import checked_points, need_gpu, ptr, stream
+from .mesh_eval import NNIndex
+from .ply import read_ply, write_mesh_ply
 
 
 def _cloud(x, name, device=None):
+    """``checked_points`` for a cloud that may be an array or live on the host: moved to ``device`` first"""
     if not torch.is_tensor(x):
         x = torch.as_tensor(np.asarray(x, np.float32)).reshape(-1, 3)
     if not x.is_cuda:
         x = x.to(device if device is not None else "cuda")
-    return _points(x, name)
+    return checked_points(x, name)
 
 
 @torch.no_grad()
@@ -55,8 +58,8 @@ def normals_from_neighbours(points, idx, count, origin, viewpoint=None, eigenval
     valid = torch.empty(m, dtype=torch.uint8, device=dev)
     if m:
         check(lib.nsa_cloud_normals(points.data_ptr(), points.shape[0], idx.data_ptr(), count.data_ptr(), m, k, origin.data_ptr(),
-                                    viewpoint.data_ptr() if rows else None, rows, normals.data_ptr(),
-                                    eig.data_ptr() if eigenvalues else None, valid.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                                    viewpoint.data_ptr() if rows else None, rows, normals.data_ptr(), ptr(eig), valid.data_ptr(),
+                                    stream(dev)))
     return normals, eig, valid.bool()
 
 
@@ -72,8 +75,7 @@ def estimate_normals(points, k=30, max_dist=math.inf, viewpoint=None, queries=No
     one line); a row that is not gets the normal (0, 0, 0), which ``icp_point_to_plane`` leaves out.
     ``info=True`` returns (normals, dict(valid [m] bool, eigenvalues [m, 3] float64 ascending, variation [m] = w0 / ((w0 + w1) + w2) -- the
     surface variation, 0 on a plane and 1/3 on an isotropic blob --, count [m] int64, idx [m, k] int64))."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("estimate_normals: needs a GPU")
+    need_gpu("estimate_normals")
     dev = index.device if index is not None else None
     pts = _cloud(points, "estimate_normals", dev)
     if pts.shape[0] == 0:
@@ -92,7 +94,6 @@ def estimate_normals(points, k=30, max_dist=math.inf, viewpoint=None, queries=No
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.cloud_normals", description=__doc__.splitlines()[0])
     ap.add_argument("input", metavar="IN.ply", help="a cloud (no face element) or a mesh, whose faces are kept")
     ap.add_argument("--out", metavar="OUT.ply", required=True, help="the vertices with nx ny nz and the faces read")
@@ -107,9 +108,7 @@ def main(argv=None):
     try:
         ply = read_ply(a.input)
         normals, extra = estimate_normals(ply["verts"], a.k, a.radius, a.viewpoint, info=True)
-        out = {key: torch.as_tensor(np.ascontiguousarray(ply[key])) for key in ("verts", "faces", "colors") if key in ply}
-        out["normals"] = normals.cpu()
-        write_ply(a.out, out)
+        write_mesh_ply(a.out, dict(ply, normals=normals))
     except (ValueError, OSError) as e:
         print(f"cloud_normals: {e}", file=sys.stderr)
         raise SystemExit(2)

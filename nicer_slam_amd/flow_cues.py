@@ -18,18 +18,11 @@ import numpy as np
 import torch
 
 from ._native import check, lib
+from .mesh_args import ptr, stream
 from .tsdf import _as_numpy, _intrinsics4
 
 DEFAULT_NEAR = 1e-3
 DEFAULT_ALPHA, DEFAULT_BETA = 0.01, 0.5              # GMFlow's forward_backward_consistency_check
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
 
 
 def _on_device(name, *tensors):
@@ -99,7 +92,7 @@ def induced_flow(depth, c2w, intrinsics, src, dst, near=DEFAULT_NEAR, device="cu
     src_d = torch.from_numpy(src.astype(np.int32)).to(dev)
     dst_d = torch.from_numpy(dst.astype(np.int32)).to(dev)
     check(lib.nsa_flowcue_induced(d.data_ptr(), n, H, W, K_d.data_ptr(), int(K.shape[0] > 1), rel_d.data_ptr(), src_d.data_ptr(),
-                                  dst_d.data_ptr(), E, float(near), flow.data_ptr(), valid.data_ptr(), _stream(dev)))
+                                  dst_d.data_ptr(), E, float(near), flow.data_ptr(), valid.data_ptr(), stream(dev)))
     return flow, valid
 
 
@@ -131,8 +124,8 @@ def consistency(fwd, bwd, fwd_valid=None, bwd_valid=None, alpha=DEFAULT_ALPHA, b
     bv = None if bwd_valid is None else bwd_valid.to(dev).ne(0).to(torch.uint8).contiguous()
     fo = torch.empty(P, H, W, dtype=torch.uint8, device=dev)
     bo = torch.empty(P, H, W, dtype=torch.uint8, device=dev)
-    check(lib.nsa_flowcue_consistency(_ptr(f), _ptr(b), _ptr(fv), _ptr(bv), P, H, W, float(alpha), float(beta), _ptr(fo), _ptr(bo),
-                                      _stream(dev)))
+    check(lib.nsa_flowcue_consistency(ptr(f), ptr(b), ptr(fv), ptr(bv), P, H, W, float(alpha), float(beta), ptr(fo), ptr(bo),
+                                      stream(dev)))
     return fo, bo
 
 
@@ -186,7 +179,7 @@ def pair_cues(depth, c2w, intrinsics, pairs, near=DEFAULT_NEAR, alpha=DEFAULT_AL
     occ = torch.empty_like(valid)
     if U:
         check(lib.nsa_flowcue_consistency(flow[:U].data_ptr(), flow[U:].data_ptr(), valid[:U].data_ptr(), valid[U:].data_ptr(), U, H, W,
-                                          float(alpha), float(beta), occ[:U].data_ptr(), occ[U:].data_ptr(), _stream(flow.device)))
+                                          float(alpha), float(beta), occ[:U].data_ptr(), occ[U:].data_ptr(), stream(flow.device)))
     order = [slot[(min(i, j), max(i, j))] + (0 if i < j else U) for i, j in pairs]
     if order == list(range(len(order))) and len(order) == 2 * U:
         return flow, occ
@@ -302,8 +295,8 @@ class FlowStore:
         b, n = s.shape
         out = torch.empty(E, n, 2, dtype=torch.float32, device=dev)
         mask = torch.empty(E, n, dtype=torch.bool, device=dev)
-        check(lib.nsa_flowcue_select(_ptr(self.flows), _ptr(self.masks), E, self.H * self.W, _ptr(s), b, n, _ptr(r), _ptr(out),
-                                     _ptr(mask), _stream(dev)))
+        check(lib.nsa_flowcue_select(ptr(self.flows), ptr(self.masks), E, self.H * self.W, ptr(s), b, n, ptr(r), ptr(out),
+                                     ptr(mask), stream(dev)))
         return out, mask
 
 
@@ -342,7 +335,7 @@ def main(argv=None):
     ap.add_argument("--rad", type=int, default=2)
     ap.add_argument("--near", type=float, default=DEFAULT_NEAR)
     args = ap.parse_args(argv)
-    from .mesh_render import read_depth_dir, read_poses
+    from .mesh_render import read_depth_dir, read_poses    # (no cycle: only the command line needs the mesh tools)
     c2w = read_poses(args.poses)
     depth = read_depth_dir(args.depth, len(c2w))
     n = write_sequence(depth, c2w, args.intrinsics, args.out, args.interval, args.rad, args.near)

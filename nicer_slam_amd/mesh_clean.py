@@ -20,53 +20,14 @@ import sys
 import numpy as np
 import torch
 
+from . import mesh_topology
 from ._native import lib, check
+from .mesh_args import PER_VERTEX, checked_faces, mesh_dict_tensors, need_gpu, ptr, restore_dict, stream, workspace
+from .mesh_eval import _transform
+from .ply import read_ply, write_mesh_ply
 
 KEEP_MODES = ("largest", "touching", "not_touching")
 CONNECTIVITY = ("vertex", "edge")
-_PER_VERTEX = ("verts", "normals", "colors")
-
-
-def _mesh_tensors(mesh, device=None):
-    """(dict of torch tensors [, moved to ``device``], was_numpy, original device)"""
-    if "verts" not in mesh or "faces" not in mesh:
-        raise ValueError("mesh: needs 'verts' and 'faces'")
-    was_numpy = not torch.is_tensor(mesh["verts"])
-    out = {}
-    for k, x in mesh.items():
-        if k in _PER_VERTEX or k == "faces":
-            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-            out[k] = t.to(device) if device is not None else t
-        else:
-            out[k] = x
-    orig = None if was_numpy else mesh["verts"].device
-    V = out["verts"].shape[0]
-    if out["verts"].dim() != 2 or out["verts"].shape[1] != 3 or out["faces"].dim() != 2 or out["faces"].shape[1] != 3:
-        raise ValueError("mesh: verts must be [V, 3] and faces [F, 3]")
-    for k in _PER_VERTEX:
-        if k in out and out[k].shape[0] != V:
-            raise ValueError(f"mesh: '{k}' has {out[k].shape[0]} rows for {V} vertices")
-    return out, was_numpy, orig
-
-
-def _restore(mesh, was_numpy, device):
-    out = {}
-    for k, x in mesh.items():
-        if torch.is_tensor(x):
-            out[k] = x.cpu().numpy() if was_numpy else x.to(device)
-        else:
-            out[k] = x
-    return out
-
-
-def _faces_i32(faces, name):
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3):
-        raise ValueError(f"{name}: faces must be a CUDA tensor [F, 3]")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: faces must be int32 or int64")
-    if faces.dtype == torch.int64 and faces.numel() and (int(faces.min()) < -2 ** 31 or int(faces.max()) >= 2 ** 31):
-        raise ValueError(f"{name}: face index outside int32")
-    return faces.to(torch.int32).contiguous()
 
 
 @torch.no_grad()
@@ -75,19 +36,15 @@ def components(faces, n_verts):
     int64) over ``n_verts`` vertices.  Faces that share a vertex index are connected; the label of a component is its smallest
     vertex index; a vertex no valid face uses and a face with an index outside [0, n_verts) get -1.  Reads the three totals
     back once (a synchronisation)."""
-    f = _faces_i32(faces, "components")
-    V, F = int(n_verts), f.shape[0]
-    if V < 0 or V >= 1 << 31 or F >= 1 << 31:
-        raise ValueError("components: count out of range")
-    dev = f.device
+    f = checked_faces(faces, "components", require_cuda=True, n_verts=n_verts).to(torch.int32).contiguous()
+    V, F, dev = int(n_verts), f.shape[0], f.device
     vl = torch.empty(V, dtype=torch.int32, device=dev)
     fl = torch.empty(F, dtype=torch.int32, device=dev)
     if V == 0 and F == 0:
         return vl, fl, 0, 0
-    ws = torch.empty(max(1, lib.nsa_mesh_components_workspace(V)), dtype=torch.uint8, device=dev)
+    ws = workspace(max(1, lib.nsa_mesh_components_workspace(V)), dev)
     totals = torch.empty(3, dtype=torch.int64, device=dev)
-    check(lib.nsa_mesh_components(f.data_ptr() if F else None, F, V, ws.data_ptr(), vl.data_ptr() if V else None,
-                                  fl.data_ptr() if F else None, totals.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    check(lib.nsa_mesh_components(ptr(f), F, V, ws.data_ptr(), ptr(vl), ptr(fl), totals.data_ptr(), stream(dev)))
     C, R, status = (int(x) for x in totals.cpu())
     if status != 0:
         raise RuntimeError(f"components: the labelling kernel left its loop on a step cap (status {status}); this is a bug")
@@ -102,7 +59,7 @@ def component_stats(verts, faces):
     if not (torch.is_tensor(verts) and verts.is_cuda and verts.dim() == 2 and verts.shape[1] == 3):
         raise ValueError("component_stats: verts must be a CUDA tensor [V, 3]")
     v = verts.detach().float().contiguous()
-    f = _faces_i32(faces, "component_stats")
+    f = checked_faces(faces, "component_stats", require_cuda=True).to(torch.int32).contiguous()
     V, F, dev = v.shape[0], f.shape[0], v.device
     if f.device != dev:
         raise ValueError("component_stats: verts and faces on different devices")
@@ -114,12 +71,10 @@ def component_stats(verts, faces):
                face_comp=torch.full((F,), -1, dtype=torch.int32, device=dev), n_components=C)
     if V == 0:
         return out
-    ws = torch.empty(max(1, lib.nsa_mesh_component_stats_workspace(V, F, C)), dtype=torch.uint8, device=dev)
-    p = lambda t: t.data_ptr() if t.numel() else None
-    check(lib.nsa_mesh_component_stats(v.data_ptr(), V, p(f), F, vl.data_ptr(), p(fl), C, ws.data_ptr(), p(out["label"]),
-                                       p(out["n_faces"]), p(out["n_verts"]), p(out["area"]), p(out["lo"]), p(out["hi"]),
-                                       out["vertex_comp"].data_ptr(), p(out["face_comp"]),
-                                       torch.cuda.current_stream(dev).cuda_stream))
+    ws = workspace(max(1, lib.nsa_mesh_component_stats_workspace(V, F, C)), dev)
+    check(lib.nsa_mesh_component_stats(v.data_ptr(), V, ptr(f), F, vl.data_ptr(), ptr(fl), C, ws.data_ptr(), ptr(out["label"]),
+                                       ptr(out["n_faces"]), ptr(out["n_verts"]), ptr(out["area"]), ptr(out["lo"]), ptr(out["hi"]),
+                                       out["vertex_comp"].data_ptr(), ptr(out["face_comp"]), stream(dev)))
     return out
 
 
@@ -128,7 +83,7 @@ def select_faces(mesh, face_mask):
     """The mesh of the faces where ``face_mask`` [F] is set: the kept faces in their original order, the vertices some kept
     face uses in their original order, faces re-indexed, every per-vertex entry (``verts``, ``normals``, ``colors``) carried.
     numpy in, numpy out; torch in, torch out on the same device."""
-    m, was_numpy, dev = _mesh_tensors(mesh)
+    m, was_numpy, dev = mesh_dict_tensors(mesh)
     f = m["faces"]
     mask = torch.as_tensor(face_mask, device=f.device).bool().reshape(-1)
     V = m["verts"].shape[0]
@@ -142,10 +97,10 @@ def select_faces(mesh, face_mask):
     remap = torch.cumsum(used.long(), 0) - 1
     out = dict(m)
     out["faces"] = remap[kept].to(f.dtype)
-    for k in _PER_VERTEX:
+    for k in PER_VERTEX:
         if k in m:
             out[k] = m[k][used]
-    return _restore(out, was_numpy, dev)
+    return restore_dict(out, was_numpy, dev)
 
 
 def _region(region):
@@ -178,15 +133,13 @@ def keep_components(mesh, keep="largest", region=None, device="cuda", connectivi
         raise ValueError(f"keep_components: connectivity must be one of {CONNECTIVITY}, got {connectivity!r}")
     if keep != "largest":
         lo, hi = _region(region)
-    if not torch.cuda.is_available():
-        raise RuntimeError("keep_components: needs a GPU")
-    m, was_numpy, orig = _mesh_tensors(mesh, device)
+    need_gpu("keep_components")
+    m, was_numpy, orig = mesh_dict_tensors(mesh, device)
     if m["verts"].shape[0] == 0 or m["faces"].shape[0] == 0:
         raise ValueError("keep_components: empty mesh")
     sv, sf = m["verts"], m["faces"]                            # the mesh the table is of
     if connectivity == "edge":
-        from . import mesh_topology
-        f32 = _faces_i32(sf, "keep_components")
+        f32 = checked_faces(sf, "keep_components", require_cuda=True).to(torch.int32).contiguous()
         label, _ = mesh_topology.face_components(f32, sv.shape[0])
         sf, origin = mesh_topology.split_faces(f32, label, sv.shape[0])
         sv = sv[origin]
@@ -215,7 +168,7 @@ def keep_components(mesh, keep="largest", region=None, device="cuda", connectivi
     st["kept"] = kept
     total = float(st["area"].sum())
     st["kept_area_fraction"] = float(st["area"][kept].sum()) / total if total > 0 else float("nan")
-    return _restore(out, was_numpy, orig), st
+    return restore_dict(out, was_numpy, orig), st
 
 
 def check_similarity(T, tol=1e-6):
@@ -240,9 +193,8 @@ def transform_mesh(mesh, T):
     """``mesh`` moved by the similarity ``T`` (4x4, T[:3, :3] = s R): vertices through mesh_eval._transform in float64, rounded
     once to fp32; normals multiplied by T[:3, :3] and normalised again (zero stays zero); everything else carried.  A ``T``
     whose linear part is not a positive multiple of a rotation within 1e-6 raises ValueError."""
-    from .mesh_eval import _transform
     _, T = check_similarity(T)
-    m, was_numpy, dev = _mesh_tensors(mesh)
+    m, was_numpy, dev = mesh_dict_tensors(mesh)
     out = dict(m)
     Tt = torch.from_numpy(T).to(m["verts"].device)
     out["verts"] = _transform(m["verts"].double(), Tt).float()
@@ -252,7 +204,7 @@ def transform_mesh(mesh, T):
         n = _transform(m["normals"].double(), Z)
         length = n.norm(dim=-1, keepdim=True)
         out["normals"] = torch.where(length > 0, n / length.clamp_min(1e-300), torch.zeros_like(n)).float()
-    return _restore(out, was_numpy, dev)
+    return restore_dict(out, was_numpy, dev)
 
 
 def format_table(stats):
@@ -291,7 +243,6 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     a = parse_args(argv)
     try:
         mesh = read_ply(a.mesh)
@@ -310,10 +261,7 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         print(f"mesh_clean: {e}", file=sys.stderr)
         raise SystemExit(2)
-    out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in mesh.items() if k in _PER_VERTEX or k == "faces"}
-    if "normals" not in out:                                   # write_ply's layout has them; a file without stays without direction
-        out["normals"] = torch.zeros_like(out["verts"])
-    write_ply(a.out, out)
+    write_mesh_ply(a.out, mesh)
     return mesh
 
 

@@ -18,24 +18,18 @@ import json
 import math
 import sys
 
-import numpy as np
 import torch
 
 from . import _native
 from ._native import lib, check
-from .mesh_simplify import _checked
+from .mesh_args import MAX_FACES_RINGS, checked_mesh, need_gpu, ptr, stream, workspace
 from .mesh_smooth import WEIGHTING, _vertex_normals
-from .mesh_topology import _need_gpu
+from .ply import read_ply, write_mesh_ply
 
 BOUNDARY = {"quadric": _native.DECIMATE_BOUNDARY_QUADRIC, "fixed": _native.DECIMATE_BOUNDARY_FIXED}
 NORMALS = ("angle", "area", None)
 TOTALS = ("rounds", "collapses", "n_candidates", "rej_lock", "rej_error", "rej_link", "rej_fold", "n_selected", "n_faces", "n_verts",
           "status")
-_MAX_FACES = (2 ** 31 - 1) // 6
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 class _Tables:
@@ -50,11 +44,11 @@ class _Tables:
         self.edge_start, self.edge_halfedges, self.face_edges = i32(H + 1), i32(H), i32(F, 3)
         self.totals = torch.empty(8, dtype=torch.int64, device=dev)
         self.ring_start, self.ring, self.ring_edge = i32(V + 1), i32(6 * F), i32(6 * F)
-        self.ws_edges = torch.empty(lib.nsa_mesh_edges_workspace(V, F), dtype=torch.uint8, device=dev)
-        self.ws_ring = torch.empty(lib.nsa_mesh_ring_workspace(V, F), dtype=torch.uint8, device=dev)
+        self.ws_edges = workspace(lib.nsa_mesh_edges_workspace(V, F), dev)
+        self.ws_ring = workspace(lib.nsa_mesh_ring_workspace(V, F), dev)
 
     def build(self, faces):
-        s = _stream(self.dev)
+        s = stream(self.dev)
         check(lib.nsa_mesh_edges(faces.data_ptr(), self.F, self.V, None, self.ws_edges.data_ptr(), self.edges.data_ptr(),
                                  self.edge_count.data_ptr(), self.edge_forward.data_ptr(), self.edge_start.data_ptr(),
                                  self.edge_halfedges.data_ptr(), self.face_edges.data_ptr(), self.totals.data_ptr(), s))
@@ -73,12 +67,11 @@ def _decimate(v, f, colors, fixed, target_faces, max_error, boundary, boundary_w
         return v.clone(), None if colors is None else colors.clone(), fw, torch.arange(V, dtype=torch.int32, device=dev), \
             torch.zeros(0, 4, dtype=torch.int64, device=dev), dict(rounds=0, collapses=0, **last, status=0)
     tb = _Tables(V, F, dev)
-    state = torch.empty(lib.nsa_mesh_decimate_state_bytes(V), dtype=torch.uint8, device=dev)
-    ws = torch.empty(lib.nsa_mesh_decimate_workspace(V, F), dtype=torch.uint8, device=dev)
+    state = workspace(lib.nsa_mesh_decimate_state_bytes(V), dev)
+    ws = workspace(lib.nsa_mesh_decimate_workspace(V, F), dev)
     log = torch.zeros(V, 4, dtype=torch.int64, device=dev)
     totals = torch.zeros(14, dtype=torch.int64, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()
-    s = _stream(dev)
+    s = stream(dev)
     tb.build(fw)
     check(lib.nsa_mesh_decimate_init(v.data_ptr(), ptr(colors), V, fw.data_ptr(), F, tb.edge_count.data_ptr(), tb.edge_start.data_ptr(),
                                      tb.edge_halfedges.data_ptr(), tb.ring_start.data_ptr(), tb.ring.data_ptr(), tb.ring_edge.data_ptr(),
@@ -177,16 +170,16 @@ def decimate(mesh, target_faces=None, max_error=None, boundary="quadric", bounda
     ``n_faces``, ``n_verts``, ``status``.  Out of scope: collapsing onto a locked vertex, attribute-aware and memoryless quadrics,
     repairing non-manifold input, merging the two sides of a sheet.  Reads fourteen words back per round (a synchronisation)."""
     _checked_args(target_faces, max_error, boundary, boundary_weight, min_cos, eps, max_rounds, normals)
-    if not isinstance(mesh, dict) or "verts" not in mesh or "faces" not in mesh:
+    if not isinstance(mesh, dict) or "verts" not in mesh:
         raise ValueError("decimate: mesh needs 'verts' and 'faces'")
     mask = None
     if fixed is not None:
         mask = torch.as_tensor(fixed).reshape(-1)
         if mask.shape[0] != mesh["verts"].shape[0]:
             raise ValueError(f"decimate: fixed mask of {mask.shape[0]} for {mesh['verts'].shape[0]} vertices")
-    if len(getattr(mesh["faces"], "shape", ())) == 2 and mesh["faces"].shape[0] > _MAX_FACES:
-        raise ValueError("decimate: count out of range (6 * n_faces < 2^31)")
-    v, f, (colors,), restore = _checked(mesh["verts"], mesh["faces"], "decimate", (("colors", mesh.get("colors")),))
+    v, f, _, _, extra, restore = checked_mesh(mesh, "decimate", float_verts=True, attributes=("colors",), float_attributes=True,
+                                              max_faces=MAX_FACES_RINGS)
+    colors = extra.get("colors")
     if mask is not None:
         mask = (mask.to(v.device) != 0).to(torch.uint8).contiguous()
     out, out_c, fw, vmap, log, totals = _decimate(v, f, colors, mask, None if target_faces is None else int(target_faces), max_error,
@@ -206,7 +199,6 @@ def decimate(mesh, target_faces=None, max_error=None, boundary="quadric", bounda
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_decimate", description=__doc__.splitlines()[0])
     ap.add_argument("mesh", metavar="IN.ply")
     ap.add_argument("--out", required=True, metavar="OUT.ply")
@@ -219,14 +211,11 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.faces is None and a.max_error is None:
         ap.error("give --faces, --max-error or both")
-    _need_gpu("mesh_decimate")
+    need_gpu("mesh_decimate")
     try:
         r = decimate(read_ply(a.mesh), target_faces=a.faces, max_error=a.max_error, boundary=a.boundary, min_cos=a.min_cos,
                      normals=None if a.normals == "none" else a.normals, return_map=True)
-        ply = {k: torch.from_numpy(np.ascontiguousarray(r[k])) for k in ("verts", "faces", "normals", "colors") if k in r}
-        if "normals" not in ply:                          # (write_ply stores normals; a file without them gets zeros)
-            ply["normals"] = torch.zeros_like(ply["verts"])
-        write_ply(a.out, ply)
+        write_mesh_ply(a.out, r)
     except (ValueError, OSError) as e:
         print(f"mesh_decimate: {e}", file=sys.stderr)
         raise SystemExit(2)

@@ -31,19 +31,11 @@ import numpy as np
 import torch
 
 from ._native import KNN_MAX_K, RAY_ANY_HIT, RAY_BRUTE, RAY_CULL_BACK, RAY_CULL_FRONT, check, lib
+from .mesh_args import MAX_FACES, checked_faces, checked_points, cuda_verts_faces, max_d2 as _max_d2, need_gpu, stream, workspace
+from .ply import read_ply
 
 F_THRESHOLDS = (0.010, 0.015, 0.020)       # np.linspace(1/1000, 1, 1000)[[9, 14, 19]] of eval_pointcloud
 COMPLETION_RATIO_THRESHOLD = 0.05          # completion_ratio's dist_th (eval_rec.py:168)
-
-
-def _points(x, name):
-    if not (torch.is_tensor(x) and x.is_cuda):
-        raise ValueError(f"{name}: needs a CUDA tensor [n, 3]")
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"{name}: needs shape [n, 3], got {tuple(x.shape)}")
-    if x.shape[0] >= 1 << 31:
-        raise ValueError(f"{name}: more than 2^31 - 1 points")
-    return x.detach().float().contiguous()
 
 
 class NNIndex:
@@ -52,20 +44,20 @@ class NNIndex:
 
     @torch.no_grad()
     def __init__(self, targets):
-        t = _points(targets, "NNIndex")
+        t = checked_points(targets, "NNIndex")
         self.n = t.shape[0]
         if self.n == 0:
             raise ValueError("NNIndex: no targets")
         self.device = t.device
-        self.buf = torch.empty(lib.nsa_nn_workspace(self.n), dtype=torch.uint8, device=t.device)
-        check(lib.nsa_nn_build(t.data_ptr(), self.n, self.buf.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream))
+        self.buf = workspace(lib.nsa_nn_workspace(self.n), t.device)
+        check(lib.nsa_nn_build(t.data_ptr(), self.n, self.buf.data_ptr(), stream(t.device)))
 
     @torch.no_grad()
     def query(self, queries, max_dist=math.inf):
         """(dist [m] fp32, idx [m] int64): the nearest target of each query, ties to the lowest index.  With a finite
         ``max_dist`` only targets with d2 < fp32(max_dist^2) count (open3d's hybrid search); none gives (+inf, -1).
         A non-finite query gives (NaN, -1)."""
-        q = _points(queries, "NNIndex.query")
+        q = checked_points(queries, "NNIndex.query")
         if q.device != self.device:
             raise ValueError("NNIndex.query: queries on another device than the index")
         if not max_dist > 0:
@@ -75,7 +67,7 @@ class NNIndex:
         dist = torch.empty(m, dtype=torch.float32, device=q.device)
         if m:
             check(lib.nsa_nn_query(self.buf.data_ptr(), self.n, q.data_ptr(), m, float(max_dist), idx.data_ptr(), dist.data_ptr(),
-                                   torch.cuda.current_stream(q.device).cuda_stream))
+                                   stream(q.device)))
         return dist, idx.long()
 
     @torch.no_grad()
@@ -93,7 +85,7 @@ class NNIndex:
         count = torch.empty(m, dtype=torch.int32, device=q.device)
         if m:
             check(lib.nsa_nn_query_k(self.buf.data_ptr(), self.n, q.data_ptr(), m, k, float(max_dist), idx.data_ptr(), dist.data_ptr(),
-                                     count.data_ptr(), torch.cuda.current_stream(q.device).cuda_stream))
+                                     count.data_ptr(), stream(q.device)))
         return dist, idx, count
 
     def knn(self, queries, k, max_dist=math.inf):
@@ -101,7 +93,7 @@ class NNIndex:
         order (d2, target index), in that order (C ABI Section 28): exact ties go to the lower index, at the k-th place too.  With a
         finite ``max_dist`` only targets with d2 < fp32(max_dist^2) count.  ``count`` is the number found; the slots behind it hold
         (+inf, -1).  A non-finite query gives count 0 and (NaN, -1).  ``knn(q, 1)`` is ``query(q)`` with a column axis."""
-        dist, idx, count = self._knn(_points(queries, "NNIndex.knn"), k, max_dist)
+        dist, idx, count = self._knn(checked_points(queries, "NNIndex.knn"), k, max_dist)
         return dist, idx.long(), count.long()
 
     def grid(self):
@@ -133,7 +125,7 @@ def sample_surface(verts, faces, n, seed=0):
     """(points [n, 3] fp32, face_idx [n] int64): ``n`` area-weighted samples of the triangle mesh, from Philox4x32-10 with
     key = seed and counter = sample index (trimesh.sample.sample_surface, restated in include/nicer_slam_amd.h Section 8).
     Raises ValueError for a mesh without faces or with zero (or non-finite) total area."""
-    v = _points(verts, "sample_surface")
+    v = checked_points(verts, "sample_surface")
     if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3):
         raise ValueError("sample_surface: faces must be a CUDA tensor [F, 3]")
     f = faces.to(torch.int32).contiguous()
@@ -144,37 +136,17 @@ def sample_surface(verts, faces, n, seed=0):
         raise ValueError("sample_surface: count out of range")
     if int(f.min()) < 0 or int(f.max()) >= V:
         raise ValueError("sample_surface: face index out of range")
-    ws = torch.empty(lib.nsa_surface_sample_workspace(F), dtype=torch.uint8, device=v.device)
+    ws = workspace(lib.nsa_surface_sample_workspace(F), v.device)
     pts = torch.empty(n, 3, device=v.device)
     fidx = torch.empty(n, dtype=torch.int32, device=v.device)
     total = torch.empty(1, dtype=torch.float64, device=v.device)
     check(lib.nsa_surface_sample(v.data_ptr(), V, f.data_ptr(), F, n, int(seed) & (2 ** 64 - 1), ws.data_ptr(),
                                  pts.data_ptr() if n else None, fidx.data_ptr() if n else None, total.data_ptr(),
-                                 torch.cuda.current_stream(v.device).cuda_stream))
+                                 stream(v.device)))
     a = float(total)
     if not (a > 0 and math.isfinite(a)):
         raise ValueError(f"sample_surface: total area {a} (zero-area or non-finite mesh)")
     return pts, fidx.long()
-
-
-def _faces(faces, name):
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dim() == 2 and faces.shape[1] == 3):
-        raise ValueError(f"{name}: faces must be a CUDA tensor [F, 3]")
-    if faces.shape[0] >= 1 << 31:
-        raise ValueError(f"{name}: more than 2^31 - 1 faces")
-    if faces.dtype != torch.int32 and faces.numel() and (int(faces.min()) < -(1 << 31) or int(faces.max()) >= 1 << 31):
-        raise ValueError(f"{name}: face index outside int32")
-    return faces.to(torch.int32).contiguous()
-
-
-def _max_d2(max_dist, name):
-    """the float64 bound of header Section 15 for ``max_dist`` (None: +inf)"""
-    if max_dist is None:
-        return math.inf
-    d = float(max_dist)
-    if not d >= 0:
-        raise ValueError(f"{name}: max_dist must be >= 0 or None, got {max_dist!r}")
-    return d * d
 
 
 def welded_faces(verts, faces):
@@ -198,8 +170,8 @@ class TriIndex:
 
     @torch.no_grad()
     def __init__(self, verts, faces):
-        v = _points(verts, "TriIndex")
-        f = _faces(faces, "TriIndex")
+        v = checked_points(verts, "TriIndex")
+        f = checked_faces(faces, "TriIndex", max_faces=MAX_FACES, dtypes=None, require_cuda=True).to(torch.int32).contiguous()
         if v.device != f.device:
             raise ValueError("TriIndex: verts and faces on different devices")
         if v.shape[0] == 0 or f.shape[0] == 0:
@@ -208,10 +180,10 @@ class TriIndex:
         self.faces = f.clone() if f.data_ptr() == faces.data_ptr() else f
         self.V, self.F = v.shape[0], f.shape[0]
         self.device = v.device
-        self.buf = torch.empty(lib.nsa_tri_workspace(self.F), dtype=torch.uint8, device=v.device)
+        self.buf = workspace(lib.nsa_tri_workspace(self.F), v.device)
         self._totals = torch.zeros(3, dtype=torch.int32, device=v.device)
         check(lib.nsa_tri_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, self.buf.data_ptr(),
-                                self._totals.data_ptr(), torch.cuda.current_stream(v.device).cuda_stream))
+                                self._totals.data_ptr(), stream(v.device)))
         self._adjacency = {}                       # weld setting -> (adjacency faces, adjacency buffer), built on first use
         self._winding = None                       # (tree buffer, info) of Section 16, built on first use
         self._ray = None                           # (tree buffer, info) of Section 17, built on first use
@@ -232,7 +204,7 @@ class TriIndex:
         measurement of the index).  ``max_dist`` (None: unbounded, the path of every call without it): only a closest point with
         d2 <= max_dist^2 counts, any other query gives (+inf, -1, NaN), and the walk stops once nothing within max_dist is left
         (header Section 15); ``counts=True`` then appends the cells visited per query as well."""
-        q = _points(points, "TriIndex.query")
+        q = checked_points(points, "TriIndex.query")
         if q.device != self.device:
             raise ValueError("TriIndex.query: points on another device than the index")
         m = q.shape[0]
@@ -247,7 +219,7 @@ class TriIndex:
                                                 q.data_ptr(), m, _max_d2(max_dist, "TriIndex.query"), face.data_ptr(), d2.data_ptr(),
                                                 closest.data_ptr(), n_eval.data_ptr() if counts else None,
                                                 n_cells.data_ptr() if counts else None,
-                                                torch.cuda.current_stream(q.device).cuda_stream))
+                                                stream(q.device)))
             else:
                 _max_d2(max_dist, "TriIndex.query")
             out = (d2 if squared else torch.sqrt(d2), face.long(), closest)
@@ -256,7 +228,7 @@ class TriIndex:
             check(lib.nsa_tri_query_counted(self.buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F,
                                             q.data_ptr(), m, face.data_ptr(), d2.data_ptr(), closest.data_ptr(),
                                             n_eval.data_ptr() if counts else None,
-                                            torch.cuda.current_stream(q.device).cuda_stream))
+                                            stream(q.device)))
         out = (d2 if squared else torch.sqrt(d2), face.long(), closest)
         return out + (n_eval.long(),) if counts else out
 
@@ -273,7 +245,7 @@ class TriIndex:
                 raise ValueError("TriIndex.adjacency: more than (2^31 - 1) / 3 faces")
             buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             check(lib.nsa_tri_adjacency_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), adj.data_ptr(), self.F,
-                                              buf.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+                                              buf.data_ptr(), stream(self.device)))
             self._adjacency[weld] = (adj, buf)
         return self._adjacency[weld]
 
@@ -282,7 +254,7 @@ class TriIndex:
         per ``weld`` setting, like ``adjacency``"""
         weld = bool(weld)
         if weld not in self._topology:
-            from .mesh_topology import topology
+            from .mesh_topology import topology              # (a cycle: mesh_topology welds and casts rays with this module)
             self._topology[weld] = topology({"verts": self.verts, "faces": self.faces}, weld=weld)
         return dict(self._topology[weld])
 
@@ -291,7 +263,7 @@ class TriIndex:
         on first use and kept, once per ``weld`` setting, like ``topology``"""
         weld = bool(weld)
         if weld not in self._orientation:
-            from .mesh_topology import orientation
+            from .mesh_topology import orientation           # (the same cycle)
             self._orientation[weld] = orientation({"verts": self.verts, "faces": self.faces}, weld=weld)
         label, orientable, flip, report = self._orientation[weld]
         return label, orientable, flip, dict(report)
@@ -305,10 +277,10 @@ class TriIndex:
         edge ab / ac / bc of ``face``, -1 without one.  A non-finite query gives (NaN, -1, NaN, -1); a query with nothing within
         ``max_dist`` (None: unbounded), or a mesh without a usable face, (+inf, -1, NaN, -1) -- -inf with ``flip``.
         ``normals=True`` appends N [m, 3] and W [m] float64; ``counts=True`` then the faces evaluated and the cells visited [m] int64."""
-        q = _points(points, "TriIndex.signed_query")
+        q = checked_points(points, "TriIndex.signed_query")
         if q.device != self.device:
             raise ValueError("TriIndex.signed_query: points on another device than the index")
-        max_d2 = _max_d2(max_dist, "TriIndex.signed_query")
+        bound = _max_d2(max_dist, "TriIndex.signed_query")
         m = q.shape[0]
         dev = q.device
         face = torch.empty(m, dtype=torch.int32, device=dev)
@@ -323,12 +295,12 @@ class TriIndex:
         if m:
             adj, buf = self.adjacency(weld)
             check(lib.nsa_tri_signed_query_counted(self.buf.data_ptr(), buf.data_ptr(), self.verts.data_ptr(), self.V,
-                                                   self.faces.data_ptr(), adj.data_ptr(), self.F, q.data_ptr(), m, max_d2,
+                                                   self.faces.data_ptr(), adj.data_ptr(), self.F, q.data_ptr(), m, bound,
                                                    1 if flip else 0, face.data_ptr(), d2.data_ptr(), closest.data_ptr(),
                                                    feature.data_ptr(), sign.data_ptr(), N.data_ptr() if normals else None,
                                                    W.data_ptr() if normals else None, n_eval.data_ptr() if counts else None,
                                                    n_cells.data_ptr() if counts else None,
-                                                   torch.cuda.current_stream(dev).cuda_stream))
+                                                   stream(dev)))
         out = (sign.double() * torch.sqrt(d2), face.long(), closest, feature)
         if normals:
             out += (N, W)
@@ -339,10 +311,10 @@ class TriIndex:
     def _winding_tree(self):
         """(tree buffer, info [3] int32 on the device: L, node count, usable faces) of header Section 16, built on first use and kept"""
         if self._winding is None:
-            buf = torch.empty(lib.nsa_tri_winding_workspace(self.F), dtype=torch.uint8, device=self.device)
+            buf = workspace(lib.nsa_tri_winding_workspace(self.F), self.device)
             info = torch.zeros(3, dtype=torch.int32, device=self.device)
             check(lib.nsa_tri_winding_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, buf.data_ptr(),
-                                            info.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+                                            info.data_ptr(), stream(self.device)))
             self._winding = (buf, info)
         return self._winding
 
@@ -356,7 +328,7 @@ class TriIndex:
         farther than beta r; 2 is theirs, ``math.inf`` the exact sum over all faces.  A non-finite point gives NaN; a mesh without a
         usable face 0.  ``counts=True`` appends the nodes accepted and the faces summed exactly per point [m] int64 (measurements).
         The tree is independent of the closest-point index and built on first use."""
-        q = _points(points, "TriIndex.winding")
+        q = checked_points(points, "TriIndex.winding")
         if q.device != self.device:
             raise ValueError("TriIndex.winding: points on another device than the index")
         beta = float(beta)
@@ -370,7 +342,7 @@ class TriIndex:
             buf, _ = self._winding_tree()
             check(lib.nsa_tri_winding_query(buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, q.data_ptr(),
                                             m, beta, 1 if flip else 0, w.data_ptr(), n_acc.data_ptr() if counts else None,
-                                            n_eval.data_ptr() if counts else None, torch.cuda.current_stream(q.device).cuda_stream))
+                                            n_eval.data_ptr() if counts else None, stream(q.device)))
         return (w, n_acc.long(), n_eval.long()) if counts else w
 
     def winding_layout(self):
@@ -382,10 +354,10 @@ class TriIndex:
     def _ray_tree(self):
         """(tree buffer, info [3] int32 on the device: L, node count, usable faces) of header Section 17, built on first use and kept"""
         if self._ray is None:
-            buf = torch.empty(lib.nsa_tri_ray_workspace(self.F), dtype=torch.uint8, device=self.device)
+            buf = workspace(lib.nsa_tri_ray_workspace(self.F), self.device)
             info = torch.zeros(3, dtype=torch.int32, device=self.device)
             check(lib.nsa_tri_ray_build(self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, buf.data_ptr(),
-                                        info.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+                                        info.data_ptr(), stream(self.device)))
             self._ray = (buf, info)
         return self._ray
 
@@ -399,7 +371,7 @@ class TriIndex:
         not hit) or "front".  ``any_hit=True`` returns bool [m] instead -- whether anything is hit -- and stops each ray at the first
         hit found.  ``brute=True`` tests every usable face (the on-device cross-check).  ``counts=True`` appends the tree nodes
         visited and the faces tested per ray [m] int64 (measurements).  The tree is built on first use."""
-        o, d = _points(origins, "TriIndex.raycast"), _points(dirs, "TriIndex.raycast")
+        o, d = checked_points(origins, "TriIndex.raycast"), checked_points(dirs, "TriIndex.raycast")
         if o.device != self.device or d.device != self.device:
             raise ValueError("TriIndex.raycast: rays on another device than the index")
         if o.shape != d.shape:
@@ -422,7 +394,7 @@ class TriIndex:
             check(lib.nsa_tri_ray_cast(buf.data_ptr(), self.verts.data_ptr(), self.V, self.faces.data_ptr(), self.F, o.data_ptr(),
                                        d.data_ptr(), m, tmin, tmax, flags, t.data_ptr(), face.data_ptr(),
                                        bary.data_ptr() if bary is not None else None, n_nodes.data_ptr() if counts else None,
-                                       n_tested.data_ptr() if counts else None, torch.cuda.current_stream(dev).cuda_stream))
+                                       n_tested.data_ptr() if counts else None, stream(dev)))
         out = (face >= 0,) if any_hit else (t, face.long(), bary)
         if counts:
             return out + (n_nodes.long(), n_tested.long())
@@ -432,7 +404,7 @@ class TriIndex:
         """(pairs int64 [n, 2], code uint8 [n], flags uint8 [F]) on the index's device: the pairs of faces that meet in more than the
         positions they share, decided exactly (header Section 25; ``mesh_intersect.self_intersections`` describes the
         arguments and the report).  Walks the ray-cast tree, built on first use and kept."""
-        from .mesh_intersect import _search
+        from .mesh_intersect import _search                  # (a cycle: mesh_intersect searches a TriIndex)
         *out, report = _search(self, kinds, between, brute)
         return tuple(out) + (report,) if return_report else tuple(out)
 
@@ -455,13 +427,6 @@ class TriIndex:
                 "skipped faces": int(st[2] - st[1])}
 
 
-def _mesh_tensors(mesh, device=None):
-    v, f = mesh["verts"], mesh["faces"]
-    if torch.is_tensor(v) and v.is_cuda and torch.is_tensor(f) and f.is_cuda:
-        return v, f
-    return _as_cuda_mesh(mesh, device if device is not None else "cuda")
-
-
 @torch.no_grad()
 def closest_point(mesh, points):
     """(closest [m, 3] fp32, dist [m] float64, face [m] int64) -- the order of trimesh.proximity.closest_point -- of ``points``
@@ -469,7 +434,7 @@ def closest_point(mesh, points):
     if isinstance(mesh, TriIndex):
         index = mesh
     else:
-        index = TriIndex(*_mesh_tensors(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
+        index = TriIndex(*cuda_verts_faces(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
     if not torch.is_tensor(points):
         points = torch.as_tensor(np.asarray(points), dtype=torch.float32).reshape(-1, 3)
     dist, face, closest = index.query(points.to(index.device))
@@ -527,10 +492,10 @@ def icp_point_to_point(source, target, max_corr=0.1, init=None, max_iter=30, rel
     ``with_scaling``: every update is Umeyama WITH scale (open3d's TransformationEstimationPointToPoint(with_scaling=True),
     CloudCompare's -ADJUST_SCALE), so the transformation is a similarity; everything else in the loop is unchanged.
     Returns dict(transformation [4,4] float64 numpy, fitness, inlier_rmse, iterations).  ``index``: a prebuilt NNIndex of target."""
-    src = _points(source, "icp_point_to_point").double()
+    src = checked_points(source, "icp_point_to_point").double()
     if src.shape[0] == 0:
         raise ValueError("icp_point_to_point: empty source")
-    tgt = _points(target, "icp_point_to_point").double()
+    tgt = checked_points(target, "icp_point_to_point").double()
     index = index if index is not None else NNIndex(target)
     T = np.eye(4) if init is None else np.asarray(init, dtype=np.float64).reshape(4, 4).copy()
     cur = _transform(src, torch.from_numpy(T).to(src.device))
@@ -566,12 +531,6 @@ def _face_normals(v, f):
     e1, e2 = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
     n = torch.linalg.cross(e1, e2)
     return n / n.norm(dim=-1, keepdim=True).clamp_min(1e-300)
-
-
-def _as_cuda_mesh(m, device):
-    v = torch.as_tensor(np.asarray(m["verts"].cpu() if torch.is_tensor(m["verts"]) else m["verts"]), dtype=torch.float32)
-    f = torch.as_tensor(np.asarray(m["faces"].cpu() if torch.is_tensor(m["faces"]) else m["faces"]), dtype=torch.int64)
-    return v.reshape(-1, 3).to(device), f.reshape(-1, 3).to(device)
 
 
 @torch.no_grad()
@@ -611,10 +570,9 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
         raise ValueError(f"mesh_metrics: icp must be 'point', 'plane' or 'surface', got {icp!r}")
     if icp != "point" and adjust_scale:
         raise ValueError(f"mesh_metrics: icp={icp!r} is rigid; adjust_scale goes with icp='point' only")
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_metrics: needs a GPU")
-    rv, rf = _as_cuda_mesh(rec, device)
-    gv, gf = _as_cuda_mesh(gt, device)
+    need_gpu("mesh_metrics")
+    rv, rf = cuda_verts_faces(rec, device, cast=True)
+    gv, gf = cuda_verts_faces(gt, device, cast=True)
     if rv.shape[0] == 0 or rf.shape[0] == 0:
         raise ValueError("mesh_metrics: empty reconstruction")
     if gv.shape[0] == 0 or gf.shape[0] == 0:
@@ -622,7 +580,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
     rv, gv = (rv.double() / scale).float(), (gv.double() / scale).float()
     extra = {}
     if pre_transform is not None or clean is not None:
-        from . import mesh_clean
+        from . import mesh_clean                             # (a cycle: mesh_clean moves vertices with _transform)
         if pre_transform is not None:
             _, P = mesh_clean.check_similarity(pre_transform)
             rv = _transform(rv.double(), torch.from_numpy(P).to(rv.device)).float()
@@ -631,7 +589,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
             rv, rf = kept["verts"], kept["faces"]
             extra = {"components": st["n_components"], "kept area fraction": st["kept_area_fraction"]}
     if cull is not None:
-        from . import mesh_render
+        from . import mesh_render                            # (a cycle: mesh_render -> mesh_clean -> this module)
         n_before = rf.shape[0]
         kept = mesh_render.cull_mesh({"verts": rv, "faces": rf}, **cull)
         rv, rf = kept["verts"], kept["faces"]
@@ -643,7 +601,7 @@ def mesh_metrics(rec, gt, n_points=200000, seed=0, align=True, scale=1.0, device
         if icp == "point":
             res = icp_point_to_point(rv, gv, 0.1, with_scaling=adjust_scale)
         else:
-            from . import mesh_register, mesh_smooth
+            from . import mesh_register, mesh_smooth         # (cycles: both are built on this module's indexes)
             if icp == "plane":
                 gn = mesh_smooth.vertex_normals({"verts": gv, "faces": gf.to(torch.int32)}, "angle")
                 res = mesh_register.icp_point_to_plane(rv, gv, gn, 0.1)
@@ -714,7 +672,6 @@ def metrics_from_surfaces(rec_pts, rec_normals, rec_mesh, gt_pts, gt_normals, gt
 
 
 def main(argv=None):
-    from .inference import read_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_eval", description=__doc__.splitlines()[0])
     ap.add_argument("rec")
     ap.add_argument("gt")
@@ -748,7 +705,7 @@ def main(argv=None):
         ap.error("--cull-intrinsics and --cull-size go with --cull-poses")
     cull = None
     if a.cull_poses:
-        from .mesh_render import read_poses
+        from .mesh_render import read_poses                  # (the cycle named in mesh_metrics)
         cull = dict(c2w=read_poses(a.cull_poses), intrinsics=a.cull_intrinsics, size=tuple(a.cull_size), mode=a.cull_mode)
         if a.cull_raycast:
             cull["method"] = "raycast"

@@ -22,13 +22,15 @@ import json
 import math
 import sys
 
-import numpy as np
 import torch
 
 from . import _native
 from ._native import lib, check
-from .mesh_smooth import WEIGHTING, _mesh, _vertex_normals
-from .mesh_topology import _edge_table, _mesh_arrays, _need_gpu
+from .mesh_args import MAX_FACES_RINGS, as_tensor, checked_mesh, need_gpu, ptr, stream, workspace
+from .mesh_eval import TriIndex
+from .mesh_smooth import WEIGHTING, _vertex_normals, smooth
+from .mesh_topology import _edge_table, _mesh_arrays
+from .ply import read_ply, write_mesh_ply
 
 CLASSES = _native.FILL_CLASSES
 TOTALS = ("n_boundary", "n_loops", "n_filled", "n_nonfinite", "n_pinched", "n_too_many_edges", "n_too_large", "n_folded",
@@ -44,10 +46,6 @@ AREA_TOTALS = ("n_selected", "n_area_filled", "n_area_too_many_edges", "n_no_tri
 AREA_INT_COLS = ("class", "n", "table_offset", "plan_face_offset", "row_offset", "face_offset")
 _MAX_AREA_EDGES = 16384
 _MAX_RINGS = 65535
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _checked_args(max_edges, max_size, rings, max_rings, fair, lam, normals, method="polar", max_area_edges=2048, min_sin=1e-6,
@@ -93,16 +91,15 @@ def _loops(v, f, names, mask, colors, V, F, max_edges, max_size, rings, max_ring
     r["_ints"], r["_reals"], r["_order"], r["_edge"] = r["ints"], r["reals"], r["order"], t
     if F == 0 or B == 0:
         return r
-    ws = torch.empty(lib.nsa_mesh_fill_workspace(F, B), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_fill_workspace(F, B), dev)
     tot = torch.zeros(len(TOTALS), dtype=torch.int64, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()
     check(lib.nsa_mesh_fill_loops(v.data_ptr(), ptr(colors), V, f.data_ptr(), ptr(names), F, t["edge_count"].data_ptr(),
                                   t["edge_forward"].data_ptr(), t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(),
                                   t["face_edges"].data_ptr(), t["_totals"].data_ptr(), B, int(max_edges is not None), int(max_edges or 0),
                                   int(max_size is not None), 0.0 if max_size is None else float(max_size) * float(max_size), rings,
                                   int(max_rings), int(bool(skip_folded)), ws.data_ptr(), r["halfedges"].data_ptr(), r["next"].data_ptr(),
                                   r["flags"].data_ptr(), r["leader"].data_ptr(), r["rank"].data_ptr(), r["order"].data_ptr(),
-                                  r["ints"].data_ptr(), r["reals"].data_ptr(), tot.data_ptr(), _stream(dev)))
+                                  r["ints"].data_ptr(), r["reals"].data_ptr(), tot.data_ptr(), stream(dev)))
     r["_totals"] = tot
     host = dict(zip(TOTALS, (int(x) for x in tot.cpu())))
     if host["status"] != 0:
@@ -123,10 +120,10 @@ def _emit(v, f, colors, V, F, r):
     out_c = None if colors is None else torch.cat([colors, torch.zeros(NV, 3, dtype=torch.float32, device=dev)])
     out_f = torch.cat([f, torch.full((NF, 3), -1, dtype=torch.int32, device=dev)])
     if NF:
-        check(lib.nsa_mesh_fill_emit(v.data_ptr(), None if colors is None else colors.data_ptr(), V, f.data_ptr(), F,
+        check(lib.nsa_mesh_fill_emit(v.data_ptr(), ptr(colors), V, f.data_ptr(), F,
                                      r["_order"].data_ptr(), r["B"], r["_ints"].data_ptr(), r["_reals"].data_ptr(),
                                      r["_totals"].data_ptr(), NV, NF, out_v[V:].data_ptr(),
-                                     None if out_c is None else out_c[V:].data_ptr(), out_f[F:].data_ptr(), _stream(dev)))
+                                     None if out_c is None else out_c[V:].data_ptr(), out_f[F:].data_ptr(), stream(dev)))
     return out_v, out_c, out_f
 
 
@@ -149,22 +146,22 @@ def _area(v, f, names, V, F, r, class_mask, max_area_edges, min_sin, tables=Fals
         return out
     plan = torch.zeros(8, dtype=torch.int64, device=dev)
     check(lib.nsa_mesh_fill_area_plan(r["_ints"].data_ptr(), r["_totals"].data_ptr(), F, B, class_mask, int(max_area_edges),
-                                      ints.data_ptr(), plan.data_ptr(), _stream(dev)))
+                                      ints.data_ptr(), plan.data_ptr(), stream(dev)))
     selected, tabled, too_many, cells, max_n, plan_faces, rows, _ = (int(x) for x in plan.cpu())
     out["totals"].update(n_selected=selected, n_area_too_many_edges=too_many, n_no_triangulation=selected - tabled - too_many,
                          n_cells=cells, max_n=max_n)
     if tabled == 0:
         return out
-    ws = torch.empty(lib.nsa_mesh_fill_area_workspace(cells, rows), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_fill_area_workspace(cells, rows), dev)
     area = torch.zeros(B, dtype=torch.float64, device=dev)
     faces = torch.full((plan_faces, 3), -1, dtype=torch.int32, device=dev)
     final = torch.zeros(4, dtype=torch.int64, device=dev)
     t = r["_edge"]
-    check(lib.nsa_mesh_fill_area_tables(v.data_ptr(), V, f.data_ptr(), None if names is None else names.data_ptr(), F,
+    check(lib.nsa_mesh_fill_area_tables(v.data_ptr(), V, f.data_ptr(), ptr(names), F,
                                         t["edges"].data_ptr(), t["_totals"].data_ptr(), r["_order"].data_ptr(), B, r["_ints"].data_ptr(),
                                         r["_totals"].data_ptr(), ints.data_ptr(), cells, rows, max_n, plan_faces,
                                         float(min_sin) * float(min_sin), ws.data_ptr(), area.data_ptr(), faces.data_ptr(),
-                                        final.data_ptr(), _stream(dev)))
+                                        final.data_ptr(), stream(dev)))
     filled, too_many, no_tri, n_faces = (int(x) for x in final.cpu())
     if no_tri:                                               # (their rows are -1; dropping them gives the final numbering)
         faces = faces[faces[:, 0] >= 0].contiguous()
@@ -181,12 +178,8 @@ def _area(v, f, names, V, F, r, class_mask, max_area_edges, min_sin, tables=Fals
 
 def _arrays(mesh, name, weld, device):
     """(verts, faces, names or None, mask or None, colours or None, V, F, give)"""
-    v, f, V, F, give = _mesh(mesh, name, device)
-    colors = mesh.get("colors")
-    if colors is not None:
-        if tuple(colors.shape) != (V, 3):
-            raise ValueError(f"{name}: colors must be [V, 3]")
-        colors = (colors if torch.is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors))).to(v.device).float().contiguous()
+    v, f, V, F, extra, give = checked_mesh(mesh, name, device, float_verts=True, attributes=("colors",), max_faces=MAX_FACES_RINGS)
+    colors = extra.get("colors")
     names = mask = None
     if weld and F and V:
         names, _, _, mask, _, _ = _mesh_arrays({"verts": v, "faces": f}, True, v.device, name)
@@ -224,7 +217,6 @@ def _area_report(out, r, a, give, method):
 
 def _patch_intersections(out_v, out_f, F, rep, method):
     """per loop: the proper pairs of the filled mesh with exactly one face in the loop's patch"""
-    from .mesh_eval import TriIndex
     L, FT = len(rep["n"]), out_f.shape[0]
     if FT == 0 or out_v.shape[0] == 0:
         return [0] * L
@@ -304,7 +296,6 @@ def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, 
             raise ValueError("fill_holes: the filled mesh leaves the index range (n_verts < 2^31, 3 * n_faces < 2^31)")
     NV = out_v.shape[0] - V
     if fair and NV:
-        from .mesh_smooth import smooth
         fixed = torch.ones(V + NV, dtype=torch.uint8, device=v.device)
         fixed[V:] = 0
         out_v = smooth({"verts": out_v, "faces": out_f}, method="laplacian", iterations=int(fair), lam=lam, fixed=fixed,
@@ -316,7 +307,7 @@ def fill_holes(mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, 
     if normals in WEIGHTING:
         result["normals"] = give(_vertex_normals(out_v.contiguous(), out_f.contiguous(), V + NV, F + out_f.shape[0] - F, normals))
     elif normals == "keep" and stored is not None:
-        old = (stored if torch.is_tensor(stored) else torch.from_numpy(np.ascontiguousarray(stored))).to(v.device).float()
+        old = as_tensor(stored).to(v.device).float()
         new = _vertex_normals(out_v.contiguous(), out_f.contiguous(), V + NV, out_f.shape[0], "angle")[V:] if NV else old[:0]
         result["normals"] = give(torch.cat([old, new]))
     if return_report:
@@ -350,7 +341,6 @@ def format_report(rep):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_fill", description=__doc__.splitlines()[0])
     ap.add_argument("mesh", metavar="IN.ply")
     ap.add_argument("--out", default=None, metavar="OUT.ply")
@@ -374,17 +364,14 @@ def main(argv=None):
             a.rings = int(a.rings)
         except ValueError:
             ap.error("--rings takes auto or an integer")
-    _need_gpu("mesh_fill")
+    need_gpu("mesh_fill")
     try:
         mesh = read_ply(a.mesh)
         r, rep = fill_holes(mesh, max_edges=a.max_edges, max_size=a.max_size, rings=a.rings, skip_folded=not a.keep_folded, fair=a.fair,
                             normals=a.normals, weld=a.weld, return_report=True, method=a.method, max_area_edges=a.max_area_edges,
                             min_sin=a.min_sin)
         if a.out is not None:
-            ply = {k: torch.from_numpy(np.ascontiguousarray(r[k])) for k in ("verts", "faces", "normals", "colors") if k in r}
-            if "normals" not in ply:                      # (write_ply stores normals; a file without them gets zeros)
-                ply["normals"] = torch.zeros_like(ply["verts"])
-            write_ply(a.out, ply)
+            write_mesh_ply(a.out, r)
     except (ValueError, OSError) as e:
         print(f"mesh_fill: {e}", file=sys.stderr)
         raise SystemExit(2)

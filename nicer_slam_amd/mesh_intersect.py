@@ -24,6 +24,11 @@ import sys
 import numpy as np
 import torch
 
+from ._native import check, lib
+from .mesh_args import as_tensor, mesh_dict_tensors, need_gpu, stream, workspace
+from .mesh_eval import TriIndex
+from .ply import read_ply, write_mesh_ply
+
 PROPER, TOUCH, UNRESOLVED, COPLANAR = 1, 2, 3, 4
 BRUTE = 1
 KINDS = ("proper", "touch")
@@ -183,29 +188,28 @@ def _late_faces(ix, state, side):
 @torch.no_grad()
 def _search(ix, kinds=KINDS, between=None, brute=False):
     """(pairs, code, flags, report) on the index's device"""
-    from ._native import check, lib
     kinds = _kinds(kinds)
     F, dev = ix.F, ix.device
     side = None
     if between is not None:
-        side = between if torch.is_tensor(between) else torch.from_numpy(np.ascontiguousarray(np.asarray(between)))
+        side = as_tensor(between)
         if side.dim() != 1 or side.shape[0] != F or side.dtype not in (torch.bool, torch.uint8):
             raise ValueError(f"between: a bool mask of {F} faces, got {tuple(side.shape)} {side.dtype}")
         side = (side.to(dev) != 0).to(torch.uint8).contiguous()
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    st = stream(dev)
     buf, _ = ix._ray_tree()
-    ws = torch.empty(lib.nsa_tri_isect_workspace(F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_tri_isect_workspace(F), dev)
     state = torch.empty(F, dtype=torch.uint8, device=dev)
     totals = torch.zeros(16, dtype=torch.int64, device=dev)
     flags = BRUTE if brute else 0
     mesh = (buf.data_ptr(), ix.verts.data_ptr(), ix.V, ix.faces.data_ptr(), F, side.data_ptr() if side is not None else None, flags)
-    check(lib.nsa_tri_isect_count(*mesh, ws.data_ptr(), state.data_ptr(), totals.data_ptr(), stream))
+    check(lib.nsa_tri_isect_count(*mesh, ws.data_ptr(), state.data_ptr(), totals.data_ptr(), st))
     t = [int(x) for x in totals.cpu()]
     n = t[0]
     pairs = torch.empty(n, 2, dtype=torch.int64, device=dev)
     code = torch.empty(n, dtype=torch.uint8, device=dev)
     if n:
-        check(lib.nsa_tri_isect_emit(*mesh, ws.data_ptr(), state.data_ptr(), n, pairs.data_ptr(), code.data_ptr(), stream))
+        check(lib.nsa_tri_isect_emit(*mesh, ws.data_ptr(), state.data_ptr(), n, pairs.data_ptr(), code.data_ptr(), st))
     by_s, n_host, n_collinear = list(t[1:5]), 0, t[11]
     late = (code & 3) == UNRESOLVED
     if bool(late.any()):                                  # pairs beyond the device's width
@@ -245,13 +249,10 @@ def _search(ix, kinds=KINDS, between=None, brute=False):
 
 
 def _index(mesh, device="cuda"):
-    from .mesh_clean import _mesh_tensors
-    from .mesh_eval import TriIndex
     if isinstance(mesh, TriIndex):
         return mesh, False, mesh.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_intersect: needs a GPU")
-    m, was_numpy, orig = _mesh_tensors(mesh, device)
+    need_gpu("mesh_intersect")
+    m, was_numpy, orig = mesh_dict_tensors(mesh, device)
     if m["verts"].shape[0] == 0 or m["faces"].shape[0] == 0:
         return None, was_numpy, orig
     return TriIndex(m["verts"], m["faces"]), was_numpy, orig
@@ -290,7 +291,6 @@ def format_report(r):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_intersect", description=__doc__.splitlines()[0])
     ap.add_argument("mesh")
     ap.add_argument("--kinds", choices=("proper", "touch", "all"), default="all")
@@ -312,11 +312,7 @@ def main(argv=None):
             f = np.asarray(mesh["faces"]).reshape(-1, 3)
             col[f[(flags & 2) != 0].reshape(-1)] = (1.0, 1.0, 0.0)
             col[f[(flags & 1) != 0].reshape(-1)] = (1.0, 0.0, 0.0)
-            ply = {k: torch.from_numpy(np.ascontiguousarray(mesh[k])) for k in ("verts", "faces", "normals") if k in mesh}
-            if "normals" not in ply:
-                ply["normals"] = torch.zeros_like(ply["verts"])
-            ply["colors"] = torch.from_numpy(col)
-            write_ply(a.out, ply)
+            write_mesh_ply(a.out, dict(mesh, colors=col))
     except (ValueError, OSError) as e:
         print(f"mesh_intersect: {e}", file=sys.stderr)
         raise SystemExit(2)

@@ -22,8 +22,9 @@ import sys
 import numpy as np
 import torch
 
-from .mesh_clean import _mesh_tensors
+from .mesh_args import mesh_dict_tensors, need_gpu
 from .mesh_eval import TriIndex
+from .ply import read_ply
 from .tsdf import _as_numpy, _intrinsics4
 
 CHANNELS = ("depth", "face_id", "normal")
@@ -35,13 +36,13 @@ def _index(mesh_or_index, device="cuda"):
     """(TriIndex, was_numpy, original device) of a mesh dict or an index"""
     if isinstance(mesh_or_index, TriIndex):
         return mesh_or_index, False, mesh_or_index.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_raycast: needs a GPU")
-    m, was_numpy, orig = _mesh_tensors(mesh_or_index, device)
+    need_gpu("mesh_raycast")
+    m, was_numpy, orig = mesh_dict_tensors(mesh_or_index, device)
     return TriIndex(m["verts"], m["faces"]), was_numpy, orig
 
 
 def _rays(x, name, dev):
+    # (not mesh_args.checked_points: rays may be arrays or live on another device, and are moved to the index's)
     t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
     if t.dim() != 2 or t.shape[1] != 3:
         raise ValueError(f"{name}: needs shape [m, 3], got {tuple(t.shape)}")
@@ -244,9 +245,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     from PIL import Image
-    from .inference import read_ply
-    from .mesh_clean import transform_mesh
-    from .mesh_render import read_poses
+    from .mesh_clean import transform_mesh            # (a cycle: mesh_clean -> mesh_topology -> this module)
+    from .mesh_render import read_poses               # (a cycle: mesh_render is built on this module)
     a = parse_args(argv)
     try:
         mesh = read_ply(a.mesh)

@@ -31,13 +31,13 @@ import torch
 
 from . import _native
 from ._native import check, lib
-from .mesh_eval import NNIndex, TriIndex, _max_d2, _mesh_tensors, _points
+from .cloud_normals import estimate_normals
+from .mesh_args import as_tensor, checked_points, cuda_verts_faces, max_d2, need_gpu, ptr, stream, workspace
+from .mesh_eval import NNIndex, TriIndex, _transform
+from .mesh_smooth import vertex_normals
+from .ply import read_ply, write_mesh_ply
 
 _KERNEL_CODE = {name: code for code, name in enumerate(_native.ICP_KERNELS)}
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _kernel(kernel):
@@ -52,8 +52,8 @@ def _kernel(kernel):
 
 
 def _cuda(x, dtype, device="cuda"):
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(np.ascontiguousarray(x))
+    # (not mesh_args.checked_points: any dtype and shape, cast and moved; the callers check the shapes against each other)
+    x = as_tensor(x)
     return x.detach().to(device=device if not x.is_cuda else x.device, dtype=dtype).contiguous()
 
 
@@ -115,7 +115,7 @@ def _matmul4(U, T):
 def _move(cur, upd, cur32):
     """nsa_icp_transform: cur [n, 3] float64 moved in place by the 4x4 ``upd``, its fp32 rounding into cur32"""
     m = (ctypes.c_double * 16)(*np.asarray(upd, np.float64).reshape(16).tolist())
-    check(lib.nsa_icp_transform(cur.data_ptr(), cur.shape[0], m, cur32.data_ptr(), _stream(cur.device)))
+    check(lib.nsa_icp_transform(cur.data_ptr(), cur.shape[0], m, cur32.data_ptr(), stream(cur.device)))
 
 
 class _System:
@@ -123,17 +123,16 @@ class _System:
 
     def __init__(self, n, device):
         self.n = n
-        self.ws = torch.empty(lib.nsa_icp_plane_system_workspace(n), dtype=torch.uint8, device=device)
+        self.ws = workspace(lib.nsa_icp_plane_system_workspace(n), device)
         self.out = torch.zeros(32, dtype=torch.int64, device=device)        # 30 float64 sums, then 2 counts
 
     def run(self, cur, mode, corr, cloud, surface, code, k):
         dist, targets, normals = cloud if cloud else (None, None, None)
         d2, closest, verts, faces = surface if surface else (None, None, None, None)
-        ptr = lambda x: x.data_ptr() if x is not None else None
         check(lib.nsa_icp_plane_system(cur.data_ptr(), self.n, mode, corr.data_ptr(), ptr(dist), ptr(targets), ptr(normals),
                                        targets.shape[0] if cloud else 0, ptr(d2), ptr(closest), ptr(verts),
                                        verts.shape[0] if surface else 0, ptr(faces), faces.shape[0] if surface else 0, code, k,
-                                       self.ws.data_ptr(), self.out.data_ptr(), self.out.data_ptr() + 240, _stream(cur.device)))
+                                       self.ws.data_ptr(), self.out.data_ptr(), self.out.data_ptr() + 240, stream(cur.device)))
 
     def read(self):
         """the one readback: dict(sums [30], k_corr, k_used, A [6, 6], b [6])"""
@@ -209,11 +208,10 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
     used rows), ``used`` (rows with a correspondence and a usable normal) and ``degenerate``: the last system left a motion free
     (``ldlt_solve`` gave None), the update was the identity and the loop ended there."""
     code, k = _kernel(kernel)
-    if not torch.cuda.is_available():
-        raise RuntimeError("icp_point_to_plane: needs a GPU")
+    need_gpu("icp_point_to_plane")
     if not torch.is_tensor(source):
         source = torch.as_tensor(np.asarray(source, np.float32)).reshape(-1, 3).cuda()
-    src32 = _points(source, "icp_point_to_plane")
+    src32 = checked_points(source, "icp_point_to_plane")
     n, dev = src32.shape[0], src32.device
     if n == 0:
         raise ValueError("icp_point_to_plane: empty source")
@@ -222,17 +220,17 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
         if normals is not None:
             raise ValueError("icp_point_to_plane: normals go with a cloud target; a mesh target takes its faces' normals")
         if index is None:
-            index = target if isinstance(target, TriIndex) else TriIndex(*_mesh_tensors(
+            index = target if isinstance(target, TriIndex) else TriIndex(*cuda_verts_faces(
                 target if isinstance(target, dict) else {"verts": target[0], "faces": target[1]}, dev))
         if not isinstance(index, TriIndex):
             raise ValueError("icp_point_to_plane: a mesh target takes a TriIndex")
-        max_d2 = _max_d2(max_corr, "icp_point_to_plane")
+        bound = max_d2(max_corr, "icp_point_to_plane")
     else:
         if normals is None:
             raise ValueError("icp_point_to_plane: a cloud target needs normals [m, 3]")
         if not torch.is_tensor(target):
             target = torch.as_tensor(np.asarray(target, np.float32)).reshape(-1, 3).to(dev)
-        tgt = _points(target, "icp_point_to_plane")
+        tgt = checked_points(target, "icp_point_to_plane")
         if isinstance(normals, str) and normals != "estimate":
             raise ValueError(f"icp_point_to_plane: normals must be [m, 3], 'estimate' or dict(k=, max_dist=, viewpoint=), got {normals!r}")
         estimate = normals if isinstance(normals, dict) else ({} if isinstance(normals, str) else None)
@@ -246,7 +244,6 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
         if not isinstance(index, NNIndex) or index.n != tgt.shape[0]:
             raise ValueError("icp_point_to_plane: a cloud target takes an NNIndex of the same targets")
         if estimate is not None:                       # once, on the index the loop queries anyway
-            from .cloud_normals import estimate_normals
             nrm = estimate_normals(tgt, index=index, **estimate)
         if not float(max_corr) > 0:
             raise ValueError("icp_point_to_plane: max_corr must be > 0")
@@ -265,10 +262,10 @@ def icp_point_to_plane(source, target, normals=None, max_corr=0.1, init=None, ma
         dist = torch.empty(n, dtype=torch.float32, device=dev)
 
     def evaluate():
-        s = _stream(dev)
+        s = stream(dev)
         if surface_mode:
             check(lib.nsa_tri_query_bounded(index.buf.data_ptr(), index.verts.data_ptr(), index.V, index.faces.data_ptr(), index.F,
-                                            cur32.data_ptr(), n, max_d2, corr.data_ptr(), d2.data_ptr(), closest.data_ptr(), None, None, s))
+                                            cur32.data_ptr(), n, bound, corr.data_ptr(), d2.data_ptr(), closest.data_ptr(), None, None, s))
             system.run(cur, _native.ICP_SURFACE, corr, None, (d2, closest, index.verts, index.faces), code, k)
         else:
             check(lib.nsa_nn_query(index.buf.data_ptr(), index.n, cur32.data_ptr(), n, float(max_corr), corr.data_ptr(), dist.data_ptr(), s))
@@ -311,9 +308,6 @@ def _parse_kernel(text):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
-    from .mesh_eval import _transform
-    from .mesh_smooth import vertex_normals
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_register", description=__doc__.splitlines()[0])
     ap.add_argument("source", metavar="SRC.ply")
     ap.add_argument("target", metavar="TGT.ply")
@@ -347,15 +341,12 @@ def main(argv=None):
             np.save(a.out_transform, r["transformation"])
         if a.out:
             T = torch.from_numpy(r["transformation"]).cuda()
-            ply = {k: torch.as_tensor(np.ascontiguousarray(src[k])) for k in ("verts", "faces", "normals", "colors") if k in src}
-            ply["verts"] = _transform(sv.double(), T).float().cpu()
-            if "normals" in ply:
+            moved = dict(src, verts=_transform(sv.double(), T).float())
+            if "normals" in src:
                 R = T.clone()
                 R[:3, 3] = 0
-                ply["normals"] = _transform(ply["normals"].double().cuda(), R).float().cpu()
-            else:
-                ply["normals"] = torch.zeros_like(ply["verts"])
-            write_ply(a.out, ply)
+                moved["normals"] = _transform(torch.as_tensor(np.ascontiguousarray(src["normals"])).double().cuda(), R).float()
+            write_mesh_ply(a.out, moved)
     except (ValueError, OSError) as e:
         print(f"mesh_register: {e}", file=sys.stderr)
         raise SystemExit(2)

@@ -21,7 +21,11 @@ import numpy as np
 import torch
 
 from ._native import RasterViews, check, lib
-from .mesh_clean import _mesh_tensors, _restore, select_faces, transform_mesh
+from .mesh_args import checked_faces, mesh_dict_tensors, need_gpu, ptr, restore_dict, stream, workspace
+from .mesh_clean import select_faces, transform_mesh
+from .mesh_eval import TriIndex
+from .mesh_raycast import occluded, render_depth
+from .ply import read_ply, write_mesh_ply
 from .tsdf import _as_numpy, _intrinsics4, world_to_camera
 
 CHANNELS = ("depth", "face_id", "normal", "colour", "shaded")
@@ -54,17 +58,11 @@ class _Scene:
             raise ValueError("c2w: no pose")
         K = _intrinsics4(intrinsics, self.n).astype(np.float32)
         self.per_view = K.shape[0] > 1
-        if not torch.cuda.is_available():
-            raise RuntimeError("mesh_render: needs a GPU")
-        m, self.was_numpy, self.orig = _mesh_tensors(mesh, device)
+        need_gpu("mesh_render")
+        m, self.was_numpy, self.orig = mesh_dict_tensors(mesh, device)
         self.dev = m["verts"].device
         self.verts = m["verts"].detach().float().contiguous()
-        f = m["faces"]
-        if f.dtype not in (torch.int32, torch.int64):
-            raise ValueError("mesh: faces must be int32 or int64")
-        if f.dtype == torch.int64 and f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) >= 2 ** 31):
-            raise ValueError("mesh: face index outside int32")
-        self.faces = f.to(torch.int32).contiguous()
+        self.faces = checked_faces(m["faces"], "mesh").to(torch.int32).contiguous()
         self.colours = m["colors"].detach().float().contiguous() if "colors" in m else None
         self.w2c = torch.from_numpy(w2c).to(self.dev)
         self.K = torch.from_numpy(np.ascontiguousarray(K)).to(self.dev)
@@ -78,16 +76,15 @@ class _Scene:
                queue_capacity=QUEUE_CAPACITY):
         """-> (zbuf int64 [m, H, W] holding the uint64 keys, totals int64 [N_TOTALS]) for views lo .. lo + m"""
         if self.ws is None or self.ws.numel() < lib.nsa_mesh_raster_workspace(queue_capacity):
-            self.ws = torch.empty(lib.nsa_mesh_raster_workspace(queue_capacity), dtype=torch.uint8, device=self.dev)
+            self.ws = workspace(lib.nsa_mesh_raster_workspace(queue_capacity), self.dev)
         zbuf = torch.empty((m, self.H, self.W), dtype=torch.int64, device=self.dev)
         totals = torch.empty(N_TOTALS, dtype=torch.int64, device=self.dev)
         V, F = self.verts.shape[0], self.faces.shape[0]
         P = 0 if points is None else points.shape[0]
         v = self.views(lo, m)
-        check(lib.nsa_mesh_raster(self.verts.data_ptr() if V else None, V, self.faces.data_ptr() if F else None, F,
-                                  points.data_ptr() if P else None, P, int(point_size), ctypes.byref(v), int(cull_backface), 1,
-                                  int(large_threshold), self.ws.data_ptr(), int(queue_capacity), zbuf.data_ptr(), totals.data_ptr(),
-                                  torch.cuda.current_stream(self.dev).cuda_stream))
+        check(lib.nsa_mesh_raster(ptr(self.verts), V, ptr(self.faces), F, ptr(points), P, int(point_size), ctypes.byref(v),
+                                  int(cull_backface), 1, int(large_threshold), self.ws.data_ptr(), int(queue_capacity), zbuf.data_ptr(),
+                                  totals.data_ptr(), stream(self.dev)))
         return zbuf, totals
 
     def resolve(self, lo, m, zbuf, channels, flip_to_camera=True, point_colour=None, palette=None):
@@ -107,26 +104,17 @@ class _Scene:
         P = 0 if point_colour is None else point_colour.shape[0]
         p = lambda k: out[k].data_ptr() if k in out else None
         v = self.views(lo, m)
-        check(lib.nsa_mesh_raster_resolve(self.verts.data_ptr() if V else None, V, self.faces.data_ptr() if F else None, F,
-                                          self.colours.data_ptr() if self.colours is not None and V else None,
-                                          point_colour.data_ptr() if P else None, P,
-                                          palette.data_ptr() if palette is not None else None,
+        check(lib.nsa_mesh_raster_resolve(ptr(self.verts), V, ptr(self.faces), F, ptr(self.colours), ptr(point_colour), P, ptr(palette),
                                           0 if palette is None else palette.shape[0], ctypes.byref(v), zbuf.data_ptr(),
                                           int(flip_to_camera), p("face_id"), p("depth"), p("normal"), p("colour"), p("shaded"),
-                                          torch.cuda.current_stream(self.dev).cuda_stream))
+                                          stream(self.dev)))
         return out
 
     def visible(self, lo, m, zbuf, mode, rel, flags):
         V, F = self.verts.shape[0], self.faces.shape[0]
         v = self.views(lo, m)
-        check(lib.nsa_mesh_visible(self.verts.data_ptr() if V else None, V, self.faces.data_ptr() if F else None, F, ctypes.byref(v),
-                                   zbuf.data_ptr() if zbuf is not None else None, MODES[mode], float(rel),
-                                   flags.data_ptr() if F else None, torch.cuda.current_stream(self.dev).cuda_stream))
-
-
-def _ray_index(sc):
-    from .mesh_eval import TriIndex
-    return TriIndex(sc.verts, sc.faces)
+        check(lib.nsa_mesh_visible(ptr(self.verts), V, ptr(self.faces), F, ctypes.byref(v), ptr(zbuf), MODES[mode], float(rel), ptr(flags),
+                                   stream(self.dev)))
 
 
 def _points_arg(points, dev):
@@ -175,7 +163,7 @@ def render_mesh(mesh, c2w, intrinsics, size, near=DEFAULT_NEAR, channels=CHANNEL
         totals += t
         parts.append(sc.resolve(lo, m, zbuf, channels, flip_to_camera, pidx, pal))
     out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
-    out = _restore(out, sc.was_numpy, sc.orig)
+    out = restore_dict(out, sc.was_numpy, sc.orig)
     out["totals"] = dict(zip(TOTALS, (int(x) for x in totals.cpu())))
     return out
 
@@ -191,8 +179,6 @@ def _visible_by_rays(sc, c2w, mode, rel):
     ``near`` that project inside the image are found by the frustum test of ``"frustum"`` (the same kernel, run on one degenerate
     face per vertex); of those, a vertex is seen when nothing is hit on the way from the camera centre to it, up to 1 - rel of the way
     (``mesh_raycast.occluded``)."""
-    from .mesh_eval import TriIndex
-    from .mesh_raycast import occluded
     F, V = sc.faces.shape[0], sc.verts.shape[0]
     flags = torch.zeros(F, dtype=torch.bool, device=sc.dev)
     if F == 0 or V == 0:
@@ -206,7 +192,7 @@ def _visible_by_rays(sc, c2w, mode, rel):
         inside = torch.zeros(V, dtype=torch.uint8, device=sc.dev)
         v = sc.views(i, 1)
         check(lib.nsa_mesh_visible(sc.verts.data_ptr(), V, each.data_ptr(), V, ctypes.byref(v), None, MODES["frustum"], 0.0,
-                                   inside.data_ptr(), torch.cuda.current_stream(sc.dev).cuda_stream))
+                                   inside.data_ptr(), stream(sc.dev)))
         seen = inside.bool()
         if ix is not None:
             idx = torch.nonzero(seen)[:, 0]
@@ -274,9 +260,8 @@ def depth_l1(mesh, depth_frames, c2w, intrinsics, near=DEFAULT_NEAR, batch=8, de
     for lo in range(0, sc.n, batch):
         m = min(batch, sc.n - lo)
         if method == "raycast":
-            from .mesh_raycast import render_depth
             if ix is None:
-                ix = _ray_index(sc)
+                ix = TriIndex(sc.verts, sc.faces)
                 c2w_all, K_all = _as_numpy(c2w, np.float64).reshape(-1, 4, 4), _intrinsics4(intrinsics, sc.n)
             r = render_depth(ix, c2w_all[lo:lo + m], K_all[lo:lo + m] if K_all.shape[0] > 1 else K_all, (sc.H, sc.W), near,
                              ("depth",))["depth"].to(sc.dev)
@@ -407,7 +392,6 @@ def fly_through(mesh_or_paths, est_c2w, gt_c2w=None, sim3=None, out_dir=".", vie
     ``background``; one ``%06d.png`` per frame in ``out_dir``.  Returns the list of files."""
     if viewpoint not in ("behind_first", "follow"):
         raise ValueError("viewpoint must be 'behind_first' or 'follow'")
-    from .inference import read_ply
     est = _as_numpy(est_c2w, np.float64).reshape(-1, 4, 4)
     gt = None if gt_c2w is None else _as_numpy(gt_c2w, np.float64).reshape(-1, 4, 4)
     if gt is not None and len(gt) != len(est):
@@ -477,7 +461,6 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     a = parse_args(argv)
     try:
         mesh = read_ply(a.mesh)
@@ -495,10 +478,7 @@ def main(argv=None):
             culled = cull_mesh(mesh, poses, a.intrinsics, a.size, a.mode, a.rel, a.near, method="raycast" if a.raycast else "raster")
             print(f"{a.cull}: kept {culled['faces'].shape[0]} of {mesh['faces'].shape[0]} faces, "
                   f"{culled['verts'].shape[0]} of {mesh['verts'].shape[0]} vertices")
-            out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in culled.items() if k in ("verts", "normals", "colors", "faces")}
-            if "normals" not in out:
-                out["normals"] = torch.zeros_like(out["verts"])
-            write_ply(a.cull, out)
+            write_mesh_ply(a.cull, culled)
         if a.out:
             files = fly_through(mesh, poses, gt, None, a.out, "follow" if a.follow else "behind_first", tuple(a.viewer_size), near=a.near)
             print(f"{a.out}: {len(files)} images")

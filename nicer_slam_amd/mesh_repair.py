@@ -21,7 +21,10 @@ import numpy as np
 import torch
 
 from ._native import lib, check, SPLIT_CUT_INCONSISTENT
-from .mesh_topology import _edge_table, _mesh_arrays, _need_gpu
+from .mesh_args import as_tensor, checked_rows, cuda_faces, need_gpu, ptr, stream, workspace
+from .mesh_eval import welded_faces
+from .mesh_topology import _edge_table, _mesh_arrays
+from .ply import read_ply, write_mesh_ply
 
 TOTALS = ("n_contributing", "n_fans", "n_singular_verts", "n_pinch_only", "n_cut_edges", "n_new", "max_fans")
 _ATTRIBUTES = ("verts", "normals", "colors")
@@ -30,7 +33,7 @@ _ATTRIBUTES = ("verts", "normals", "colors")
 def _checked_labels(labels, F, _dev, name):
     if labels is None:
         return None
-    lab = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    lab = as_tensor(labels)
     if lab.dim() != 1 or lab.shape[0] != F:
         raise ValueError(f"{name}: labels must be [F] = [{F}]")
     if lab.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8, torch.bool):
@@ -38,13 +41,6 @@ def _checked_labels(labels, F, _dev, name):
     if lab.numel() and lab.dtype == torch.int64 and (int(lab.min()) < -2 ** 31 or int(lab.max()) >= 2 ** 31):
         raise ValueError(f"{name}: label outside int32")
     return lab
-
-
-def _checked_attributes(mesh, V, name):
-    for k in _ATTRIBUTES[1:]:
-        a = mesh.get(k)
-        if a is not None and (len(a.shape) < 1 or a.shape[0] != V):
-            raise ValueError(f"{name}: {k} must have one row per vertex ({V})")
 
 
 @torch.no_grad()
@@ -62,14 +58,14 @@ def _split_fans(f, V, F, mask, labels, cut_inconsistent):
         raise ValueError("split_nonmanifold: n_verts + 3 * n_faces must stay below 2^31")
     t, _ = _edge_table(f, V, F, mask)
     lab = labels.to(dev).to(torch.int32).contiguous() if labels is not None else None
-    ws = torch.empty(lib.nsa_mesh_split_fans_workspace(V, F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_split_fans_workspace(V, F), dev)
     tot = torch.empty(8, dtype=torch.int64, device=dev)
-    check(lib.nsa_mesh_split_fans(f.data_ptr(), F, V, lab.data_ptr() if lab is not None else None,
+    check(lib.nsa_mesh_split_fans(f.data_ptr(), F, V, ptr(lab),
                                   SPLIT_CUT_INCONSISTENT if cut_inconsistent else 0, t["edges"].data_ptr(), t["edge_count"].data_ptr(),
                                   t["edge_forward"].data_ptr(), t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(),
                                   t["face_edges"].data_ptr(), t["_totals"].data_ptr(), ws.data_ptr(), out["corner_fan"].data_ptr(),
                                   out["vertex_fans"].data_ptr() if V else None, out["faces"].data_ptr(), out["new_source"].data_ptr(),
-                                  tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                                  tot.data_ptr(), stream(dev)))
     host = [int(x) for x in tot.cpu()]
     if host[7] != 0:
         raise RuntimeError(f"split_nonmanifold: the union-find left its loop on a step cap (status {host[7]}); this is a bug")
@@ -81,8 +77,7 @@ def _split_fans(f, V, F, mask, labels, cut_inconsistent):
 def split_fans(faces, n_verts, face_mask=None, cut_inconsistent=False, labels=None):
     """Header Section 26 as it stands, on ``faces`` [F, 3] over ``n_verts`` vertices: a dict of ``corner_fan`` [3 F], ``vertex_fans``
     [V], ``faces`` [F, 3], ``new_source`` [n_new] (int32; arrays for numpy faces) and the totals as ints."""
-    from .mesh_topology import _checked
-    f, V, F, mask, restore = _checked(faces, n_verts, face_mask, "split_fans")
+    f, V, F, mask, restore = cuda_faces(faces, n_verts, face_mask, "split_fans")
     lab = _checked_labels(labels, F, f.device, "split_fans")
     out, totals = _split_fans(f, V, F, mask, lab, bool(cut_inconsistent))
     r = {k: restore(x) for k, x in out.items()}
@@ -132,7 +127,7 @@ def split_nonmanifold(mesh, cut_inconsistent=False, labels=None, return_report=F
     ``return_map=True`` adds ``vertex_source`` [V'] (the input vertex each output vertex copies) to the mesh."""
     name = "split_nonmanifold"
     if "verts" in mesh and "faces" in mesh and len(mesh["verts"].shape) == 2 and len(mesh["faces"].shape) == 2:
-        _checked_attributes(mesh, mesh["verts"].shape[0], name)                   # (before the move to the device: no GPU needed to refuse)
+        checked_rows(mesh, mesh["verts"].shape[0], name)                   # (before the move to the device: no GPU needed to refuse)
         _checked_labels(labels, mesh["faces"].shape[0], None, name)
     f, V, F, _, _, _ = _mesh_arrays(mesh, False, device, name)
     lab = _checked_labels(labels, F, f.device, name)
@@ -163,16 +158,14 @@ def weld(mesh, return_report=False, return_map=False):
     ``normals`` and ``colors``.  A face with an index outside [0, V), or with a repeated index after the merge, is dropped and
     counted.  torch only, wherever the mesh lives; numpy in, numpy out.  ``return_report=True`` appends a dict of ints (``n_verts_in``,
     ``n_verts_out``, ``n_faces_in``, ``n_faces_out``, ``n_dropped``); ``return_map=True`` adds ``vertex_source`` [V']."""
-    from .mesh_eval import welded_faces
     if "verts" not in mesh or "faces" not in mesh:
         raise ValueError("weld: mesh needs 'verts' and 'faces'")
     was_numpy = not torch.is_tensor(mesh["faces"])
-    as_t = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    v, f = as_t(mesh["verts"]), as_t(mesh["faces"])
+    v, f = as_tensor(mesh["verts"]), as_tensor(mesh["faces"])
     if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
         raise ValueError("weld: verts must be [V, 3] and faces [F, 3]")
     V, F, dev = v.shape[0], f.shape[0], v.device
-    _checked_attributes(mesh, V, "weld")
+    checked_rows(mesh, V, "weld")
     f = f.to(dev).long()
     idx = torch.arange(V, device=dev)
     name = welded_faces(v.detach().float(), idx.to(torch.int32)[:, None].expand(V, 3).contiguous())[:, 0].long() if V else idx
@@ -210,7 +203,6 @@ def format_report(r):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_repair", description=__doc__.splitlines()[0])
     ap.add_argument("mesh")
     ap.add_argument("--out", metavar="OUT.ply", help="the PLY file to write (not needed with --list)")
@@ -221,7 +213,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.out is None and not a.list:
         ap.error("--out is required unless --list is given")
-    _need_gpu("mesh_repair")
+    need_gpu("mesh_repair")
     try:
         mesh = read_ply(a.mesh)
         report = {}
@@ -233,10 +225,7 @@ def main(argv=None):
         if a.list:
             del report["n_verts_out"]
         else:
-            ply = {k: torch.from_numpy(np.ascontiguousarray(out[k])) for k in ("verts", "faces", "normals", "colors") if k in out}
-            if "normals" not in ply:                      # (write_ply stores normals; a file without them gets zeros)
-                ply["normals"] = torch.zeros_like(ply["verts"])
-            write_ply(a.out, ply)
+            write_mesh_ply(a.out, out)
     except (ValueError, OSError) as e:
         print(f"mesh_repair: {e}", file=sys.stderr)
         raise SystemExit(2)

@@ -29,13 +29,16 @@ import math
 import numpy as np
 import torch
 
-from .mesh_eval import TriIndex, _mesh_tensors, sample_surface
+from .mesh_args import cuda_verts_faces, need_gpu
+from .mesh_eval import TriIndex, sample_surface
+from .mesh_topology import orient as orient_mesh
+from .ply import read_ply
 
 
 def _index(mesh, points=None):
     if isinstance(mesh, TriIndex):
         return mesh
-    return TriIndex(*_mesh_tensors(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
+    return TriIndex(*cuda_verts_faces(mesh, points.device if torch.is_tensor(points) and points.is_cuda else None))
 
 
 def _on_device(points, index):
@@ -53,7 +56,6 @@ def _oriented(mesh, orient, weld=True, points=None):
     index = _index(mesh, points)
     if not orient:
         return index
-    from .mesh_topology import orient as orient_mesh
     return TriIndex(index.verts, orient_mesh({"verts": index.verts, "faces": index.faces}, outward="volume", weld=weld)["faces"])
 
 
@@ -225,7 +227,7 @@ def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0,
     if callable(sdf) and not isinstance(sdf, torch.nn.Module):
         f = sdf(pts)
     else:
-        from . import inference
+        from . import inference            # (no cycle: it keeps the render stack out of a mesh tool's import)
         f = inference.sdf_values(sdf, pts)
     if not (torch.is_tensor(f) and f.numel() == pts.shape[0]):
         raise ValueError("sdf_field_metrics: the field must return one value per point")
@@ -233,7 +235,6 @@ def sdf_field_metrics(sdf, mesh, n_points=200000, sigma=0.01, band=0.05, seed=0,
 
 
 def main(argv=None):
-    from .inference import read_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_sdf", description=__doc__.splitlines()[0])
     ap.add_argument("mesh")
     ap.add_argument("--resolution", type=int, help="write the [R, R, R] narrow-band SDF grid to --out")
@@ -262,8 +263,7 @@ def main(argv=None):
     if not a.beta >= 1.0:
         ap.error("--beta must be >= 1")
     beta = math.inf if a.exact else a.beta
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_sdf: needs a GPU")
+    need_gpu("mesh_sdf")
     index = _oriented(read_ply(a.mesh), a.orient)
     rule = resolve_sign(index, a.sign)
     result = {}

@@ -22,49 +22,13 @@ import numpy as np
 import torch
 
 from ._native import lib, check
+from .mesh_args import checked_mesh, need_gpu, ptr, stream, workspace
+from .mesh_repair import split_nonmanifold
+from .ply import read_ply, write_mesh_ply
 
 TOTALS = ("n_clusters", "n_contributing", "n_used", "n_outside", "n_collapsed", "n_duplicate", "n_verts", "n_faces")
 PLACEMENTS = ("mean", "quadric")
 GRID = 1 << 21
-_MAX_FACES = (2 ** 31 - 1) // 3
-
-
-def _need_gpu(name):
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{name}: needs a GPU")
-
-
-def _as_tensor(x):
-    return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-
-
-def _checked(verts, faces, name, extra=()):
-    """(verts fp32 CUDA [V, 3], faces int32 CUDA [F, 3], extras fp32 CUDA or None, restore): shapes and types first, wherever the
-    arguments live, then the move to the GPU"""
-    was_numpy = not torch.is_tensor(verts)
-    v, f = _as_tensor(verts), _as_tensor(faces)
-    if v.dim() != 2 or v.shape[1] != 3 or not v.dtype.is_floating_point:
-        raise ValueError(f"{name}: verts must be floating point [V, 3]")
-    if f.dim() != 2 or f.shape[1] != 3 or f.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: faces must be int32 or int64 [F, 3]")
-    if v.shape[0] >= 1 << 31 or f.shape[0] > _MAX_FACES:
-        raise ValueError(f"{name}: count out of range (n_verts < 2^31, 3 * n_faces < 2^31)")
-    if f.dtype == torch.int64 and f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) >= 2 ** 31):
-        raise ValueError(f"{name}: face index outside int32")
-    extras = []
-    for key, x in extra:
-        if x is not None:
-            x = _as_tensor(x)
-            if x.shape != v.shape or not x.dtype.is_floating_point:
-                raise ValueError(f"{name}: {key} must be floating point [V, 3]")
-        extras.append(x)
-    orig = None if was_numpy else v.device
-    if not (torch.is_tensor(verts) and verts.is_cuda):
-        _need_gpu(name)
-    dev = v.device if v.is_cuda else torch.device("cuda")
-    on = lambda x: x.detach().to(dev).float().contiguous()
-    restore = lambda t: t.cpu().numpy() if was_numpy else t.to(orig)
-    return on(v), f.detach().to(dev).to(torch.int32).contiguous(), [None if x is None else on(x) for x in extras], restore
 
 
 def _extent(v):
@@ -104,12 +68,12 @@ def _cluster(v, f, origin, h, n_cells=GRID):
         t["vertex_cluster"].fill_(-1)
         t["cluster_vertex"].fill_(-1)
         return t, totals
-    ws = torch.empty(lib.nsa_mesh_cluster_workspace(V, F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_cluster_workspace(V, F), dev)
     tot = torch.empty(9, dtype=torch.int64, device=dev)
     org = (ctypes.c_double * 3)(*origin)
     check(lib.nsa_mesh_cluster(v.data_ptr(), V, f.data_ptr(), F, org, h, int(n_cells), ws.data_ptr(), t["vertex_cluster"].data_ptr(),
                                t["cluster_vertex"].data_ptr(), t["out_cluster"].data_ptr(), t["faces"].data_ptr(),
-                               t["face_origin"].data_ptr(), tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                               t["face_origin"].data_ptr(), tot.data_ptr(), stream(dev)))
     host = [int(x) for x in tot.cpu()]
     if host[8] != 0:
         raise RuntimeError(f"mesh_simplify: a sort order left its range (status {host[8]}); this is a bug")
@@ -126,13 +90,12 @@ def _place(v, f, normals, colors, origin, h, eps, placement, t, n_out):
         out["colors"] = torch.empty(n_out, 3, device=dev)
     if n_out == 0:
         return out
-    ws = torch.empty(lib.nsa_mesh_cluster_place_workspace(V, F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_cluster_place_workspace(V, F), dev)
     org = (ctypes.c_double * 3)(*origin)
-    ptr = lambda x: None if x is None else x.data_ptr()
     check(lib.nsa_mesh_cluster_place(v.data_ptr(), V, f.data_ptr(), F, ptr(normals), ptr(colors), org, h, float(eps),
                                      PLACEMENTS.index(placement), t["vertex_cluster"].data_ptr(), t["cluster_vertex"].data_ptr(), n_out,
                                      ws.data_ptr(), out["verts"].data_ptr(), ptr(out.get("normals")), ptr(out.get("colors")),
-                                     out["vertex_cell"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                                     out["vertex_cell"].data_ptr(), stream(dev)))
     return out
 
 
@@ -146,7 +109,7 @@ def cluster(faces, verts, cell, origin=None):
     h = _checked_cell(cell, "cluster")
     if origin is not None:
         origin = _checked_origin(origin, "cluster")
-    v, f, _, restore = _checked(verts, faces, "cluster")
+    v, f, _, _, _, restore = checked_mesh({"verts": verts, "faces": faces}, "cluster", float_verts=True)
     o = _extent(v)[0] if origin is None else origin
     t, totals = _cluster(v, f, o, h)
     out = dict(vertex_cluster=restore(t["vertex_cluster"]), faces=restore(t["faces"][:totals["n_faces"]]),
@@ -199,8 +162,6 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
 
     Synchronises for the extent of the vertices and once for the totals (``target_faces``: once per probe as well)."""
     name = "simplify"
-    if "verts" not in mesh or "faces" not in mesh:
-        raise ValueError("simplify: mesh needs 'verts' and 'faces'")
     if (cell is None) == (target_faces is None):
         raise ValueError("simplify: give exactly one of cell and target_faces")
     if placement not in PLACEMENTS:
@@ -216,8 +177,8 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
         raise ValueError("simplify: target_faces must be a non-negative integer")
     if origin is not None:
         origin = _checked_origin(origin, name)
-    v, f, (normals, colors), restore = _checked(mesh["verts"], mesh["faces"], name,
-                                                 (("normals", mesh.get("normals")), ("colors", mesh.get("colors"))))
+    v, f, _, _, extra, restore = checked_mesh(mesh, name, float_verts=True, attributes=("normals", "colors"), float_attributes=True)
+    normals, colors = extra.get("normals"), extra.get("colors")
     lo3, hi3 = _extent(v)
     o = lo3 if origin is None else origin
     if cell is None:
@@ -235,7 +196,6 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
         out.update(vertex_cluster=restore(t["vertex_cluster"]), face_origin=restore(t["face_origin"][:totals["n_faces"]]),
                    vertex_cell=restore(p["vertex_cell"]), totals=totals, cell=h)
     if split:
-        from .mesh_repair import split_nonmanifold
         out = split_nonmanifold(out, **dict(split if isinstance(split, dict) else {}, return_report=False, return_map=return_map))
         if return_map:
             src = out["vertex_source"]
@@ -244,7 +204,6 @@ def simplify(mesh, cell=None, target_faces=None, placement="quadric", origin=Non
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_simplify", description=__doc__.splitlines()[0])
     ap.add_argument("mesh")
     ap.add_argument("--out", required=True, help="the PLY file to write")
@@ -254,16 +213,13 @@ def main(argv=None):
     ap.add_argument("--placement", choices=PLACEMENTS, default="quadric")
     ap.add_argument("--json", action="store_true", help="print the totals as one JSON object")
     a = ap.parse_args(argv)
-    _need_gpu("mesh_simplify")
+    need_gpu("mesh_simplify")
     try:
         r = simplify(read_ply(a.mesh), cell=a.cell, target_faces=a.faces, placement=a.placement, return_map=True)
     except (ValueError, OSError) as e:
         print(f"mesh_simplify: {e}", file=sys.stderr)
         raise SystemExit(2)
-    mesh = {k: torch.from_numpy(np.ascontiguousarray(r[k])) for k in ("verts", "faces", "normals", "colors") if k in r}
-    if "normals" not in mesh:                             # (write_ply stores normals; a file without them gets zeros)
-        mesh["normals"] = torch.zeros_like(mesh["verts"])
-    write_ply(a.out, mesh)
+    write_mesh_ply(a.out, r)
     report = dict(r["totals"], cell=r["cell"])
     if a.json:
         print(json.dumps(report))

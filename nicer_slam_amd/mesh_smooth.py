@@ -22,23 +22,19 @@ import json
 import math
 import sys
 
-import numpy as np
 import torch
 
 from . import _native
 from ._native import lib, check
-from .mesh_topology import _checked, _edge_table, _need_gpu, _to_cuda
+from .mesh_args import MAX_FACES_RINGS, checked_mesh, cuda_faces, need_gpu, ptr, stream, workspace
+from .mesh_topology import _edge_table
+from .ply import read_ply, write_mesh_ply
 
 METHODS = ("taubin", "laplacian")
 BOUNDARY = {"free": _native.SMOOTH_FREE, "fixed": _native.SMOOTH_FIXED, "curve": _native.SMOOTH_CURVE}
 WEIGHTING = {"area": _native.NORMALS_AREA, "angle": _native.NORMALS_ANGLE}
 NORMALS = ("angle", "area", "keep", None)
 STATE_LIVE, STATE_ON_BOUNDARY, STATE_MOVES, STATE_STEPS = 1, 2, 4, 8
-_MAX_FACES = (2 ** 31 - 1) // 6
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 @torch.no_grad()
@@ -48,16 +44,10 @@ def _ring(t, V, F, dev):
     ring = torch.empty(6 * F, dtype=torch.int32, device=dev)
     ring_edge = torch.empty(6 * F, dtype=torch.int32, device=dev)
     if F:
-        ws = torch.empty(lib.nsa_mesh_ring_workspace(V, F), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.nsa_mesh_ring_workspace(V, F), dev)
         check(lib.nsa_mesh_ring(t["edges"].data_ptr(), t["_totals"].data_ptr(), V, F, ws.data_ptr(), ring_start.data_ptr(),
-                                ring.data_ptr(), ring_edge.data_ptr(), _stream(dev)))
+                                ring.data_ptr(), ring_edge.data_ptr(), stream(dev)))
     return ring_start, ring, ring_edge
-
-
-def _checked_faces(faces, n_verts, name, device="cuda"):
-    if len(getattr(faces, "shape", ())) == 2 and faces.shape[0] > _MAX_FACES:
-        raise ValueError(f"{name}: count out of range (6 * n_faces < 2^31)")
-    return _checked(faces, n_verts, None, name, device)
 
 
 def vertex_ring(faces, n_verts):
@@ -65,7 +55,7 @@ def vertex_ring(faces, n_verts):
     for numpy faces): ``ring_start`` [V + 1], ``ring`` [2 E] the neighbours of vertex v at ``ring_start[v]:ring_start[v + 1]`` in
     ascending index, ``ring_edge`` [2 E] the edge id of each entry in ``mesh_topology.edge_table``'s numbering, all int32 -- plus that
     table's totals as ints (``n_edges``, ``n_boundary``, ...).  Reads the totals back once (a synchronisation)."""
-    f, V, F, _, restore = _checked_faces(faces, n_verts, "vertex_ring")
+    f, V, F, _, restore = cuda_faces(faces, n_verts, None, "vertex_ring", max_faces=MAX_FACES_RINGS)
     t, totals = _edge_table(f, V, F, None)
     ring_start, ring, ring_edge = _ring(t, V, F, f.device)
     n = 2 * totals["n_edges"]
@@ -84,13 +74,13 @@ def _smooth(v, V, F, t, rings, factors, boundary, fixed, max_move):
         return out, state
     n = len(factors)
     fac = (ctypes.c_double * max(n, 1))(*factors)
-    ws = torch.empty(lib.nsa_mesh_smooth_workspace(V, F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_smooth_workspace(V, F), dev)
     ring_start, ring, ring_edge = rings
-    ptr = lambda x: x.data_ptr() if F else None
-    check(lib.nsa_mesh_smooth(v.data_ptr(), V, F, ptr(ring_start), ptr(ring), ptr(ring_edge), ptr(t["edge_count"]),
-                              fixed.data_ptr() if fixed is not None else None, fac, n, BOUNDARY[boundary],
+    no_faces = lambda x: x.data_ptr() if F else None        # (NULL without faces, though ring_start is never empty)
+    check(lib.nsa_mesh_smooth(v.data_ptr(), V, F, no_faces(ring_start), ptr(ring), ptr(ring_edge), ptr(t["edge_count"]),
+                              ptr(fixed), fac, n, BOUNDARY[boundary],
                               math.inf if max_move is None else float(max_move), ws.data_ptr(), out.data_ptr(), state.data_ptr(),
-                              _stream(dev)))
+                              stream(dev)))
     return out, state
 
 
@@ -99,28 +89,10 @@ def _vertex_normals(v, f, V, F, weighting):
     out = torch.empty(V, 3, dtype=torch.float32, device=v.device)
     if V == 0:
         return out
-    ws = torch.empty(lib.nsa_mesh_vertex_normals_workspace(V, F), dtype=torch.uint8, device=v.device) if F else None
-    check(lib.nsa_mesh_vertex_normals(v.data_ptr(), V, f.data_ptr() if F else None, F, WEIGHTING[weighting],
-                                      ws.data_ptr() if F else None, out.data_ptr(), _stream(v.device)))
+    ws = workspace(lib.nsa_mesh_vertex_normals_workspace(V, F), v.device) if F else None
+    check(lib.nsa_mesh_vertex_normals(v.data_ptr(), V, ptr(f), F, WEIGHTING[weighting], ws.data_ptr() if F else None, out.data_ptr(),
+                                      stream(v.device)))
     return out
-
-
-def _mesh(mesh, name, device):
-    """(verts fp32 CUDA [V, 3], faces int32 CUDA [F, 3], V, F, give): the checked arrays of a mesh dict -- shapes first, on whatever
-    device they live, then the move to the GPU -- and the function that gives a result tensor the kind of the mesh's verts back"""
-    if not isinstance(mesh, dict) or "verts" not in mesh or "faces" not in mesh:
-        raise ValueError(f"{name}: mesh needs 'verts' and 'faces'")
-    verts = mesh["verts"]
-    if len(verts.shape) != 2 or verts.shape[1] != 3:
-        raise ValueError(f"{name}: verts must be [V, 3]")
-    if torch.is_tensor(verts) and not verts.dtype.is_floating_point or not torch.is_tensor(verts) and verts.dtype.kind != "f":
-        raise ValueError(f"{name}: verts must be floating point")
-    if torch.is_tensor(verts) and verts.is_cuda:
-        device = verts.device
-    f, V, F, _, _ = _checked_faces(mesh["faces"], verts.shape[0], name, device)
-    v, was_numpy, orig = _to_cuda(verts, name, f.device)
-    v = v.detach().float().contiguous()
-    return v, f, V, F, (lambda x: x.cpu().numpy() if was_numpy else x.to(orig))
 
 
 def factors_of(method="taubin", iterations=10, lam=0.5, mu=-0.53):
@@ -170,7 +142,7 @@ def smooth(mesh, method="taubin", iterations=10, lam=0.5, mu=-0.53, boundary="cu
         mask = torch.as_tensor(fixed).reshape(-1)
         if mask.shape[0] != mesh["verts"].shape[0]:
             raise ValueError(f"smooth: fixed mask of {mask.shape[0]} for {mesh['verts'].shape[0]} vertices")
-    v, f, V, F, give = _mesh(mesh, "smooth", device)
+    v, f, V, F, _, give = checked_mesh(mesh, "smooth", device, float_verts=True, max_faces=MAX_FACES_RINGS)
     if mask is not None:
         mask = (mask.to(v.device) != 0).to(torch.uint8).contiguous()
     t, _ = _edge_table(f, V, F, None)
@@ -199,7 +171,7 @@ def vertex_normals(mesh, weighting="angle", device="cuda"):
     vector for a vertex on no face with finite vertices.  Same kind (numpy or torch, device) as the mesh's verts."""
     if weighting not in WEIGHTING:
         raise ValueError(f"vertex_normals: weighting must be one of {tuple(WEIGHTING)}, got {weighting!r}")
-    v, f, V, F, give = _mesh(mesh, "vertex_normals", device)
+    v, f, V, F, _, give = checked_mesh(mesh, "vertex_normals", device, float_verts=True, max_faces=MAX_FACES_RINGS)
     return give(_vertex_normals(v, f, V, F, weighting))
 
 
@@ -209,7 +181,6 @@ def format_report(r):
 
 
 def main(argv=None):
-    from .inference import read_ply, write_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_smooth", description=__doc__.splitlines()[0])
     ap.add_argument("mesh", metavar="IN.ply")
     ap.add_argument("--out", required=True, metavar="OUT.ply")
@@ -222,15 +193,12 @@ def main(argv=None):
     ap.add_argument("--normals", choices=("angle", "area", "keep", "none"), default="angle")
     ap.add_argument("--json", action="store_true", help="print the report as one JSON object")
     a = ap.parse_args(argv)
-    _need_gpu("mesh_smooth")
+    need_gpu("mesh_smooth")
     try:
         mesh = read_ply(a.mesh)
         out, r = smooth(mesh, a.method, a.iterations, a.lam, a.mu, a.boundary, None, a.max_move,
                         None if a.normals == "none" else a.normals, return_report=True)
-        ply = {k: torch.from_numpy(np.ascontiguousarray(out[k])) for k in ("verts", "faces", "normals", "colors") if k in out}
-        if "normals" not in ply:                          # (write_ply stores normals; a file without them gets zeros)
-            ply["normals"] = torch.zeros_like(ply["verts"])
-        write_ply(a.out, ply)
+        write_mesh_ply(a.out, out)
     except (ValueError, OSError) as e:
         print(f"mesh_smooth: {e}", file=sys.stderr)
         raise SystemExit(2)

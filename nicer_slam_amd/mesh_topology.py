@@ -25,55 +25,17 @@ import sys
 import numpy as np
 import torch
 
+from . import mesh_raycast as R
 from ._native import lib, check
+from .mesh_args import MAX_FACES_EDGES, checked_mesh, cuda_faces, kind, need_gpu, restore_dict, restorer, stream, workspace
+from .mesh_eval import TriIndex, welded_faces
+from .mesh_intersect import self_intersections
+from .ply import read_ply, write_mesh_ply
 
 REPORT_KEYS = ("n_faces", "n_contributing", "n_used_verts", "n_edges", "n_boundary", "n_nonmanifold", "n_inconsistent",
                "n_boundary_loops", "n_components", "euler", "is_watertight", "is_oriented")
 _TOTALS = ("n_edges", "n_contributing", "n_used_verts", "n_boundary", "n_nonmanifold", "n_inconsistent", "n_boundary_loops")
-_MAX_FACES = (2 ** 31 - 1) // 3
-
-
-def _need_gpu(name):
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{name}: needs a GPU")
-
-
-def _to_cuda(x, name, device="cuda"):
-    """(CUDA tensor, was_numpy, original device) of an array or tensor"""
-    if torch.is_tensor(x):
-        if x.is_cuda:
-            return x, False, x.device
-        _need_gpu(name)
-        return x.to(device), False, x.device
-    _need_gpu(name)
-    return torch.from_numpy(np.ascontiguousarray(x)).to(device), True, None
-
-
-def _checked(faces, n_verts, face_mask, name, device="cuda"):
-    """(faces int32 CUDA [F, 3], V, F, mask uint8 CUDA or None, restore): the checked arguments -- shapes and ranges first, on
-    whatever device they live, then the move to the GPU -- and the function that gives a result tensor the caller's kind back"""
-    was_numpy = not torch.is_tensor(faces)
-    f = torch.from_numpy(np.ascontiguousarray(faces)) if was_numpy else faces
-    if f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError(f"{name}: faces must be [F, 3]")
-    if f.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: faces must be int32 or int64")
-    V, F = int(n_verts), f.shape[0]
-    if V < 0 or V >= 1 << 31 or F > _MAX_FACES:
-        raise ValueError(f"{name}: count out of range (0 <= n_verts < 2^31, 3 * n_faces < 2^31)")
-    if f.dtype == torch.int64 and f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) >= 2 ** 31):
-        raise ValueError(f"{name}: face index outside int32")
-    mask = None
-    if face_mask is not None:
-        mask = torch.as_tensor(face_mask).reshape(-1)
-        if mask.shape[0] != F:
-            raise ValueError(f"{name}: mask of {mask.shape[0]} for {F} faces")
-    orig = None if was_numpy else f.device
-    f, _, _ = _to_cuda(f, name, device)
-    f = f.to(torch.int32).contiguous()
-    if mask is not None:
-        mask = (mask.to(f.device) != 0).to(torch.uint8).contiguous()
-    return f, V, F, mask, lambda t: t.cpu().numpy() if was_numpy else t.to(orig)
+_checked = cuda_faces            # (faces, n_verts, face_mask, name) -> what _edge_table takes: the name the kernels' device tests use
 
 
 @torch.no_grad()
@@ -87,12 +49,12 @@ def _edge_table(f, V, F, mask):
     if F == 0:
         t["edge_start"].zero_()
         return t, totals
-    ws = torch.empty(lib.nsa_mesh_edges_workspace(V, F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_edges_workspace(V, F), dev)
     tot = torch.empty(8, dtype=torch.int64, device=dev)
     check(lib.nsa_mesh_edges(f.data_ptr(), F, V, mask.data_ptr() if mask is not None else None, ws.data_ptr(),
                              t["edges"].data_ptr(), t["edge_count"].data_ptr(), t["edge_forward"].data_ptr(),
                              t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(), t["face_edges"].data_ptr(),
-                             tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                             tot.data_ptr(), stream(dev)))
     host = [int(x) for x in tot.cpu()]
     if host[7] != 0:
         raise RuntimeError(f"edge_table: the boundary union-find left its loop on a step cap (status {host[7]}); this is a bug")
@@ -106,10 +68,10 @@ def _face_components(t, F, dev):
     label = torch.empty(F, dtype=torch.int32, device=dev)
     if F == 0:
         return label, 0
-    ws = torch.empty(lib.nsa_mesh_face_components_workspace(F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_face_components_workspace(F), dev)
     tot = torch.empty(2, dtype=torch.int64, device=dev)
     check(lib.nsa_mesh_face_components(t["face_edges"].data_ptr(), t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(), F,
-                                       ws.data_ptr(), label.data_ptr(), tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                                       ws.data_ptr(), label.data_ptr(), tot.data_ptr(), stream(dev)))
     C, status = (int(x) for x in tot.cpu())
     if status != 0:
         raise RuntimeError(f"face_components: the labelling kernel left its loop on a step cap (status {status}); this is a bug")
@@ -131,7 +93,7 @@ def edge_table(faces, n_verts, face_mask=None):
     ints: ``n_edges``, ``n_contributing``, ``n_used_verts``, ``n_boundary``, ``n_nonmanifold``, ``n_inconsistent``,
     ``n_boundary_loops``.  A face contributes when its indices lie in [0, n_verts), are pairwise distinct and ``face_mask`` [F]
     (None: all) is non-zero for it.  Reads the totals back once (a synchronisation)."""
-    f, V, F, mask, restore = _checked(faces, n_verts, face_mask, "edge_table")
+    f, V, F, mask, restore = cuda_faces(faces, n_verts, face_mask, "edge_table")
     return {k: restore(x) if torch.is_tensor(x) else x for k, x in _slice(*_edge_table(f, V, F, mask)).items()}
 
 
@@ -139,7 +101,7 @@ def face_components(faces, n_verts, face_mask=None):
     """(face_label [F] int32, n_components): the components of the contributing faces joined across shared edges (any edge with two or
     more faces; the closure is transitive).  The label is the smallest face index of the component, -1 for a face that does not
     contribute.  trimesh's ``split`` cuts at a non-manifold edge; this joins across it."""
-    f, V, F, mask, restore = _checked(faces, n_verts, face_mask, "face_components")
+    f, V, F, mask, restore = cuda_faces(faces, n_verts, face_mask, "face_components")
     t, _ = _edge_table(f, V, F, mask)
     label, C = _face_components(t, F, f.device)
     return restore(label), C
@@ -147,7 +109,7 @@ def face_components(faces, n_verts, face_mask=None):
 
 def face_adjacency(faces, n_verts):
     """[P, 2] int32: the face pairs (f0 < f1) of the edges with exactly two faces, in edge order -- trimesh's ``face_adjacency``"""
-    f, V, F, _, restore = _checked(faces, n_verts, None, "face_adjacency")
+    f, V, F, _, restore = cuda_faces(faces, n_verts, None, "face_adjacency")
     t = _slice(*_edge_table(f, V, F, None))
     s = t["edge_start"][:-1][t["edge_count"] == 2].long()
     he = t["edge_halfedges"]
@@ -157,7 +119,7 @@ def face_adjacency(faces, n_verts):
 
 def boundary_edges(faces, n_verts):
     """[B, 2] int32: the (lo, hi) of the edges with one face, in edge order"""
-    f, V, F, _, restore = _checked(faces, n_verts, None, "boundary_edges")
+    f, V, F, _, restore = cuda_faces(faces, n_verts, None, "boundary_edges")
     t = _slice(*_edge_table(f, V, F, None))
     return restore(t["edges"][t["edge_count"] == 1])
 
@@ -175,15 +137,7 @@ def _report(F, totals, C):
 def _mesh_arrays(mesh, weld, device, name):
     """(faces of the topology int32 CUDA [F, 3], V, F, mask or None, verts CUDA, the mesh's own faces int32 CUDA) of a mesh dict:
     with ``weld`` the first are ``mesh_eval.welded_faces`` and the mask leaves out the faces that have a non-finite vertex"""
-    from .mesh_eval import welded_faces
-    if "verts" not in mesh or "faces" not in mesh:
-        raise ValueError(f"{name}: mesh needs 'verts' and 'faces'")
-    if len(mesh["verts"].shape) != 2 or mesh["verts"].shape[1] != 3:
-        raise ValueError(f"{name}: verts must be [V, 3]")
-    if torch.is_tensor(mesh["verts"]) and mesh["verts"].is_cuda:
-        device = mesh["verts"].device
-    f, V, F, _, _ = _checked(mesh["faces"], mesh["verts"].shape[0], None, name, device)
-    v, _, _ = _to_cuda(mesh["verts"], name, f.device)
+    v, f, V, F, _, _ = checked_mesh(mesh, name, device, max_faces=MAX_FACES_EDGES)
     mask, f0 = None, f
     if weld and F:
         v = v.detach().float()
@@ -211,7 +165,6 @@ def topology(mesh, weld=False, device="cuda", intersections=False):
     _, C = _face_components(t, F, f.device)
     r = _report(F, totals, C)
     if intersections:
-        from .mesh_intersect import self_intersections
         r["n_proper_pairs"] = int(self_intersections(mesh, kinds=("proper",), device=device)[0].shape[0])
         r["embedded"] = r["n_proper_pairs"] == 0
     return r
@@ -253,11 +206,11 @@ def _orientation(f, t, F):
     flip = torch.empty(F, dtype=torch.uint8, device=dev)
     if F == 0:
         return label, orientable, flip, dict.fromkeys(_ORIENT_TOTALS, 0)
-    ws = torch.empty(lib.nsa_mesh_orient_workspace(F), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.nsa_mesh_orient_workspace(F), dev)
     tot = torch.empty(4, dtype=torch.int64, device=dev)
     check(lib.nsa_mesh_orient(f.data_ptr(), F, t["face_edges"].data_ptr(), t["edge_start"].data_ptr(), t["edge_halfedges"].data_ptr(),
                               t["_totals"].data_ptr(), ws.data_ptr(), label.data_ptr(), orientable.data_ptr(), flip.data_ptr(),
-                              tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                              tot.data_ptr(), stream(dev)))
     host = [int(x) for x in tot.cpu()]
     if host[3] != 0:
         raise RuntimeError(f"orientation: the union-find left its loop on a step cap (status {host[3]}); this is a bug")
@@ -288,12 +241,12 @@ def _orient_volume(v, f, V, F, t, label, orientable, flip):
     out = torch.empty(F, dtype=torch.uint8, device=dev)
     totals = dict(n_closed=0, n_decided=0, n_toggled=0, n_flipped=0)
     if F:
-        ws = torch.empty(lib.nsa_mesh_orient_volume_workspace(F), dtype=torch.uint8, device=dev)
+        ws = workspace(lib.nsa_mesh_orient_volume_workspace(F), dev)
         tot = torch.empty(5, dtype=torch.int64, device=dev)
         check(lib.nsa_mesh_orient_volume(v.data_ptr() if V else None, V, f.data_ptr(), F, t["face_edges"].data_ptr(),
                                          t["edge_start"].data_ptr(), label.data_ptr(), orientable.data_ptr(), flip.data_ptr(),
                                          origin.data_ptr(), ws.data_ptr(), S.data_ptr(), P.data_ptr(), n.data_ptr(), flags.data_ptr(),
-                                         out.data_ptr(), tot.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+                                         out.data_ptr(), tot.data_ptr(), stream(dev)))
         host = [int(x) for x in tot.cpu()]
         if host[4] != 0:
             raise RuntimeError(f"orient: the sort by label left its range (status {host[4]}); this is a bug")
@@ -338,8 +291,6 @@ def view_votes(verts, faces, flip, hit_face, dirs):
 @torch.no_grad()
 def _view_hits(v, f0, c2w, intrinsics, size):
     """(hit face int64 [m], dirs fp32 [m, 3]) of the pixel rays of every camera, cast with ``TriIndex.raycast`` at the default near"""
-    from . import mesh_raycast as R
-    from .mesh_eval import TriIndex
     P = R._as_numpy(c2w, np.float64)
     P = P[None] if P.ndim == 2 else P
     if P.ndim != 3 or P.shape[1:] != (4, 4) or P.shape[0] == 0:
@@ -399,15 +350,6 @@ def _orient_arrays(mesh, outward, c2w, intrinsics, size, weld, device, name):
     return f0, V, F, label, orientable, flip, out, rep
 
 
-def _report_out(rep, was_numpy, orig):
-    return {k: ((x.cpu().numpy() if was_numpy else x.to(orig)) if torch.is_tensor(x) else x) for k, x in rep.items()}
-
-
-def _kind(mesh):
-    was_numpy = not torch.is_tensor(mesh["faces"])
-    return was_numpy, None if was_numpy else mesh["faces"].device
-
-
 def orientation(mesh, weld=False, device="cuda"):
     """(orient_label [F] int32, orientable [F] bool, flip [F] bool, report) of ``mesh`` (a dict with ``verts`` and ``faces``, numpy or
     torch; header Section 20).  Faces are joined across the edges that carry exactly two half-edges (trimesh's ``face_adjacency``);
@@ -417,10 +359,10 @@ def orientation(mesh, weld=False, device="cuda"):
     and per component, in ascending label, ``component_label``, ``component_faces`` and ``component_closed`` (every half-edge on
     an edge of count 2).  ``weld`` as in ``topology``."""
     _, _, _, label, orientable, flip, _, rep = _orient_arrays(mesh, None, None, None, None, weld, device, "orientation")
-    was_numpy, orig = _kind(mesh)
-    back = lambda x: x.cpu().numpy() if was_numpy else x.to(orig)
+    was_numpy, orig = kind(mesh["faces"])
+    back = restorer(was_numpy, orig)
     keep = _ORIENT_TOTALS + ("is_orientable", "component_label", "component_faces", "component_closed")
-    return back(label), back(orientable != 0), back(flip != 0), _report_out({k: rep[k] for k in keep}, was_numpy, orig)
+    return back(label), back(orientable != 0), back(flip != 0), restore_dict({k: rep[k] for k in keep}, was_numpy, orig)
 
 
 def orient(mesh, outward="volume", c2w=None, intrinsics=None, size=None, weld=False, return_report=False, device="cuda"):
@@ -440,7 +382,7 @@ def orient(mesh, outward="volume", c2w=None, intrinsics=None, size=None, weld=Fa
     ``n_mixed_normals``, the per-component ``component_decided`` / ``component_toggled`` and, by rule, ``component_volume`` and
     ``component_volume_bound`` (S_c, P_c) or ``component_votes``; ``n_flipped`` counts the faces reversed in the result."""
     f0, V, F, label, _, _, out, rep = _orient_arrays(mesh, outward, c2w, intrinsics, size, weld, device, "orient")
-    was_numpy, orig = _kind(mesh)
+    was_numpy, orig = kind(mesh["faces"])
     faces = mesh["faces"] if torch.is_tensor(mesh["faces"]) else torch.from_numpy(np.ascontiguousarray(mesh["faces"]))
     sw = (out != 0).to(faces.device)
     new_faces = torch.where(sw[:, None], faces[:, [0, 2, 1]], faces) if F else faces.clone()
@@ -462,7 +404,7 @@ def orient(mesh, outward="volume", c2w=None, intrinsics=None, size=None, weld=Fa
         else:
             nrm = np.asarray(nrm)
             result["normals"] = np.where(neg.cpu().numpy()[:, None], -nrm, nrm).astype(nrm.dtype)
-    return (result, _report_out(rep, was_numpy, orig)) if return_report else result
+    return (result, restore_dict(rep, was_numpy, orig)) if return_report else result
 
 
 def format_report(r):
@@ -484,7 +426,6 @@ def format_orient_report(r):
 
 
 def main(argv=None):
-    from .inference import read_ply
     ap = argparse.ArgumentParser(prog="python -m nicer_slam_amd.mesh_topology", description=__doc__.splitlines()[0])
     ap.add_argument("mesh")
     ap.add_argument("--weld", action="store_true", help="name vertices by their coordinates: connect across repeated seam vertices")
@@ -503,25 +444,21 @@ def main(argv=None):
         ap.error("--outward views needs --poses, --intrinsics and --size")
     if a.split and a.weld:
         ap.error("--split and --weld undo each other: the welded names join the vertices that the split made")
-    _need_gpu("mesh_topology")
+    need_gpu("mesh_topology")
     try:
         mesh = read_ply(a.mesh)
         if a.split:
-            from .mesh_repair import split_nonmanifold
+            from .mesh_repair import split_nonmanifold            # (a cycle: mesh_repair is built on this module's edge table)
             mesh = split_nonmanifold(mesh)
         if a.orient is None:
             r = topology(mesh, weld=a.weld, intersections=a.intersections)
         else:
-            from .inference import write_ply
             poses = None
             if a.outward == "views":
                 poses = np.load(a.poses) if a.poses.endswith(".npy") else np.loadtxt(a.poses).reshape(-1, 4, 4)
             out, full = orient(mesh, None if a.outward == "none" else a.outward, poses, a.intrinsics, a.size, weld=a.weld,
                                return_report=True)
-            ply = {k: torch.from_numpy(np.ascontiguousarray(out[k])) for k in ("verts", "faces", "normals", "colors") if k in out}
-            if "normals" not in ply:                      # (write_ply stores normals; a file without them gets zeros)
-                ply["normals"] = torch.zeros_like(ply["verts"])
-            write_ply(a.orient, ply)
+            write_mesh_ply(a.orient, out)
             r = {k: (x if isinstance(x, (bool, str)) or x is None else int(x)) for k, x in full.items() if np.ndim(x) == 0}
     except (ValueError, OSError) as e:
         print(f"mesh_topology: {e}", file=sys.stderr)

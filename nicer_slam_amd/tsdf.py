@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ._native import TsdfVolumeDesc, check, lib
+from .ply import write_ply
 
 MAX_VOXELS = 1 << 31                      # marching cubes' limit (Section 7)
 SCENES7_CAMERA = (585.0, 585.0, 320.0, 240.0)
@@ -302,7 +303,6 @@ def main(argv=None):
     ap.add_argument("--voxel", type=float, default=4.0 / 512)
     ap.add_argument("--trunc", type=float, default=0.04)
     args = ap.parse_args(argv)
-    from .inference import write_ply
     mesh = fuse_7scenes(args.seq_dir, args.frames, args.voxel, args.trunc)
     write_ply(args.out, mesh)
     print(f"{args.out}: {mesh['verts'].shape[0]} vertices, {mesh['faces'].shape[0]} faces")
