@@ -10,7 +10,8 @@ import torch
 
 import bf16_gate as G
 import ref64
-from test_gemm_float64_gpu import KINK, _colour_inputs, _cot, _cube_points, _scaled, _scales, _sdf_families
+from gemm_cases import KINK, colour_inputs, cot, cube_points, scaled, scales
+from gemm_cases import sdf_families as fp32_families
 
 N = 4123                                        # 128 x 32 + 27: ragged for both tilings
 UNIT = "all three x c_p in [1/8, 8]"            # the accumulate = 1 family: every point's c_p = 2^U{-3..3}
@@ -30,11 +31,11 @@ def emulate(call, weights=None, order="natural", fault=None):
 
 
 def sdf_families(n=N):
-    """tests/test_gemm_float64_gpu.py's cotangent families + UNIT -> name -> (g_sdf, g_feat, g_grad, c_p)"""
-    fam = _sdf_families(n)
+    """tests/gemm_cases.py's cotangent families + UNIT -> name -> (g_sdf, g_feat, g_grad, c_p)"""
+    fam = fp32_families(n)
     g = torch.Generator().manual_seed(31)
     c = torch.exp2(torch.randint(-3, 4, (n,), generator=g).double())
-    fam[UNIT] = tuple(_scaled(b, c) for b in (_cot(n, 10, ()), _cot(n, 11, (64,)), _cot(n, 12, (3,)))) + (c,)
+    fam[UNIT] = tuple(scaled(b, c) for b in (cot(n, 10, ()), cot(n, 11, (64,)), cot(n, 12, (3,)))) + (c,)
     return fam
 
 
@@ -66,10 +67,10 @@ def colour_coarse_case(params, cfg, x, d, normals, feat, g_rgb, grid_grad, g_sdf
 def inputs(params, cfg, n=N):
     """every input of the suite (the fp32 suite's builders and seeds at n points): xf / xb the points of the SDF forwards / backwards,
     fam the cotangent families, x, d, normals, feat, c, g_rgb, g_sdf the colour kernels' inputs and cotangents"""
-    x, d, normals, feat = _colour_inputs(types.SimpleNamespace(params=params, cfg=cfg), n, 7)
-    c = _scales(n, 8)
-    return types.SimpleNamespace(xf=_cube_points(n, 1), xb=_cube_points(n, 5), fam=sdf_families(n), x=x, d=d, normals=normals, feat=feat, c=c,
-                                 g_rgb=_scaled(_cot(n, 9, (3,)), c), g_sdf=_scaled(_cot(n, 15, ()), c))
+    x, d, normals, feat = colour_inputs(types.SimpleNamespace(params=params, cfg=cfg), n, 7)
+    c = scales(n, 8)
+    return types.SimpleNamespace(xf=cube_points(n, 1), xb=cube_points(n, 5), fam=sdf_families(n), x=x, d=d, normals=normals, feat=feat, c=c,
+                                 g_rgb=scaled(cot(n, 9, (3,)), c), g_sdf=scaled(cot(n, 15, ()), c))
 
 
 def all_cases(params, cfg, n=N):

@@ -19,19 +19,13 @@ summation order) stay within the kept-point gate for every kernel family, while 
 points and MIN_KEPT points (tests/test_ref64_bf16_cpu.py::test_threshold_is_the_smallest_of_the_ladder_that_holds)."""
 import torch
 
+from gate64 import fwd_norm, per_point        # noqa: F401  (fwd_norm: the suites take the forward norm from here)
+
 LADDER = (1e-4, 3e-4, 1e-3, 3e-3, 1e-2, 3e-2, 0.1, 0.3, 1.0, 3.0, 10.0, 30.0, 100.0, 300.0)
 THRESHOLD = 3.0
 KEPT_LOOSE, LOOSE_FWD, LOOSE_BWD = 0.005, 0.02, 0.05
 MIN_SHARE, MIN_KEPT = 0.10, 400
 REPORT = []
-
-
-def _per_point(e, norm):
-    return e.reshape(e.shape[0], -1).double().norm(dim=1) / norm
-
-
-def fwd_norm(ref):
-    return ref.reshape(ref.shape[0], -1).double().norm(dim=1).clamp_min(1.0)
 
 
 def gate(what, got, b64, y32, f64, norm, margin, backward, keep=None, failures=None, threshold=None, quiet=False):
@@ -48,7 +42,7 @@ def gate(what, got, b64, y32, f64, norm, margin, backward, keep=None, failures=N
     judged = ~zero if keep is None else (~zero & keep)
     nz = norm.clone().double()
     nz[zero] = 1
-    e_k, e_y, eff = _per_point(got - b64, nz), _per_point(y32 - b64, nz), _per_point(b64 - f64, nz)
+    e_k, e_y, eff = per_point(got - b64, nz), per_point(y32 - b64, nz), per_point(b64 - f64, nz)
     kept = judged & margin.kept(threshold)
     n_j, n_k = int(judged.sum()), int(kept.sum())
     r.update(n=n_j, kept=n_k / max(n_j, 1))

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 import optim_ref64 as R
+from gate64 import gate, report
 
 F32, F64 = torch.float32, torch.float64
 CLASSES = "ABCDEFG"
@@ -92,10 +93,10 @@ def adam_norms(case, r64):
 class AdamJudge:
     """Adam results judged class by class and once pooled: a class with >= 64 elements in a case is gated on the spot, smaller ones
     are gathered over the cases and gated in ``finish``.  Class C is held to equality; class E's m and v are reported, not gated.
-    gate / report: tests/test_gemm_float64_gpu.py::gate, tests/test_objective_float64_gpu.py::gate_larger and ::report."""
+    The gate and the report are tests/gate64.py's, with the camera order as second yardstick unless ``table_order_only``."""
 
-    def __init__(self, gate_larger, report, failures, caught=None):
-        self.gate_larger, self.report, self.failures = gate_larger, report, failures
+    def __init__(self, failures, caught=None, table_order_only=False):
+        self.failures, self.table_order_only = failures, table_order_only
         self.pool, self.summary = {}, {}
         self.caught = caught             # optional set: the (quantity, class) pairs that FAILED are added instead of `failures`
 
@@ -110,14 +111,14 @@ class AdamJudge:
             s.update(gates=s["gates"] + 1, n=s["n"] + norm.numel(), rms_k=max(s["rms_k"], rms(e_k)), max_k=max(s["max_k"], float(e_k.max())),
                      rms_ratio=max(s["rms_ratio"], ratio(rms(e_k), rms_32)), max_ratio=max(s["max_ratio"], ratio(float(e_k.max()), max_32)))
         fails = []
-        ok = self.gate_larger(what, got[:, None], ref[:, None], y_a[:, None], y_b[:, None], norm, torch.ones_like(norm, dtype=torch.bool),
-                              fails)
+        ok = gate(what, got[:, None], ref[:, None], y_a[:, None], norm, torch.ones_like(norm, dtype=torch.bool), fails,
+                  None if self.table_order_only else y_b[:, None])
         (self.failures if self.caught is None else []).extend(fails)
         return ok
 
     def add(self, tag, case, got, r64, y_table, y_camera):
         """got, r64, y_table, y_camera: (m, v, p) triples; the gate takes the larger of the two yardsticks' errors -- a kernel with ONE documented
-        order is handed that yardstick twice, which makes gate_larger the plain gate"""
+        order is handed that yardstick twice, which makes the two-yardstick gate the plain one"""
         cls, norms = case["cls"], adam_norms(case, r64)
         c_ = cls == ord("C")
         if bool(c_.any()):
@@ -150,7 +151,7 @@ class AdamJudge:
         for (q, c, how), rows in sorted(self.pool.items()):
             if how == "report":
                 got, ref, y_a, _y_b, norm = (torch.cat([r[i] for r in rows]).cpu() for i in range(5))
-                self.report(f"{tag}: {q} class {c}", got[:, None], ref[:, None], y_a[:, None], norm, torch.ones_like(norm, dtype=torch.bool))
+                report(f"{tag}: {q} class {c}", got[:, None], ref[:, None], y_a[:, None], norm, torch.ones_like(norm, dtype=torch.bool))
             elif not self._gate(f"{tag}: {q} class {c} (over cases)", rows, (q, c)) and self.caught is not None:
                 self.caught.add((q, c))
         self.pool = {}

@@ -2,47 +2,24 @@
 neighbourhood's mean and scatter, the cyclic Jacobi, the normal's orientation and validity), compiled by the host compiler with
 -ffp-contract=off into tests/cloud_normals_host_check.cpp and held to tests/normals_ref.py bit for bit; once plain and once under the
 address and undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_program
+from host_program import bits32, words
 import normals_ref as N
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "cloud_normals_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "cloud_normals_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
-
-
-words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
-bits32 = lambda a: words(np.ascontiguousarray(a, np.float32).view(np.uint32))
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("cloud_normals_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("cloud_normals_host_check.cpp", tmp_path_factory.mktemp("cloud_normals_host"),
+                             sanitize, flags=("-ffp-contract=off",))
 
     def call(mode, path, lines):
         with open(path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
-        out = subprocess.run([exe, mode, str(path)], capture_output=True, text=True, timeout=300)
+        out = host_program.run(exe, [mode, str(path)], 300, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout[-2000:] + out.stderr
         return out.stdout.split("\n")
     return call

@@ -1,7 +1,7 @@
 """Every bf16-operand MLP kernel (csrc/*_bf16.hip, NSA_PIECES == 1: the twelve nsa_*_bf16 entry points of csrc/bf16_entries.hpp, each
 called DIRECTLY) against the float64-accumulating bf16 reference (tests/ref64.py, quant mode), per point.
 
-The launch helpers, input builders and cotangent families are tests/test_gemm_float64_gpu.py's (Net(precision="bf16") makes them
+The launch helpers, input builders and cotangent families are the fp32 suite's (tests/mlp_calls.py, tests/gemm_cases.py; Net(precision="bf16") makes them
 call the _bf16 twins); the gate is tests/bf16_gate.py's: kept points (rounding margin >= THRESHOLD) are held to the fp32
 yardstick with no flip allowance, left-out points to the tensor's largest bf16 effect, with caps on how many points may be loose.
 tests/test_ref64_bf16_cpu.py fixes THRESHOLD on the CPU and shows that the gate refuses four subtly wrong emulations.
@@ -50,7 +50,6 @@ MEASURED on the MI355X (N = 4 123, threshold 3; e_k, e_y divided by the float64 
 """
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -60,9 +59,10 @@ import torch
 import bf16_cases as C
 import bf16_gate as G
 import ref64
-import test_gemm_float64_gpu as F
-from test_gemm_float64_gpu import (Net, _cot, _cube_points, _fn, _st, _to_hl, k_colour_backward, k_colour_forward, k_sdf_backward,
-                                   k_sdf_forward, k_sdf_pair)
+from devcall import st
+from gemm_cases import cot
+from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, fn, k_colour_backward, k_colour_forward,
+                       k_sdf_backward, k_sdf_forward, k_sdf_pair, long_inputs, persistent_sweep, to_hl)
 
 pytestmark = pytest.mark.gpu
 
@@ -161,9 +161,9 @@ def k_sampler(net, tile, o, d, t_rand):
     od, dd, tr = o.cuda().contiguous(), d.cuda().contiguous(), t_rand.cuda().contiguous()
     z, sdf, far = torch.empty(R, E, device="cuda"), torch.empty(R, E, device="cuda"), torch.empty(R, device="cuda")
     t_lin = torch.linspace(0.0, 1.0, steps=E, device="cuda")
-    check(_fn(net, "nsa_sampler_sdf")(od.data_ptr(), dd.data_ptr(), R, E, t_lin.data_ptr(), tr.data_ptr(), float(us.near),
+    check(fn(net, "nsa_sampler_sdf")(od.data_ptr(), dd.data_ptr(), R, E, t_lin.data_ptr(), tr.data_ptr(), float(us.near),
                                       float(us.scene_bounding_sphere), float(us.far), ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(),
-                                      pf.data_ptr(), z.data_ptr(), sdf.data_ptr(), far.data_ptr(), _st()))
+                                      pf.data_ptr(), z.data_ptr(), sdf.data_ptr(), far.data_ptr(), st()))
     torch.cuda.synchronize()
     return z.cpu(), sdf.cpu(), far.cpu()
 
@@ -179,8 +179,8 @@ def k_sdf_points(net, tile, x):
     pc, pf = fs.packed_sdf(m, "coarse", use="sampler"), fs.packed_sdf(m, "fine", use="sampler")
     xd = x.cuda().contiguous()
     out = torch.full((x.shape[0],), float("nan"), device="cuda")
-    check(_fn(net, "nsa_sdf_points")(xd.data_ptr(), x.shape[0], ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
-                                     out.data_ptr(), _st()))
+    check(fn(net, "nsa_sdf_points")(xd.data_ptr(), x.shape[0], ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
+                                     out.data_ptr(), st()))
     torch.cuda.synchronize()
     return out.cpu()
 
@@ -222,7 +222,7 @@ def test_sampler_and_sdf_points_bf16_vs_float64(net, capsys):
 @pytest.mark.parametrize("which", ["coarse", "fine"])
 def test_sdf_backward_bf16_vs_float64(net, refs, which, capsys):
     x, fam = refs.inp.xb, refs.inp.fam
-    init = _cot(N, 40, (3,))
+    init = cot(N, 40, (3,))
     fails = []
     with capsys.disabled():
         print()
@@ -282,7 +282,7 @@ def test_colour_forward_composite_and_track_bf16_write_the_plain_kernels_rgb(net
     o = ((torch.rand(Rn, 3, generator=g) * 2 - 1) * 0.3).cuda()
     d = torch.nn.functional.normalize(torch.randn(Rn, 3, generator=g), dim=-1).cuda()
     z = (torch.rand(Rn, S, generator=g) * 0.6).sort(dim=1).values.cuda().contiguous()
-    grad, feat = torch.randn(P, 3, generator=g).cuda(), _to_hl(torch.randn(P, 64, generator=g) * 0.2)
+    grad, feat = torch.randn(P, 3, generator=g).cuda(), to_hl(torch.randn(P, 64, generator=g) * 0.2)
     sdf = (torch.randn(P, generator=g) * 0.05).cuda()
     gt = torch.rand(Rn, 3, generator=g).cuda()
     m = net.model
@@ -293,17 +293,17 @@ def test_colour_forward_composite_and_track_bf16_write_the_plain_kernels_rgb(net
     rgb, save = {}, {}
     for kind in ("plain", "composite", "track"):
         rgb[kind], save[kind] = new(P, 3), torch.zeros(fr.save_size(P), device="cuda")
-    check(_fn(net, "nsa_colour_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
-                                         rgb["plain"].data_ptr(), save["plain"].data_ptr(), _st()))
+    check(fn(net, "nsa_colour_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
+                                         rgb["plain"].data_ptr(), save["plain"].data_ptr(), st()))
     w, rv, dep, nm, ent = new(Rn, S), new(Rn, 3), new(Rn), new(Rn, 3), new(Rn)
-    check(_fn(net, "nsa_colour_forward_composite")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
+    check(fn(net, "nsa_colour_forward_composite")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
                                                    rgb["composite"].data_ptr(), save["composite"].data_ptr(), sdf.data_ptr(), vox.data_ptr(),
-                                                   m.voxel_res, w.data_ptr(), rv.data_ptr(), dep.data_ptr(), nm.data_ptr(), ent.data_ptr(), _st()))
+                                                   m.voxel_res, w.data_ptr(), rv.data_ptr(), dep.data_ptr(), nm.data_ptr(), ent.data_ptr(), st()))
     rv2, loss, g_sdf, g_rgb, g_grad = new(Rn, 3), new(Rn), new(P), new(P, 3), new(P, 3)
-    check(_fn(net, "nsa_colour_forward_track")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
+    check(fn(net, "nsa_colour_forward_track")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), feat.data_ptr(),
                                                rgb["track"].data_ptr(), save["track"].data_ptr(), sdf.data_ptr(), vox.data_ptr(), m.voxel_res,
                                                gt.data_ptr(), Rn, rv2.data_ptr(), loss.data_ptr(), g_sdf.data_ptr(), g_rgb.data_ptr(),
-                                               g_grad.data_ptr(), _st()))
+                                               g_grad.data_ptr(), st()))
     torch.cuda.synchronize()
     assert bool(torch.isfinite(rgb["plain"]).all())
     for kind in ("composite", "track"):
@@ -360,33 +360,18 @@ def test_bf16_backwards_are_point_independent_and_scale_equivariant_bit_for_bit(
     """bf16 rounding commutes with powers of two: cotangents x 2^k (k = -40, -13, 17, 40) scale every backward output exactly; other
     points' cotangents change nothing; a point whose cotangents are all zero comes out exactly 0 (the fp32 suite's test on the bf16
     entry points: plain, _params and colour + coarse twins)"""
-    F.test_backwards_are_point_independent_and_scale_equivariant_bit_for_bit(net, P)
+    check_backwards_point_independent(net, P)
 
 
 def test_bf16_forwards_are_point_independent(net):
-    F.test_forwards_are_point_independent(net)
-
-
-def _persistent_sweep():
-    """points of one sweep of the persistent kernels: CU count x waves per workgroup x 16 (both read, not assumed)"""
-    src = open(os.path.join(ROOT, "nicer_slam_amd", "csrc", "render_sdfnet4.hip")).read()
-    nw = {k: int(re.search(r"#define\s+" + k + r"\s+(\d+)", src).group(1)) for k in ("NSA_NW4_PAIR", "NSA_NW4_BWD")}
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    return cus * max(nw.values()) * 16
-
-
-def _long_inputs():
-    P = _persistent_sweep() * 5 // 4 + 11
-    x = torch.cat([_cube_points(N, 5), _cube_points(P - N, 95)]).contiguous()
-    gs, gf, gg = _cot(P, 96, ()), _cot(P, 97, (64,)), _cot(P, 98, (3,))
-    return P, x, gs, gf, gg
+    check_forwards_point_independent(net)
 
 
 def test_persistent_kernels_past_one_sweep_repeat_the_first_points_bit_for_bit(net):
     """the resident paired forward and fine backward loop over their tiles: a shape past one sweep (and ragged) makes later iterations
     of that loop and the last partial tile run, and its first N points must be the N-point run's bit for bit"""
-    P, x, gs, gf, gg = _long_inputs()
-    assert P > _persistent_sweep() and P % 32 not in (0, 16)
+    P, x, gs, gf, gg = long_inputs(N)
+    assert P > persistent_sweep() and P % 32 not in (0, 16)
     long_f, short_f = k_sdf_pair(net, x), k_sdf_pair(net, x[:N].contiguous())
     for k in long_f:
         assert bool(torch.isfinite(long_f[k]).all()), k
@@ -406,24 +391,12 @@ def test_persistent_kernels_past_one_sweep_repeat_the_first_points_bit_for_bit(n
 
 
 # ------------------------------------------------------------------------------------------------------------------ resident vs staged
-def _resident_child(path):
-    """(child process) pair forward and fine backward on the long shape and on P = 1, 17, 33 -> path"""
-    net = Net(precision="bf16")
-    P, x, gs, gf, gg = _long_inputs()
-    out = {}
-    for p in (P, 1, 17, 33):
-        f = k_sdf_pair(net, x[:p].contiguous())
-        out.update({f"pair {p} {k}": v for k, v in f.items()})
-        out[f"bwd {p}"] = k_sdf_backward(net, "fine", 16, x[:p].contiguous(), gs[:p], gf[:p], gg[:p])["x"]
-    torch.save(out, path)
-
-
 def test_resident_and_staged_forms_agree_at_kernel_level(tmp_path, capsys):
     """NSA_BF16_RESIDENT is read once per process: two fresh child processes, each under its own time limit, every exit status checked.
     The paired forward must agree bit for bit; the fine backward is a different kernel function in the two forms (same statements,
     the compiler may contract differently): to the last bits, the allowance tests/test_precision_gpu.py states (1e-6 of the largest)."""
-    script = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gemm_bf16_gpu as t; t._resident_child(sys.argv[1])" % (
-        ROOT, os.path.join(ROOT, "tests"))
+    script = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import mlp_calls; mlp_calls.resident_child(sys.argv[1], %d)" % (
+        ROOT, os.path.join(ROOT, "tests"), N)
     res = {}
     for flag in ("1", "0"):
         path = str(tmp_path / f"res{flag}.pt")

@@ -11,296 +11,19 @@ Cotangent scales c_p = 2^U(-60, 40), neighbours alternating between 2^40 and 2^-
 alone and all three at independent scales; g_sdf alone at 2^20..2^40 (the accumulator of the feature GEMM then holds sbar ws while its
 operand vector is zero); weights with max |w| in [64, 127.9] and rows below 2^-11.  Bit-for-bit properties that need no reference:
 point independence (other points' inputs changed, ragged P) and scale equivariance of the backwards (cotangents x 2^k).
-Inputs are explicit fp32 points (colour kernels: one sample per ray at z = 0, so x = o exactly), identical for kernel and references."""
-import ctypes
-
+Inputs are explicit fp32 points (colour kernels: one sample per ray at z = 0, so x = o exactly), identical for kernel and references.
+The gate is tests/gate64.py, the kernel calls tests/mlp_calls.py, the operands tests/gemm_cases.py."""
 import numpy as np
 import pytest
 import torch
 
 import ref64
-from helpers import load, params_of, oracle_config
+from gate64 import fwd_norm, gate
+from gemm_cases import KINK, N_BIG, SMALL_P, colour_inputs, cot, cube_points, scaled, scales, sdf_families
+from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, k_colour_backward, k_colour_forward,
+                       k_sdf_backward, k_sdf_forward, k_sdf_pair)
 
 pytestmark = pytest.mark.gpu
-
-N_BIG = 16411                                   # ragged (16411 = 512 x 32 + 27)
-SMALL_P = (1, 15, 17, 31, 33, 4097)
-KINK = 2e-6                                     # colour ReLU margin left out on both sides (as tests/test_configs_gpu.py)
-REPORT = []
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-# ------------------------------------------------------------------------------------------------------------------ the network
-def perturbed(name="full_vis_eval", edit=None, seed=0):
-    """-> (fixture, oracle config, parameters) of a golden model with every weight_v perturbed, optionally edited (CPU only)"""
-    fx = dict(load(name))
-    g = torch.Generator().manual_seed(seed)
-    for k in sorted(fx):
-        if k.startswith("param_") and k.endswith("weight_v"):
-            v = torch.from_numpy(np.array(fx[k]))
-            fx[k] = (v + 0.05 * torch.randn(v.shape, generator=g)).numpy()
-    if edit:
-        edit(fx, g)
-    return fx, oracle_config(fx), params_of(fx)
-
-
-def _fn(net, name):
-    """the entry point ``name`` for ``net``: the public one, or (Net(precision="bf16")) its bf16-operand twin, called directly"""
-    from nicer_slam_amd._native import lib
-    base = getattr(lib, name)
-    if not net.suffix:
-        return base
-    twin = getattr(lib, name + net.suffix)
-    twin.restype, twin.argtypes = base.restype, base.argtypes
-    return twin
-
-
-class Net:
-    """A golden model's parameters with every weight_v perturbed (so that all input columns matter), optionally edited, on the CPU
-    (references) and the GPU (kernels)."""
-
-    def __init__(self, name="full_vis_eval", edit=None, seed=0, precision="fp32"):
-        from test_model_cpu import build_model
-        fx, self.cfg, self.params = perturbed(name, edit, seed)
-        self.fx = fx
-        self.model = build_model(fx).cuda().eval()
-        for p in self.model.parameters():
-            p.requires_grad_(False)
-        # "bf16": the grid descriptors say precision 1 and every k_* helper below calls the nsa_*_bf16 entry point itself
-        assert precision in ("fp32", "bf16"), precision
-        self.model.mlp_precision = precision
-        self.suffix = "_bf16" if precision == "bf16" else ""
-
-    def sdf(self, which, tile):
-        from nicer_slam_amd.fused import sampler as fs
-        self.model.sdf_tile = tile
-        gd, keep = fs.sdf_grid_desc(self.model, which)
-        return gd, keep, fs.packed_sdf(self.model, which)
-
-    def colour(self):
-        from nicer_slam_amd.fused import render as fr, sampler as fs
-        m = self.model
-        gd, keep = fs.grid_desc(m.rendering_network.encoding, m.rendering_network.divide_factor, 2, fs.precision_of(m, "colour"))
-        return gd, keep, fr.packed_colour(m)
-
-
-def _hl(P):
-    from nicer_slam_amd.fused import render as fr
-    return fr.hl_index(P, "cuda")
-
-
-def _to_hl(v):
-    from nicer_slam_amd.fused import render as fr
-    P = v.shape[0]
-    buf = torch.zeros(fr.hl_size(P), device="cuda")
-    buf[_hl(P)] = v.cuda()
-    return buf
-
-
-def _explicit(x):
-    from nicer_slam_amd._native import PointsDesc
-    return PointsDesc(None, None, None, x.data_ptr(), x.shape[0], 0, None)
-
-
-def _one_per_ray(o, d):
-    """rays with ONE sample at z = 0: x = o + 0 d = o exactly, view dir d (the colour kernels need rays)"""
-    from nicer_slam_amd._native import PointsDesc
-    z = torch.zeros(o.shape[0], 1, device="cuda")
-    return PointsDesc(o.data_ptr(), d.data_ptr(), z.data_ptr(), None, o.shape[0], 1, None), z
-
-
-# ------------------------------------------------------------------------------------------------------------------ kernels
-def k_sdf_forward(net, which, tile, x, accumulate=0, init=None):
-    from nicer_slam_amd._native import lib, check
-    P = x.shape[0]
-    xd = x.cuda().contiguous()
-    gd, _keep, pk = net.sdf(which, tile)
-    sdf = torch.zeros(P, device="cuda") if init is None else init[0].cuda().clone()
-    grad = torch.zeros(P, 3, device="cuda") if init is None else init[1].cuda().clone()
-    feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda") if init is None else _to_hl(init[2])
-    pts = _explicit(xd)
-    check(_fn(net, "nsa_sdfnet_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), accumulate, sdf.data_ptr(), grad.data_ptr(),
-                                 feat.data_ptr(), _st()))
-    torch.cuda.synchronize()
-    return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
-
-
-def k_sdf_pair(net, x):
-    from nicer_slam_amd._native import lib, check
-    from nicer_slam_amd.fused import sampler as fs
-    P = x.shape[0]
-    xd = x.cuda().contiguous()
-    net.model.sdf_tile = 16
-    gc, kc = fs.sdf_grid_desc(net.model, "coarse", "coarse_pair")
-    gf, kf = fs.sdf_grid_desc(net.model, "fine")
-    pc, pf = fs.packed_sdf(net.model, "coarse", use="coarse_pair"), fs.packed_sdf(net.model, "fine")
-    sdf, grad = torch.full((P,), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
-    feat = torch.zeros(((P + 31) // 32) * 2048, device="cuda")
-    pts = _explicit(xd)
-    check(_fn(net, "nsa_sdfnet_forward_pair")(ctypes.byref(pts), ctypes.byref(gc), ctypes.byref(gf), pc.data_ptr(), pf.data_ptr(),
-                                      sdf.data_ptr(), grad.data_ptr(), feat.data_ptr(), _st()))
-    torch.cuda.synchronize()
-    return dict(sdf=sdf.cpu(), grad=grad.cpu(), feat=feat[_hl(P)].cpu())
-
-
-def k_sdf_backward(net, which, tile, x, g_sdf=None, g_feat=None, g_grad=None, accumulate=0, init=None, params=False):
-    from nicer_slam_amd._native import lib, check
-    from nicer_slam_amd.fused import mapping
-    P = x.shape[0]
-    xd = x.cuda().contiguous()
-    gd, _keep, pk = net.sdf(which, tile)
-    gs = g_sdf.cuda().contiguous() if g_sdf is not None else None
-    gf = _to_hl(g_feat) if g_feat is not None else None
-    gg = g_grad.cuda().contiguous() if g_grad is not None else None
-    g_x = torch.zeros(P, 3, device="cuda") if init is None else init.cuda().clone()
-    pts = _explicit(xd)
-    if not params:
-        check(_fn(net, "nsa_sdfnet_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
-                                      g_x.data_ptr(), _st()))
-        torch.cuda.synchronize()
-        return dict(x=g_x.cpu())
-    rows = _fn(net, "nsa_sdfnet_emit_rows_tile")(gd.n_hidden, tile)
-    assert rows > 0
-    emit = torch.full((rows, mapping.emit_ld(P)), float("nan"), device="cuda")
-    check(_fn(net, "nsa_sdfnet_backward_params")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), accumulate,
-                                         g_x.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
-    torch.cuda.synchronize()
-    return dict(x=g_x.cpu()), emit
-
-
-def k_colour_forward(net, x, d, normals, feat):
-    from nicer_slam_amd._native import lib, check
-    from nicer_slam_amd.fused import render as fr
-    P = x.shape[0]
-    o, dd = x.cuda().contiguous(), d.cuda().contiguous()
-    pts, _z = _one_per_ray(o, dd)
-    gd, _keep, pk = net.colour()
-    grad, fh = normals.cuda().contiguous(), _to_hl(feat)
-    rgb = torch.full((P, 3), float("nan"), device="cuda")
-    save = torch.zeros(fr.save_size(P), device="cuda")
-    check(_fn(net, "nsa_colour_forward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), rgb.data_ptr(),
-                                 save.data_ptr(), _st()))
-    torch.cuda.synchronize()
-    return rgb.cpu(), (o, dd, _z, grad, fh, save)
-
-
-def k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="plain", coarse_tile=32, g_sdf=None):
-    """kind: plain (nsa_colour_backward), params (nsa_colour_backward_params), coarse (nsa_colour_coarse_backward: + the coarse SDF
-    backward of the same points with g_sdf and the feature / normal cotangents just written)"""
-    from nicer_slam_amd._native import lib, check
-    from nicer_slam_amd.fused import mapping
-    P = x.shape[0]
-    _rgb, (o, dd, z, grad, fh, save) = k_colour_forward(net, x, d, normals, feat)
-    pts, _z = _one_per_ray(o, dd)
-    gd, _keep, pk = net.colour()
-    gr = g_rgb.cuda().contiguous()
-    g_feat = torch.full((((P + 31) // 32) * 2048,), float("nan"), device="cuda")
-    g_grad = torch.zeros(P, 3, device="cuda")
-    g_x, g_dir = torch.full((P, 3), float("nan"), device="cuda"), torch.full((P, 3), float("nan"), device="cuda")
-    emit = None
-    if kind == "plain":
-        check(_fn(net, "nsa_colour_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(), save.data_ptr(),
-                                      gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(), g_x.data_ptr(), g_dir.data_ptr(),
-                                      _st()))
-    elif kind == "params":
-        emit = torch.full((_fn(net, "nsa_colour_emit_rows")(), mapping.emit_ld(P)), float("nan"), device="cuda")
-        check(_fn(net, "nsa_colour_backward_params")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
-                                             save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
-                                             g_x.data_ptr(), g_dir.data_ptr(), None, emit.data_ptr(), emit.shape[1], _st()))
-    else:
-        gc, _kc, pc = net.sdf("coarse", coarse_tile)
-        gs = g_sdf.cuda().contiguous()
-        check(_fn(net, "nsa_colour_coarse_backward")(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
-                                             save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
-                                             g_x.data_ptr(), g_dir.data_ptr(), ctypes.byref(gc), pc.data_ptr(), gs.data_ptr(), _st()))
-    torch.cuda.synchronize()
-    out = dict(feat=g_feat[_hl(P)].cpu(), normals=g_grad.cpu(), x=g_x.cpu(), dirs=g_dir.cpu())
-    return (out, emit) if kind == "params" else out
-
-
-# ------------------------------------------------------------------------------------------------------------------ inputs
-def _cube_points(n, seed):
-    """uniform in the cube, an eighth of them within 1e-3 of a face (some exactly on it)"""
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.999
-    m = n // 8
-    i, face = torch.arange(m), torch.randint(3, (m,), generator=g)
-    x[i, face] = torch.sign(x[i, face]) * (1 - torch.rand(m, generator=g) * 1e-3)
-    x[i[::17], face[::17]] = torch.sign(x[i[::17], face[::17]])
-    return x[torch.randperm(n, generator=g)].contiguous()
-
-
-def _scales(n, seed, alternate=True, zeros=True):
-    """c_p = 2^U(-60, 40); within the first half neighbours alternate 2^40 / 2^-60; every 97th point 0"""
-    g = torch.Generator().manual_seed(seed)
-    e = torch.randint(-60, 41, (n,), generator=g).double()
-    if alternate:
-        h = torch.arange(n // 2)
-        e[h] = torch.where(h % 2 == 0, 40.0, -60.0).double()
-    c = torch.exp2(e)
-    if zeros:
-        c[torch.arange(n) % 97 == 5] = 0.0
-    return c
-
-
-def _cot(n, seed, shape):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn((n,) + shape, generator=g)
-
-
-def _scaled(base, c):
-    return (base.double() * c.reshape((-1,) + (1,) * (base.dim() - 1))).float()
-
-
-def _colour_inputs(net, n, seed):
-    from oracle import render_ref as R
-    x = _cube_points(n, seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    _s, feat, grad = R.sdf_outputs(net.params, net.cfg, x.clone(), "fine")
-    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1) * (0.6 + 0.8 * torch.rand(n, 1, generator=g))
-    return x, d.contiguous(), grad.detach().contiguous(), feat.detach().contiguous()
-
-
-# ------------------------------------------------------------------------------------------------------------------ the gate
-def _per_point(e, norm):
-    e = e.reshape(e.shape[0], -1).double().norm(dim=1)
-    return e / norm
-
-
-def gate(what, got, ref, y32, norm, keep=None, failures=None):
-    """per-point errors of kernel (got) and yardstick (y32) against float64 (ref), divided by norm [P]; rows with norm 0 must be
-    exactly 0 in the kernel output and are left out; keep: rows to judge."""
-    got, ref, y32 = (t.reshape(t.shape[0], -1).double() for t in (got, ref, y32))
-    zero = norm == 0
-    if bool(zero.any()):
-        assert bool((got[zero] == 0).all()), f"{what}: a point with all-zero cotangents has a non-zero output"
-    sel = ~zero if keep is None else (~zero & keep)
-    nz = norm.clone()
-    nz[zero] = 1
-    e_k, e_32 = _per_point(got - ref, nz)[sel], _per_point(y32 - ref, nz)[sel]
-    finite = bool(torch.isfinite(got[sel]).all())
-    rms = lambda e: float((e ** 2).mean().sqrt())
-    r = dict(what=what, n=int(sel.sum()), rms_k=rms(e_k), rms_32=rms(e_32), max_k=float(e_k.max()), max_32=float(e_32.max()),
-             finite=finite)
-    ok = finite and r["rms_k"] <= 1.5 * r["rms_32"] and r["max_k"] <= 3.0 * r["max_32"]
-    r["ok"] = ok
-    REPORT.append(r)
-    print(f"  {what:<58s} n={r['n']:6d}  e_k rms {r['rms_k']:.2e} max {r['max_k']:.2e}   e_32 rms {r['rms_32']:.2e} "
-          f"max {r['max_32']:.2e}  {'ok' if ok else 'FAIL'}")
-    if failures is not None and not ok:
-        failures.append(r)
-    return ok
-
-
-def _fwd_norm(ref):
-    return ref.reshape(ref.shape[0], -1).double().norm(dim=1).clamp_min(1.0)
 
 
 @pytest.fixture(scope="module")
@@ -311,7 +34,7 @@ def net():
 # ------------------------------------------------------------------------------------------------------------------ forward
 def test_sdf_forward_kernels_vs_float64(net, capsys):
     from oracle import render_ref as R
-    x = _cube_points(N_BIG, 1)
+    x = cube_points(N_BIG, 1)
     fails = []
     g = torch.Generator().manual_seed(2)
     init = (torch.randn(N_BIG, generator=g), torch.randn(N_BIG, 3, generator=g), torch.randn(N_BIG, 64, generator=g))
@@ -329,7 +52,7 @@ def test_sdf_forward_kernels_vs_float64(net, capsys):
                     for k, r, y, i in zip(("sdf", "grad", "feat"), ref, y32, range(3)):
                         r_ = r + init[i].double() if acc else r
                         y_ = (y + init[i]) if acc else y
-                        gate(f"sdfnet_forward {which} tile {tile} acc {acc}: {k}", out[k], r_, y_, _fwd_norm(r_), failures=fails)
+                        gate(f"sdfnet_forward {which} tile {tile} acc {acc}: {k}", out[k], r_, y_, fwd_norm(r_), failures=fails)
                     if acc == 0:
                         for P in SMALL_P:
                             small = k_sdf_forward(net, which, tile, x[:P].contiguous())
@@ -339,7 +62,7 @@ def test_sdf_forward_kernels_vs_float64(net, capsys):
         so, fo, go = R.sdf_outputs(net.params, net.cfg, x.clone(), "fine")
         out = k_sdf_pair(net, x)
         for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
-            gate(f"sdfnet_forward_pair: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+            gate(f"sdfnet_forward_pair: {k}", out[k], r, y, fwd_norm(r), failures=fails)
     assert not fails, [f["what"] for f in fails]
 
 
@@ -373,26 +96,11 @@ def test_sampler_vs_float64(net, capsys):
                     y32 = R.sdf_vals(net.params, net.cfg, x.clone()).reshape(-1)
             res[tile] = (z, sdf)
             assert torch.equal(z, res[16][0]), f"tile {tile}: z differs from the quad tiling's"
-            gate(f"sampler_sdf tile {tile}: sdf", sdf.reshape(-1), ref, y32, _fwd_norm(ref), failures=fails)
+            gate(f"sampler_sdf tile {tile}: sdf", sdf.reshape(-1), ref, y32, fwd_norm(ref), failures=fails)
     assert not fails, [f["what"] for f in fails]
 
 
 # ------------------------------------------------------------------------------------------------------------------ SDF backward
-def _sdf_families(n):
-    """name -> (g_sdf, g_feat, g_grad, c_p): cotangents of O(1) random base values times per-point scales"""
-    base = (_cot(n, 10, ()), _cot(n, 11, (64,)), _cot(n, 12, (3,)))
-    c = _scales(n, 13)
-    fam = {"all three x c_p": tuple(_scaled(b, c) for b in base) + (c,)}
-    for i, name in enumerate(("g_sdf", "g_feat", "g_grad")):
-        fam[name + " alone x c_p"] = tuple(_scaled(b, c) if j == i else None for j, b in enumerate(base)) + (c,)
-    cs = [_scales(n, 20 + i, alternate=(i == 1)) for i in range(3)]
-    fam["independent scales per input"] = tuple(_scaled(b, ci) for b, ci in zip(base, cs)) + (torch.stack(cs).amax(0),)
-    g = torch.Generator().manual_seed(30)
-    ca = torch.exp2(torch.randint(20, 41, (n,), generator=g).double())
-    fam["g_sdf alone at 2^20..2^40 (features, normals NULL)"] = (_scaled(base[0], ca), None, None, ca)
-    return fam
-
-
 def _sdf_refs(net, which, x, fam):
     from oracle import render_ref as R
     out = {}
@@ -408,10 +116,10 @@ def _sdf_refs(net, which, x, fam):
 
 @pytest.mark.parametrize("which", ["coarse", "fine"])
 def test_sdf_backward_vs_float64(net, which, capsys):
-    x = _cube_points(N_BIG, 5)
-    fam = _sdf_families(N_BIG)
+    x = cube_points(N_BIG, 5)
+    fam = sdf_families(N_BIG)
     refs = _sdf_refs(net, which, x, fam)
-    init = _cot(N_BIG, 40, (3,))
+    init = cot(N_BIG, 40, (3,))
     fails = []
     with capsys.disabled():
         print()
@@ -446,7 +154,7 @@ def _colour_refs(net, x, d, normals, feat, g_rgb, grid_grad):
 
 def test_colour_kernels_vs_float64(net, capsys):
     from oracle import render_ref as R
-    x, d, normals, feat = _colour_inputs(net, N_BIG, 7)
+    x, d, normals, feat = colour_inputs(net, N_BIG, 7)
     keep = R.colour_relu_margin(net.params, net.cfg, x, normals, d, feat) >= KINK
     assert int((~keep).sum()) <= N_BIG // 100, int((~keep).sum())
     fails = []
@@ -456,12 +164,12 @@ def test_colour_kernels_vs_float64(net, capsys):
         ref = ref64.colour_forward(net.params, net.cfg, x, normals, d, feat)
         with torch.no_grad():
             y32 = R.colour_net(net.params, net.cfg, x, normals, d, feat)
-        gate("colour_forward: rgb", rgb, ref, y32, _fwd_norm(ref), keep, failures=fails)
+        gate("colour_forward: rgb", rgb, ref, y32, fwd_norm(ref), keep, failures=fails)
         for P in SMALL_P:
             small, _b = k_colour_forward(net, x[:P].contiguous(), d[:P].contiguous(), normals[:P].contiguous(), feat[:P].contiguous())
             assert torch.equal(small, rgb[:P]), f"colour forward: P = {P} changes rgb"
-        c = _scales(N_BIG, 8)
-        g_rgb = _scaled(_cot(N_BIG, 9, (3,)), c)
+        c = scales(N_BIG, 8)
+        g_rgb = scaled(cot(N_BIG, 9, (3,)), c)
         for grid_grad in (0, 1):
             ref, y32 = _colour_refs(net, x, d, normals, feat, g_rgb, grid_grad)
             out = k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad)
@@ -474,7 +182,7 @@ def test_colour_kernels_vs_float64(net, capsys):
                     assert torch.equal(small[k], out[k][:P]), f"colour backward: P = {P} changes d/d {k}"
             # colour + coarse SDF backward in one launch: d/dx = colour's + the coarse network's for (g_sdf, the colour's feature and
             # normal cotangents); the float64 chain takes the float64 cotangents, the yardstick its own fp32 ones
-            g_sdf = _scaled(_cot(N_BIG, 15, ()), c)
+            g_sdf = scaled(cot(N_BIG, 15, ()), c)
             outc = k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="coarse", g_sdf=g_sdf)
             for k in ("feat", "normals", "dirs"):
                 assert torch.equal(outc[k], out[k]), f"colour_coarse_backward: d/d {k} differs from nsa_colour_backward's"
@@ -498,8 +206,8 @@ LDS_JACOBIAN_ONLY_IN_MAP = {("coarse", 32)}
 
 @pytest.mark.parametrize("which,tile", [("coarse", 16), ("coarse", 32), ("fine", 16), ("fine", 32)])
 def test_sdf_params_kernel_data_path_and_padding(net, which, tile, capsys):
-    x_big = _cube_points(N_BIG, 11)
-    fam = _sdf_families(N_BIG)
+    x_big = cube_points(N_BIG, 11)
+    fam = sdf_families(N_BIG)
     gs, gf, gg, c = fam["all three x c_p"]
     big, smalls = None, []
     for P in (33, 4097, N_BIG):
@@ -528,8 +236,8 @@ def test_sdf_params_kernel_data_path_and_padding(net, which, tile, capsys):
 
 @pytest.mark.parametrize("P", [33, 4097, N_BIG])
 def test_colour_params_kernel_data_path_is_bit_identical_and_padding_zero(net, P):
-    xc, d, normals, feat = _colour_inputs(net, P, 12)
-    g_rgb = _scaled(_cot(P, 13, (3,)), _scales(P, 14))
+    xc, d, normals, feat = colour_inputs(net, P, 12)
+    g_rgb = scaled(cot(P, 13, (3,)), scales(P, 14))
     for grid_grad in (0, 1):
         plain = k_colour_backward(net, xc, d, normals, feat, g_rgb, grid_grad)
         out, emit = k_colour_backward(net, xc, d, normals, feat, g_rgb, grid_grad, kind="params")
@@ -540,86 +248,13 @@ def test_colour_params_kernel_data_path_is_bit_identical_and_padding_zero(net, P
 
 
 # ------------------------------------------------------------------------------------------------------------------ properties
-def _backward_runs(net, x, xc, d, normals, feat):
-    """name -> f(scale [P]) running one backward kernel with every cotangent of point p multiplied by scale[p]"""
-    P = x.shape[0]
-    base = (_cot(P, 50, ()), _cot(P, 51, (64,)), _cot(P, 52, (3,)))
-    g_rgb, g_sdf = _cot(P, 53, (3,)), _cot(P, 54, ())
-    runs = {}
-    for which in ("coarse", "fine"):
-        for tile in (16, 32):
-            runs[f"sdfnet_backward {which} t{tile}"] = (
-                lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(_scaled(b, s) for b in base)))
-            runs[f"sdfnet_backward_params {which} t{tile}"] = (
-                lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(_scaled(b, s) for b in base), params=True)[0])
-    for grid_grad in (0, 1):
-        runs[f"colour_backward gg {grid_grad}"] = (
-            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad))
-        runs[f"colour_backward_params gg {grid_grad}"] = (
-            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad, kind="params")[0])
-        runs[f"colour_coarse_backward gg {grid_grad}"] = (
-            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, _scaled(g_rgb, s), grid_grad, kind="coarse",
-                                                             g_sdf=_scaled(g_sdf, s)))
-    return runs
-
-
 @pytest.mark.parametrize("P", [33, 4097])
 def test_backwards_are_point_independent_and_scale_equivariant_bit_for_bit(net, P):
-    x = _cube_points(P, 60)
-    xc, d, normals, feat = _colour_inputs(net, P, 61)
-    ones = torch.ones(P).double()
-    odd = torch.arange(P) % 2 == 1
-    g = torch.Generator().manual_seed(62)
-    other = torch.where(odd, torch.exp2(torch.randint(0, 3, (P,), generator=g).double() * 40 - 40), ones)   # 2^-40, 1, 2^40
-    other[odd & (torch.arange(P) % 3 == 0)] = 0.0
-    for name, run in _backward_runs(net, x, xc, d, normals, feat).items():
-        ref = run(ones)
-        moved = run(other)
-        for k in ref:
-            assert torch.equal(moved[k][~odd], ref[k][~odd]), f"{name}: other points' cotangents change d/d {k}"
-        for kexp in (-40, -13, 17, 40):
-            s = torch.where(odd, torch.full((P,), 2.0 ** kexp).double(), ones)
-            out = run(s)
-            for k in ref:
-                want = ref[k].double() * s.reshape((-1,) + (1,) * (ref[k].dim() - 1))
-                assert torch.equal(out[k].double(), want), \
-                    f"{name}: cotangents x 2^{kexp} do not scale d/d {k} by 2^{kexp}: {int((out[k].double() != want).sum())} entries"
+    check_backwards_point_independent(net, P)
 
 
 def test_forwards_are_point_independent(net):
-    P = 4097
-    x = _cube_points(P, 70)
-    odd = torch.arange(P) % 2 == 1
-    x2 = x.clone()
-    x2[odd] = _cube_points(P, 71)[odd]
-    for which in ("coarse", "fine"):
-        for tile in (16, 32):
-            a, b = k_sdf_forward(net, which, tile, x), k_sdf_forward(net, which, tile, x2)
-            for k in a:
-                assert torch.equal(a[k][~odd], b[k][~odd]), f"sdfnet_forward {which} t{tile}: other points' positions change {k}"
-    a, b = k_sdf_pair(net, x), k_sdf_pair(net, x2)
-    for k in a:
-        assert torch.equal(a[k][~odd], b[k][~odd]), f"sdfnet_forward_pair: other points' positions change {k}"
-    xc, d, normals, feat = _colour_inputs(net, P, 72)
-    xc2, d2, n2, f2 = _colour_inputs(net, P, 73)
-    sw = lambda u, v: torch.where(odd.reshape((-1,) + (1,) * (u.dim() - 1)), v, u).contiguous()
-    a, _ = k_colour_forward(net, xc, d, normals, feat)
-    b, _ = k_colour_forward(net, sw(xc, xc2), sw(d, d2), sw(normals, n2), sw(feat, f2))
-    assert torch.equal(a[~odd], b[~odd]), "colour_forward: other points' inputs change rgb"
-    # the sampler: other rays' origins, directions and jitter changed (ragged ray count)
-    from nicer_slam_amd.fused import sampler as fs
-    g = torch.Generator().manual_seed(74)
-    Rn, E = 261, net.model.ray_sampler.N_samples_eval
-    rays = [(((torch.rand(Rn, 3, generator=g) * 2 - 1) * 0.8), torch.nn.functional.normalize(torch.randn(Rn, 3, generator=g), dim=-1),
-             torch.rand(Rn, E, generator=g)) for _ in range(2)]
-    odd_r = torch.arange(Rn) % 2 == 1
-    mixed = [torch.where(odd_r.reshape((-1,) + (1,) * (u.dim() - 1)), v, u).contiguous() for u, v in zip(*rays)]
-    for tile in (16, 32, 64):
-        net.model.sdf_tile = tile
-        a = fs.sampler_sdf(net.model, *(t.cuda() for t in rays[0]))
-        b = fs.sampler_sdf(net.model, *(t.cuda() for t in mixed))
-        for u, v, what in zip(a, b, ("z", "sdf", "far")):
-            assert torch.equal(u[~odd_r.cuda()], v[~odd_r.cuda()]), f"sampler_sdf tile {tile}: other rays change {what}"
+    check_forwards_point_independent(net)
 
 
 # ------------------------------------------------------------------------------------------------------------------ weights
@@ -658,31 +293,31 @@ def test_weights_near_the_pack_limit_vs_float64(tile, capsys):
     for prefix in ("implicit_network.fine.lin1", "rendering_network.lin1"):
         top, small = _max_w(net.params, prefix)
         assert 64 <= top <= 127.9 and small < 2.0 ** -11, (prefix, top, small)
-    x = _cube_points(N_BIG, 80)
+    x = cube_points(N_BIG, 80)
     fails = []
     with capsys.disabled():
         print()
         ref = ref64.sdf_forward(net.params, net.cfg, x, ("fine",))
         so, fo, go = R._net_outputs(net.params, "implicit_network.fine", net.cfg.fine, x.clone())
-        fam = _sdf_families(N_BIG)
+        fam = sdf_families(N_BIG)
         refs = _sdf_refs(net, "fine", x, {k: fam[k] for k in ("all three x c_p", "g_sdf alone at 2^20..2^40 (features, normals NULL)")})
         out = k_sdf_forward(net, "fine", tile, x)
         for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
-            gate(f"big weights: sdfnet_forward fine t{tile}: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+            gate(f"big weights: sdfnet_forward fine t{tile}: {k}", out[k], r, y, fwd_norm(r), failures=fails)
         for name, (r, y) in refs.items():
             gs, gf, gg, c = fam[name]
             gate(f"big weights: sdfnet_backward fine t{tile}: {name}", k_sdf_backward(net, "fine", tile, x, gs, gf, gg)["x"],
                  r, y, c, failures=fails)
-        xc, d, normals, feat = _colour_inputs(net, N_BIG, 81)
+        xc, d, normals, feat = colour_inputs(net, N_BIG, 81)
         keep = R.colour_relu_margin(net.params, net.cfg, xc, normals, d, feat) >= KINK
         assert int((~keep).sum()) <= N_BIG // 100
         rgb, _b = k_colour_forward(net, xc, d, normals, feat)
         r = ref64.colour_forward(net.params, net.cfg, xc, normals, d, feat)
         with torch.no_grad():
             y = R.colour_net(net.params, net.cfg, xc, normals, d, feat)
-        gate("big weights: colour_forward: rgb", rgb, r, y, _fwd_norm(r), keep, failures=fails)
-        c = _scales(N_BIG, 82)
-        g_rgb = _scaled(_cot(N_BIG, 83, (3,)), c)
+        gate("big weights: colour_forward: rgb", rgb, r, y, fwd_norm(r), keep, failures=fails)
+        c = scales(N_BIG, 82)
+        g_rgb = scaled(cot(N_BIG, 83, (3,)), c)
         ref_c, y32 = _colour_refs(net, xc, d, normals, feat, g_rgb, 1)
         out = k_colour_backward(net, xc, d, normals, feat, g_rgb, 1)
         for k in ("feat", "normals", "x", "dirs"):
@@ -710,9 +345,9 @@ def test_a_weight_past_the_pack_limit_is_loud_in_form_2(capsys):
     net = Net(edit=edit, seed=4)
     top, _ = _max_w(net.params, "implicit_network.fine.lin1")
     assert abs(top - 130.0) < 1e-3, top
-    x = _cube_points(4097, 90)
-    c = _scales(4097, 91, zeros=False)
-    gs, gf, gg = (_scaled(b, c) for b in (_cot(4097, 92, ()), _cot(4097, 93, (64,)), _cot(4097, 94, (3,))))
+    x = cube_points(4097, 90)
+    c = scales(4097, 91, zeros=False)
+    gs, gf, gg = (scaled(b, c) for b in (cot(4097, 92, ()), cot(4097, 93, (64,)), cot(4097, 94, (3,))))
     form = pack.operand_form()
     fails = []
     with capsys.disabled():
@@ -727,7 +362,7 @@ def test_a_weight_past_the_pack_limit_is_loud_in_form_2(capsys):
                 ref = ref64.sdf_forward(net.params, net.cfg, x, ("fine",))
                 so, fo, go = R._net_outputs(net.params, "implicit_network.fine", net.cfg.fine, x.clone())
                 for k, r, y in zip(("sdf", "grad", "feat"), ref, (so[:, 0].detach(), go.detach(), fo.detach())):
-                    gate(f"|w| = 130, form 3: sdfnet_forward fine t{tile}: {k}", out[k], r, y, _fwd_norm(r), failures=fails)
+                    gate(f"|w| = 130, form 3: sdfnet_forward fine t{tile}: {k}", out[k], r, y, fwd_norm(r), failures=fails)
                 r, y = _sdf_refs(net, "fine", x, {"b": (gs, gf, gg, c)})["b"]
                 gate(f"|w| = 130, form 3: sdfnet_backward fine t{tile}: all three x c_p", bwd, r, y, c, failures=fails)
     # (the 32-point fine backward with large weights is a known miss of the float64 gate, see KNOWN_BIG_WEIGHT_MISSES)

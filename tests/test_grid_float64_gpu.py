@@ -16,9 +16,9 @@ error of 100 % of a faint row passes; here every error is divided by a quantity 
       "cell"     the sum over the row's contributing points of what the point sends into its cell, |g[b, l]| (second order:
                  |g[b, l]| max|q_b| scale), whatever the corner's weight: e_32 is 1e-7 .. 1e-6 in every pool, and a row that is
                  wrong by a percent of its point's cotangent fails.
-The gate is tests/test_gemm_float64_gpu.py's: rms(e_k) <= 1.5 rms(e_32) and max(e_k) <= 3 max(e_32), all finite, with
+The gate is tests/gate64.py: rms(e_k) <= 1.5 rms(e_32) and max(e_k) <= 3 max(e_32), all finite, with
 e_k = |kernel - float64| and e_32 = |C oracle - float64|; the table gradients have a second fp32 yardstick in the kernels' order of
-summation and are gated against the larger of the two (test_objective_float64_gpu.gate_larger; class Rows says why).  Rows no in-range point touches keep their prior content bit for bit, from a
+summation and are gated against the larger of the two (gate64.gate with kernel_order; class Rows says why).  Rows no in-range point touches keep their prior content bit for bit, from a
 zeroed buffer and from one pre-filled with a pattern (the ABI accumulates into it).  Without a reference: a permutation of the points
 passes the same gate and leaves the untouched rows alone; cotangents times 2^k scale rows of occupancy 1 by exactly 2^k.
 Which scatter path the inputs walk is counted by grid_ref64.paths and asserted in tests/test_grid_ref64_cpu.py.
@@ -29,8 +29,10 @@ import pytest
 import torch
 
 import grid_ref64 as G
-from test_gemm_float64_gpu import gate
-from test_objective_float64_gpu import gate_larger
+from devcall import ptr, st
+from gate64 import fwd_norm, gate
+from gemm_cases import KINK, cot, scaled
+from mlp_calls import Net, explicit, k_colour_forward, k_sdf_forward, one_per_ray, to_hl
 
 pytestmark = pytest.mark.gpu
 
@@ -181,7 +183,7 @@ class Rows:
             width = max(i[0].shape[1] for i in items)
             got, ref, y32, yker = (torch.cat([torch.nn.functional.pad(i[k], (0, width - i[k].shape[1])) for i in items]) for k in range(4))
             norm = torch.cat([i[4].reshape(-1) for i in items])
-            gate_larger(label, got, ref, y32, yker, norm, torch.ones_like(norm, dtype=torch.bool), fails)
+            gate(label, got, ref, y32, norm, failures=fails, kernel_order=yker)
 
 
 @pytest.fixture(scope="module")
@@ -384,27 +386,26 @@ def test_shipped_colour_geometry_sparse_scatter(capsys):
 # nsa_sdfnet_backward_params' g_table (csrc/sdf_net.hpp::table_grad_scatter, csrc/sdf_net4.hpp::table_grad_scatter4): per corner row
 # ONE value  w_corner hb + k_corner dl  -- the value path plus the table's share of the double backward through grad sdf.  float64 and
 # the fp32 yardstick are tests/ref64.py with grid="exact" (sdf_table_grad), on the golden model with perturbed weights
-# (test_gemm_float64_gpu.Net).  Its grids are small (4 levels of 64 rows, 8 levels up to 32^3 capped at 2^10), so thousands of
+# (mlp_calls.Net).  Its grids are small (4 levels of 64 rows, 8 levels up to 32^3 capped at 2^10), so thousands of
 # contributions meet in a row: the classes are pooled over the levels, and the second yardstick is the same fp32 rows summed by the
 # run merge of 64 consecutive points (a valid order, not these kernels' exact one: they tile 16 / 32 points).
 def k_sdf_table(net, which, tile, x, g_sdf, g_feat, g_grad, prefill=None):
     import ctypes
     from nicer_slam_amd._native import lib, check
     from nicer_slam_amd.fused import mapping
-    from test_gemm_float64_gpu import _explicit, _to_hl, _st, _ptr
     P = x.shape[0]
     xd = x.cuda().contiguous()
     gd, _keep, pk = net.sdf(which, tile)
     emb = getattr(net.model.implicit_network, which).encoding.embeddings
     gs = g_sdf.cuda().contiguous() if g_sdf is not None else None
-    gf = _to_hl(g_feat) if g_feat is not None else None
+    gf = to_hl(g_feat) if g_feat is not None else None
     gg = g_grad.cuda().contiguous() if g_grad is not None else None
     g_x = torch.zeros(P, 3, device="cuda")
     g_table = torch.zeros_like(emb) if prefill is None else prefill.cuda().clone()
     emit = torch.full((lib.nsa_sdfnet_emit_rows_tile(gd.n_hidden, tile), mapping.emit_ld(P)), float("nan"), device="cuda")
-    pts = _explicit(xd)
-    check(lib.nsa_sdfnet_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), _ptr(gs), _ptr(gf), _ptr(gg), 0,
-                                         g_x.data_ptr(), g_table.data_ptr(), emit.data_ptr(), emit.shape[1], _st()))
+    pts = explicit(xd)
+    check(lib.nsa_sdfnet_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), ptr(gs), ptr(gf), ptr(gg), 0,
+                                         g_x.data_ptr(), g_table.data_ptr(), emit.data_ptr(), emit.shape[1], st()))
     torch.cuda.synchronize()
     return g_x.cpu(), g_table.cpu()
 
@@ -427,7 +428,6 @@ def shipped_geometry(fx, g):
 
 @pytest.fixture(scope="module", params=["golden", "shipped"])
 def net(request):
-    from test_gemm_float64_gpu import Net
     n = Net(edit=shipped_geometry if request.param == "shipped" else None)
     n.geometry = request.param
     return n
@@ -455,14 +455,13 @@ def spread_copies(x, divide_factor):
 
 def _sdf_case(net, which, fam):
     import ref64
-    from test_gemm_float64_gpu import _scaled, _cot
     spec = getattr(net.cfg, which)
     P = 4123
     x = spread_copies((G.points(P, spec.grid) * 2.0 - 1.0) * spec.divide_factor, spec.divide_factor)
     c = G.point_scales(P, 7)
-    gs = _scaled(_cot(P, 21, ()), c) if fam in ("all", "sdf") else None
-    gf = _scaled(_cot(P, 22, (64,)), c) if fam in ("all", "feat") else None
-    gg = _scaled(_cot(P, 23, (3,)), c) if fam in ("all", "grad") else None
+    gs = scaled(cot(P, 21, ()), c) if fam in ("all", "sdf") else None
+    gf = scaled(cot(P, 22, (64,)), c) if fam in ("all", "feat") else None
+    gg = scaled(cot(P, 23, (3,)), c) if fam in ("all", "grad") else None
     r_x, r_t, plan = ref64.sdf_table_grad(net.params, net.cfg, x, which, gs, gf, gg)
     y_x, y_t, plan32 = ref64.sdf_table_grad(net.params, net.cfg, x, which, gs, gf, gg, dtype=torch.float32)
     # every row's contributions, float64 (norms) and fp32 (the second order of summation)
@@ -519,10 +518,9 @@ def k_colour_table(net, x, d, normals, feat, g_rgb, grid_grad, prefill=None):
     import ctypes
     from nicer_slam_amd._native import lib, check
     from nicer_slam_amd.fused import mapping
-    from test_gemm_float64_gpu import k_colour_forward, _one_per_ray, _st
     P = x.shape[0]
     _rgb, (o, dd, _z, grad, fh, save) = k_colour_forward(net, x, d, normals, feat)
-    pts, _keep_z = _one_per_ray(o, dd)
+    pts, _keep_z = one_per_ray(o, dd)
     gd, _keep, pk = net.colour()
     emb = net.model.rendering_network.encoding.embeddings
     gr = g_rgb.cuda().contiguous()
@@ -532,7 +530,7 @@ def k_colour_table(net, x, d, normals, feat, g_rgb, grid_grad, prefill=None):
     emit = torch.full((lib.nsa_colour_emit_rows(), mapping.emit_ld(P)), float("nan"), device="cuda")
     check(lib.nsa_colour_backward_params(ctypes.byref(pts), ctypes.byref(gd), pk.data_ptr(), grad.data_ptr(), fh.data_ptr(),
                                          save.data_ptr(), gr.data_ptr(), grid_grad, g_feat.data_ptr(), g_grad.data_ptr(),
-                                         g_x.data_ptr(), g_dir.data_ptr(), g_table.data_ptr(), emit.data_ptr(), emit.shape[1], _st()))
+                                         g_x.data_ptr(), g_dir.data_ptr(), g_table.data_ptr(), emit.data_ptr(), emit.shape[1], st()))
     torch.cuda.synchronize()
     return g_x.cpu(), g_table.cpu()
 
@@ -540,7 +538,6 @@ def k_colour_table(net, x, d, normals, feat, g_rgb, grid_grad, prefill=None):
 def test_fused_colour_table_gradient_row_by_row(net, capsys):
     import ref64
     from oracle import render_ref as R
-    from test_gemm_float64_gpu import _scaled, _cot, KINK
     cfg = net.cfg
     P = 4123
     x = spread_copies((G.points(P, cfg.colour_grid) * 2.0 - 1.0) * cfg.colour_divide_factor, cfg.colour_divide_factor)
@@ -548,7 +545,7 @@ def test_fused_colour_table_gradient_row_by_row(net, capsys):
     d = torch.nn.functional.normalize(torch.randn(P, 3, generator=gen), dim=-1).contiguous()
     normals, feat = torch.randn(P, 3, generator=gen), torch.randn(P, 64, generator=gen) * 0.3
     c = G.point_scales(P, 9)
-    g_rgb = _scaled(_cot(P, 32, (3,)), c)
+    g_rgb = scaled(cot(P, 32, (3,)), c)
     keep = R.colour_relu_margin(net.params, cfg, x, normals, d, feat) >= KINK
     assert int((~keep).sum()) <= P // 50, int((~keep).sum())
     ref, r_t, plan = ref64.colour_table_grad(net.params, cfg, x, normals, d, feat, g_rgb)
@@ -592,7 +589,6 @@ def test_fused_colour_table_gradient_row_by_row(net, capsys):
 @pytest.mark.parametrize("which", ["coarse", "fine"])
 def test_fused_sdf_forward_through_the_exact_grid(net, which, capsys):
     import ref64
-    from test_gemm_float64_gpu import k_sdf_forward, _fwd_norm
     spec = getattr(net.cfg, which)
     x = (G.points(4123, spec.grid) * 2.0 - 1.0) * spec.divide_factor
     k = torch.arange(2600, 2664)
@@ -614,7 +610,7 @@ def test_fused_sdf_forward_through_the_exact_grid(net, which, capsys):
         for tile in (16, 32):
             out = k_sdf_forward(net, which, tile, x)
             for k, r, y in zip(("sdf", "grad", "feat"), ref, y32):
-                gate(f"sdfnet_forward {net.geometry} {which} tile {tile} exact grid: {k}", out[k], r, y, _fwd_norm(r), keep=distinct, failures=fails)
-                gate(f"sdfnet_forward {net.geometry} {which} tile {tile} exact grid, u = 1 face: {k}", out[k], r, y, _fwd_norm(r), keep=on,
+                gate(f"sdfnet_forward {net.geometry} {which} tile {tile} exact grid: {k}", out[k], r, y, fwd_norm(r), keep=distinct, failures=fails)
+                gate(f"sdfnet_forward {net.geometry} {which} tile {tile} exact grid, u = 1 face: {k}", out[k], r, y, fwd_norm(r), keep=on,
                      failures=fails)
     assert not fails, [f["what"] for f in fails]

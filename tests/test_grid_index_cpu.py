@@ -9,45 +9,26 @@ tests/test_grid_float64_gpu.py: once plain, once under the address and undefined
     and the generic gather stay inside the level on every hashed or power-of-two level -- and do NOT on a dense level whose row count is
     no power of two (LV_SUBONCE: one conditional subtract is a modulo only for cell + 1 <= res).  That last finding is asserted as found
     (DESIGN.md section 7): a guard of the gather has to turn it into zero, and this assertion with it."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import grid_ref64 as G
+import host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
 LV_HASHED, LV_POW2, LV_SUBONCE = 1, 2, 4
 SHIPPED = {"coarse": (4, 8, 32, 32, 19), "fine": (8, 4, 32, 128, 19), "colour": (16, 2, 16, 2048, 24)}
 
 
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "grid_index_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", os.path.join(ROOT, "tests", "grid_index_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
-
-
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def sweep(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("grid_index_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("grid_index_host_check.cpp", tmp_path_factory.mktemp("grid_index_host"), sanitize)
 
     def call(geometry):
         from oracle import render_ref as R
         spec = R.make_grid_spec(*geometry)
         args = [spec.level_dim, repr(float(np.float32(np.log2(spec.per_level_scale)))), spec.base_resolution] + [int(o) for o in spec.offsets]
-        out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(a) for a in args], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout + out.stderr
         keys = "level flags rows res n_in in_disagree n_far generic_over generic_max offsets_over level_row_over offsets_out_of_table".split()
         rows = [dict(zip(keys, (int(x) for x in line.split()))) for line in out.stdout.strip().splitlines()]

@@ -12,6 +12,7 @@ import torch
 
 import grid_ref64 as G
 from helpers import load, tt, assert_close
+from mlp_calls import perturbed
 from oracle import hashenc
 from oracle import render_ref as R
 
@@ -162,16 +163,10 @@ def test_every_scatter_path_is_walked_by_the_gpu_inputs(name):
 
 
 def _listening_model(seed=0):
-    """the golden model with every weight_v perturbed, as tests/test_gemm_float64_gpu.py::Net does: its networks then listen to their
+    """the golden model with every weight_v perturbed, as tests/mlp_calls.py::Net does: its networks then listen to their
     grid features (the golden's own first-layer grid columns are zero)"""
-    from helpers import params_of, oracle_config
-    fx = dict(load("full_vis_eval"))
-    g = torch.Generator().manual_seed(seed)
-    for k in sorted(fx):
-        if k.startswith("param_") and k.endswith("weight_v"):
-            v = torch.from_numpy(np.array(fx[k]))
-            fx[k] = (v + 0.05 * torch.randn(v.shape, generator=g)).numpy()
-    return params_of(fx), oracle_config(fx)
+    _fx, cfg, params = perturbed(seed=seed)
+    return params, cfg
 
 
 @pytest.mark.parametrize("which", ["coarse", "fine"])

@@ -3,40 +3,21 @@ csrc/bulk_grid.hpp: the resolution solve, lower_bound, the 256-byte round-up) --
 compiler into tests/index_host_check.cpp and held to the numpy oracles; once plain and once under the address and
 undefined-behaviour sanitizers where the host compiler has them."""
 import bisect
-import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import raycast_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "index_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", os.path.join(ROOT, "tests", "index_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("index_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("index_host_check.cpp", tmp_path_factory.mktemp("index_host"), sanitize)
 
     def call(*args):
-        out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(a) for a in args], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout + out.stderr
         return [line.split() for line in out.stdout.strip().splitlines()]
     return call

@@ -2,9 +2,6 @@
 installed), Umeyama, the torch plumbing of nicer_slam_amd/mesh_clean.py on CPU tensors, the error paths, the command lines'
 parsing, the argument validation of C ABI Section 11, and the labelling passes of csrc/uf_passes.hpp run by host threads."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +9,7 @@ import torch
 
 import clean_ref as C
 import eval_ref as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program
 
 
 def _two_quads():
@@ -232,18 +228,7 @@ def test_argument_validation_needs_no_gpu():
 def test_labelling_passes_on_host_threads(tmp_path, sanitize):
     """The device's pass bodies (csrc/uf_passes.hpp) as host C++ on 8 threads, adversarial orders, against a sequential
     union-find; once more under the thread sanitizer where the host compiler has it."""
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = str(tmp_path / "uf_host_check")
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-pthread", os.path.join(ROOT, "tests", "uf_host_check.cpp"), "-o", exe]
-    if sanitize:
-        probe = subprocess.run(cmd + ["-fsanitize=thread"], capture_output=True, text=True)
-        if probe.returncode != 0:
-            pytest.skip("host compiler without -fsanitize=thread")
-    else:
-        subprocess.run(cmd, check=True)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    run = subprocess.run([exe, "8", "20000" if sanitize else "100000"], capture_output=True, text=True, env=env, timeout=600)
-    if sanitize and "FATAL: ThreadSanitizer" in run.stderr and "data race" not in run.stderr:
-        pytest.skip("the thread sanitizer cannot start here: " + run.stderr.strip().splitlines()[-1])
+    sanitize = "thread" if sanitize else None
+    exe = host_program.build("uf_host_check.cpp", tmp_path, sanitize, flags=("-pthread",))
+    run = host_program.run(exe, ["8", "20000" if sanitize else "100000"], 600, sanitize)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout + run.stderr

@@ -2,37 +2,16 @@
 the fold test, m1 / m2 / select, the prefix rule, apply, rename and compose), compiled by the host compiler with -ffp-contract=off
 into tests/decimate_host_check.cpp, run one item at a time and held to tests/decimate_ref.py bit for bit; once plain and once under
 the address and undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import clean_ref
 import decimate_ref as D
+import host_program
+from host_program import words
 import simplify_ref
 import smooth_ref as S
 import topology_ref as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "decimate_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "decimate_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 def _bits(x):
@@ -41,7 +20,8 @@ def _bits(x):
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("decimate_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("decimate_host_check.cpp", tmp_path_factory.mktemp("decimate_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, mesh, target_faces=None, max_error=None, boundary="quadric", boundary_weight=1.0, min_cos=0.2, eps=1e-3, fixed=None,
              max_rounds=256):
@@ -53,11 +33,10 @@ def run(request, tmp_path_factory):
         head = [len(v), len(f), int(target_faces is not None), int(target_faces or 0), int(max_error is not None), _bits(me2),
                 _bits(np.float64(min_cos) * np.float64(min_cos)), _bits(eps), D.BOUNDARY.index(boundary), _bits(boundary_weight),
                 max_rounds, int(c is not None)]
-        words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
         with open(path, "w") as fh:
             fh.write("\n".join([words(head), words(v.view(np.uint32)), words(f), words(fx),
                                 words(np.zeros(0) if c is None else np.ascontiguousarray(c, np.float32).view(np.uint32))]) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(path)], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout[-2000:] + out.stderr
         rows = [np.array([int(x) for x in line.split()], np.int64 if i == 2 else np.uint64)       # (the faces may hold -1)
                 for i, line in enumerate(out.stdout.split("\n")[:8])]

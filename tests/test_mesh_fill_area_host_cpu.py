@@ -2,42 +2,22 @@
 cell minimum as one lane and as 64 striding lanes merged along the xor butterfly, the final class, a face by descent), compiled by the
 host compiler with -ffp-contract=off into tests/fill_area_host_check.cpp, run one item at a time and held to tests/fill_area_ref.py
 bit for bit; once plain and once under the address and undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import clean_ref
 import fill_area_ref as A
 import fill_ref as R
+import host_program
+from host_program import words
 import simplify_ref
 import topology_ref as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "fill_area_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "fill_area_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("fill_area_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("fill_area_host_check.cpp", tmp_path_factory.mktemp("fill_area_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, mesh, method, max_area_edges=2048, min_sin=1e-6, **kw):
         """the program on the loops of the oracle; compares everything it prints with the oracle"""
@@ -52,10 +32,9 @@ def run(request, tmp_path_factory):
         ms2 = np.float64(min_sin) * np.float64(min_sin)
         mask = 1 << R.FOLDED if method == "auto" else 1 << R.FILLED | 1 << R.FOLDED
         head = [len(v), len(f), B, L, len(edges), mask, max_area_edges, int(np.array([ms2]).view(np.uint64)[0]), 0]
-        words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
         with open(path, "w") as fh:
             fh.write("\n".join([words(head), words(v.view(np.uint32)), words(f), words(edges), words(order), words(ref["ints"])]) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=300)
+        out = host_program.run(exe, [str(path)], 300, sanitize)
         assert out.returncode == 0 and not out.stderr, (out.returncode, out.stdout[-500:], out.stderr[-2000:])
         rows = [np.array([int(x) for x in line.split()], np.uint64 if i in (3, 5) else np.int64)
                 for i, line in enumerate(out.stdout.split("\n")[:8])]

@@ -2,35 +2,14 @@
 rounds of pointer jumping and list ranking, the row of a loop, the faces and vertices of the patch), compiled by the host compiler
 with -ffp-contract=off into tests/fill_host_check.cpp, run one item at a time and held to tests/fill_ref.py bit for bit; once plain
 and once under the address and undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import clean_ref
 import fill_ref as R
+import host_program
+from host_program import words
 import simplify_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "fill_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "fill_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 def _bits(x):
@@ -39,7 +18,8 @@ def _bits(x):
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("fill_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("fill_host_check.cpp", tmp_path_factory.mktemp("fill_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, mesh, max_edges=None, max_size=None, rings="auto", max_rings=64, skip_folded=True):
         v = np.ascontiguousarray(mesh["verts"], np.float32)
@@ -48,11 +28,10 @@ def run(request, tmp_path_factory):
         ms2 = 0.0 if max_size is None else np.float64(max_size) * np.float64(max_size)
         head = [len(v), len(f), int(c is not None), int(max_edges is not None), int(max_edges or 0), int(max_size is not None), _bits(ms2),
                 0 if rings == "auto" else int(rings), max_rings, int(skip_folded)]
-        words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
         with open(path, "w") as fh:
             fh.write("\n".join([words(head), words(v.view(np.uint32)), words(f),
                                 words(np.zeros(0) if c is None else np.ascontiguousarray(c, np.float32).view(np.uint32))]) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(path)], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout[-2000:] + out.stderr
         rows = [np.array([int(x) for x in line.split()], np.uint64 if i in (0, 8) else np.int64)
                 for i, line in enumerate(out.stdout.split("\n")[:12])]

@@ -3,44 +3,26 @@ tests/intersect_host_check.cpp: the 256-bit integer against Python's, products c
 fp32 -> integer conversion; the stage-1 / stage-2 decisions against tests/intersect_ref.py on the known pairs and the lattice soup.
 Once plain and once under the address and undefined-behaviour sanitizers where the host compiler has them."""
 import functools
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import intersect_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
 M = 1 << 256
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "intersect_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "intersect_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("intersect_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("intersect_host_check.cpp", tmp_path_factory.mktemp("intersect_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, lines):
         with open(path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=300)
+        out = host_program.run(exe, [str(path)], 300, sanitize)
         assert out.returncode == 0 and not out.stderr, (out.returncode, out.stdout[-500:], out.stderr[-2000:])
         got = out.stdout.split("\n")[:-1]
         assert len(got) == len(lines)

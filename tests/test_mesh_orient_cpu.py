@@ -2,18 +2,13 @@
 against exact rationals, the argument validation of the four entry points and of the Python functions, and the pass bodies of
 csrc/orient_passes.hpp on host threads.  No GPU."""
 import ctypes
-import os
-import platform
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import orient_ref as O
 import topology_ref as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def flips(f, V):
@@ -201,23 +196,7 @@ def test_orientation_passes_on_host_threads(tmp_path, sanitize):
     """The pass bodies the kernels run (csrc/orient_passes.hpp on uf_passes.hpp), compiled as host C++ into a stand-alone program and
     run by 8 threads on a host-built edge table: labels, orientability and flips equal a sequential two-colouring; once more under
     the thread sanitizer where the host compiler has it."""
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = str(tmp_path / "orient_host_check")
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-pthread", os.path.join(ROOT, "tests", "orient_host_check.cpp"),
-           "-o", exe]
-    if sanitize:
-        probe = subprocess.run(cmd + ["-fsanitize=thread"], capture_output=True, text=True)
-        if probe.returncode != 0:
-            pytest.skip("host compiler without -fsanitize=thread")
-    else:
-        subprocess.run(cmd, check=True)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    # the sanitizer's shadow memory needs the address space laid out its way: with many bits of address randomisation its start-up
-    # can die before main() (a FATAL line, or a bare SIGSEGV), so the sanitized program starts with randomisation off
-    setarch = shutil.which("setarch") if sanitize else None
-    prefix = [setarch, platform.machine(), "-R"] if setarch else []
-    run = subprocess.run(prefix + [exe, "8", "10000" if sanitize else "50000"], capture_output=True, text=True, env=env, timeout=600)
-    if sanitize and "FATAL: ThreadSanitizer" in run.stderr and "data race" not in run.stderr:
-        pytest.skip("the thread sanitizer cannot start here: " + run.stderr.strip().splitlines()[-1])
+    sanitize = "thread" if sanitize else None
+    exe = host_program.build("orient_host_check.cpp", tmp_path, sanitize, flags=("-pthread",))
+    run = host_program.run(exe, ["8", "10000" if sanitize else "50000"], 600, sanitize)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout + run.stderr

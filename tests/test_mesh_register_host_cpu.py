@@ -2,46 +2,24 @@
 rows a lane adds and the tree over the lanes), compiled by the host compiler with -ffp-contract=off into
 tests/register_host_check.cpp and held to tests/register_ref.py bit for bit; once plain and once under the address and
 undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import eval_ref as E
+import host_program
+from host_program import bits32, bits64, words
 import register_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
 KERNELS = ("l2", ("huber", R.K_EXACT), ("tukey", R.K_EXACT))
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "register_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "register_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("register_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("register_host_check.cpp", tmp_path_factory.mktemp("register_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, args, kernel, T):
         name, k = R.parse_kernel(kernel)
-        words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
-        bits64 = lambda a: words(np.ascontiguousarray(a, np.float64).view(np.uint64))
-        bits32 = lambda a: words(np.ascontiguousarray(a, np.float32).view(np.uint32))
         cur = args["cur"]
         surface = "face_idx" in args
         m, V, F = (0, len(args["verts"]), len(args["faces"])) if surface else (len(args["targets"]), 0, 0)
@@ -53,7 +31,7 @@ def run(request, tmp_path_factory):
             lines += [words(args["idx"]), bits32(args["dist"]), bits32(args["targets"]), bits32(args["normals"])]
         with open(path, "w") as fh:
             fh.write("\n".join(lines) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(path)], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout[-2000:] + out.stderr
         rows = out.stdout.split("\n")
         return dict(sums=np.array(rows[0].split(), np.uint64), counts=[int(x) for x in rows[1].split()],

@@ -2,16 +2,11 @@
 program (tests/manifold_host_check.cpp) and run by 8 threads on host-built edge tables: every output array and total equals the
 sequential oracle tests/manifold_ref.py element for element.  Once plain, once under the address and undefined-behaviour sanitizers
 and once under the thread sanitizer, where the host compiler has them.  No GPU."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_program
 import manifold_ref as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -31,21 +26,7 @@ def cases_file(tmp_path_factory):
 
 @pytest.mark.parametrize("sanitize", [None, "address,undefined", "thread"])
 def test_fan_split_passes_on_host_threads(tmp_path, cases_file, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = str(tmp_path / "manifold_host_check")
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-pthread", os.path.join(ROOT, "tests", "manifold_host_check.cpp"),
-           "-o", exe]
-    if sanitize:
-        probe = subprocess.run(cmd + [f"-fsanitize={sanitize}", "-fno-sanitize-recover=all"], capture_output=True, text=True)
-        if probe.returncode != 0:
-            pytest.skip(f"host compiler without -fsanitize={sanitize}")
-    else:
-        subprocess.run(cmd, check=True)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66", ASAN_OPTIONS="exitcode=67", UBSAN_OPTIONS="halt_on_error=1")
-    run = subprocess.run([exe, cases_file, "8"], capture_output=True, text=True, env=env, timeout=600)
-    if sanitize and ("FATAL: ThreadSanitizer" in run.stderr and "data race" not in run.stderr
-                     or "ReserveShadowMemoryRange failed" in run.stderr or "Shadow memory range interleaves" in run.stderr):
-        pytest.skip("the sanitizer cannot start here: " + run.stderr.strip().splitlines()[-1])
+    exe = host_program.build("manifold_host_check.cpp", tmp_path, sanitize, flags=("-pthread",))
+    run = host_program.run(exe, [cases_file, "8"], 600, sanitize)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout + run.stderr
     assert f"{len(M.kernel_cases())} cases" in run.stdout

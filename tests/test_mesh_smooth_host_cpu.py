@@ -2,41 +2,21 @@
 passes, one vertex's step, one vertex's area normal), compiled by the host compiler with -ffp-contract=off into
 tests/smooth_host_check.cpp and held to tests/smooth_ref.py bit for bit; once plain and once under the address and
 undefined-behaviour sanitizers where the host compiler has them."""
-import functools
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import clean_ref
+import host_program
+from host_program import words
 import simplify_ref
 import smooth_ref as S
 import topology_ref as T
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SANITIZE = "-fsanitize=address,undefined"
-
-
-@functools.lru_cache(maxsize=None)
-def _program(tmp, sanitize):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = os.path.join(tmp, "smooth_host_check" + ("_san" if sanitize else ""))
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "smooth_host_check.cpp"), "-o", exe]
-    if sanitize:
-        if subprocess.run(cmd + [SANITIZE, "-fno-sanitize-recover=all"], capture_output=True, text=True).returncode != 0:
-            pytest.skip("host compiler without " + SANITIZE)
-    else:
-        subprocess.run(cmd, check=True)
-    return exe
-
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])
 def run(request, tmp_path_factory):
-    exe = _program(str(tmp_path_factory.mktemp("smooth_host")), request.param)
+    sanitize = "address,undefined" if request.param else None
+    exe = host_program.build("smooth_host_check.cpp", tmp_path_factory.mktemp("smooth_host"), sanitize, flags=("-ffp-contract=off",))
 
     def call(path, verts, faces, factors, boundary, fixed=None, max_move=None):
         v = np.ascontiguousarray(verts, np.float32)
@@ -44,11 +24,10 @@ def run(request, tmp_path_factory):
         fx = np.zeros(len(v), np.uint32) if fixed is None else (np.asarray(fixed).reshape(-1) != 0).astype(np.uint32)
         mm = np.array([np.inf if max_move is None else max_move], np.float64)
         head = [len(v), len(f), len(factors), S.BOUNDARY.index(boundary), int(max_move is not None), int(mm.view(np.uint64)[0])]
-        words = lambda a: " ".join(str(int(x)) for x in np.asarray(a).reshape(-1))
         with open(path, "w") as fh:
             fh.write("\n".join([words(head), words(v.view(np.uint32)), words(f), words(fx),
                                 words(np.asarray(factors, np.float64).view(np.uint64))]) + "\n")
-        out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+        out = host_program.run(exe, [str(path)], 120, sanitize)
         assert out.returncode == 0 and not out.stderr, out.stdout[-2000:] + out.stderr
         rows = [np.array(line.split(), np.int64) for line in out.stdout.split("\n")[:6]]
         return dict(ring_start=rows[0], ring=rows[1], ring_edge=rows[2], out=rows[3].astype(np.uint32).reshape(-1, 3), state=rows[4],

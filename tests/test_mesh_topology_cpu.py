@@ -1,18 +1,14 @@
 """The numpy oracle of header Section 18 (tests/topology_ref.py) pinned on meshes whose answers can be derived by hand, against the
 older helpers of tests/mc_ref.py and tests/clean_ref.py, and the argument validation of the four entry points.  No GPU."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import clean_ref as C
+import host_program
 import mc_ref
 import topology_ref as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -149,19 +145,7 @@ def test_union_find_passes_on_host_threads(tmp_path, sanitize):
     """The pass bodies the kernels run (csrc/topo_passes.hpp on uf_passes.hpp), compiled as host C++ into a stand-alone program and
     run by 8 threads on a host-built edge table: face labels, boundary marks and loop roots equal a sequential union-find; once more
     under the thread sanitizer where the host compiler has it."""
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++")
-    assert cxx, "no host C++ compiler (the oracle's Makefile needs one as well)"
-    exe = str(tmp_path / "topology_host_check")
-    cmd = [cxx, "-O1" if sanitize else "-O2", "-g", "-std=c++17", "-pthread", os.path.join(ROOT, "tests", "topology_host_check.cpp"),
-           "-o", exe]
-    if sanitize:
-        probe = subprocess.run(cmd + ["-fsanitize=thread"], capture_output=True, text=True)
-        if probe.returncode != 0:
-            pytest.skip("host compiler without -fsanitize=thread")
-    else:
-        subprocess.run(cmd, check=True)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    run = subprocess.run([exe, "8", "10000" if sanitize else "50000"], capture_output=True, text=True, env=env, timeout=600)
-    if sanitize and "FATAL: ThreadSanitizer" in run.stderr and "data race" not in run.stderr:
-        pytest.skip("the thread sanitizer cannot start here: " + run.stderr.strip().splitlines()[-1])
+    sanitize = "thread" if sanitize else None
+    exe = host_program.build("topology_host_check.cpp", tmp_path, sanitize, flags=("-pthread",))
+    run = host_program.run(exe, ["8", "10000" if sanitize else "50000"], 600, sanitize)
     assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout + run.stderr

@@ -2,7 +2,7 @@
 compositing (nsa_composite_forward / _backward / _track), ray lifting and the camera chain (nsa_rays_forward, nsa_rays_pose_backward,
 nsa_rays_backward, nsa_cam_to_pose, nsa_pose_grad_to_cam, nsa_track_head, nsa_l1_loss) and the loss terms (nsa_slam_loss).
 
-The method is tests/test_gemm_float64_gpu.py's, and so is the gate (imported from there):
+The method is tests/test_gemm_float64_gpu.py's, and the gate is tests/gate64.py:
   * e_k = |kernel - float64|, e_32 = |fp32 mode of the same restatement - float64| (the yardstick; tests/test_objective_ref64_cpu.py
     holds that mode to oracle/render_ref.py and to the loss goldens, and bounds it on these very inputs),
   * PER RAY (or per image / per eikonal point): forward outputs divided by max(|float64 output|, 1), backward outputs by the ray's
@@ -32,91 +32,12 @@ import torch
 
 import objective_cases as C
 import objective_ref64 as O
-from test_gemm_float64_gpu import gate, _per_point
+from devcall import dev, nan, ptr, st
+from gate64 import Pool, fwd_norm, gate, report
 
 pytestmark = pytest.mark.gpu
 F32 = torch.float32
 NAN = float("nan")
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _dev(t):
-    return None if t is None else t.detach().to("cuda", torch.float32).contiguous()
-
-
-def _nan(*shape):
-    return torch.full(shape, NAN, device="cuda")
-
-
-def _fwd_norm(ref):
-    return ref.detach().reshape(ref.shape[0], -1).double().norm(dim=1).clamp_min(1.0)
-
-
-def gate_larger(what, got, ref, y_ref, y_ker, norm, keep, failures):
-    """gate() with TWO fp32 yardsticks -- the restatement's reference order (y_ref) and the kernel's documented order (y_ker): the
-    same per-row errors, the same factors 1.5 and 3, against the LARGER of the two yardsticks' rms and the larger of their maxima;
-    one line in gate's format, with both yardsticks' figures."""
-    got, ref, y_ref, y_ker = (t.reshape(t.shape[0], -1).double() for t in (got, ref, y_ref, y_ker))
-    zero = norm == 0
-    if bool(zero.any()):
-        assert bool((got[zero] == 0).all()), f"{what}: a point with all-zero cotangents has a non-zero output"
-    sel = ~zero & keep
-    nz = norm.clone()
-    nz[zero] = 1
-    e_k, e_r, e_o = (_per_point(t - ref, nz)[sel] for t in (got, y_ref, y_ker))
-    rms = lambda e: float((e ** 2).mean().sqrt())
-    finite = bool(torch.isfinite(got[sel]).all())
-    rms_32, max_32 = max(rms(e_r), rms(e_o)), max(float(e_r.max()), float(e_o.max()))
-    r = dict(what=what, n=int(sel.sum()), rms_k=rms(e_k), rms_32=rms_32, max_k=float(e_k.max()), max_32=max_32, finite=finite)
-    r["ok"] = ok = finite and r["rms_k"] <= 1.5 * rms_32 and r["max_k"] <= 3.0 * max_32
-    print(f"  {what:<58s} n={r['n']:6d}  e_k rms {r['rms_k']:.2e} max {r['max_k']:.2e}   e_32 rms {rms_32:.2e} max {max_32:.2e}  "
-          f"{'ok' if ok else 'FAIL'}   (e_32 reference order rms {rms(e_r):.2e} max {float(e_r.max()):.2e}, kernel order rms "
-          f"{rms(e_o):.2e} max {float(e_o.max()):.2e})")
-    if not ok:
-        failures.append(r)
-    return ok
-
-
-def report(what, got, ref, y32, norm, keep):
-    """a line in gate's format WITHOUT a verdict, for a quantity that no fp32 evaluation determines (rounding noise on both sides)"""
-    got, ref, y32 = (t.detach().cpu().reshape(t.shape[0], -1).double() for t in (got, ref, y32))
-    e_k, e_32 = _per_point(got - ref, norm)[keep], _per_point(y32 - ref, norm)[keep]
-    rms = lambda e: float((e ** 2).mean().sqrt())
-    print(f"  {what:<58s} n={int(keep.sum()):6d}  e_k rms {rms(e_k):.2e} max {float(e_k.max()):.2e}   e_32 rms {rms(e_32):.2e} "
-          f"max {float(e_32.max()):.2e}  reported, not gated")
-
-
-class Pool:
-    """rows of one quantity gathered over several cases (padded to a common width with zeros on all three sides), judged once"""
-
-    def __init__(self):
-        self.rows = {}
-
-    def add(self, what, got, ref, y32, norm, keep=None, kernel_order=None):
-        """kernel_order: a second fp32 yardstick in the kernel's documented operation order (the comment below lists the quantities
-        that have one and why); such a quantity is gated against the larger of the two yardsticks' errors (gate_larger)"""
-        P = got.shape[0]
-        flat = [t.detach().cpu().reshape(P, -1).double() for t in (got, ref, y32, y32 if kernel_order is None else kernel_order)]
-        keep = torch.ones(P, dtype=torch.bool) if keep is None else keep
-        self.rows.setdefault(what, []).append((flat, norm.double(), keep, kernel_order is not None))
-
-    def judge(self, prefix, failures):
-        for what, items in self.rows.items():
-            width = max(f[0].shape[1] for f, _n, _k, _a in items)
-            pad = lambda t: torch.nn.functional.pad(t, (0, width - t.shape[1]))
-            got, ref, y32, alt = (torch.cat([pad(f[i]) for f, _n, _k, _a in items]) for i in range(4))
-            norm, keep = torch.cat([n for _f, n, _k, _a in items]), torch.cat([k for _f, _n, k, _a in items])
-            if any(a for _f, _n, _k, a in items):
-                gate_larger(prefix + what, got, ref, y32, alt, norm, keep, failures)
-            else:
-                gate(prefix + what, got, ref, y32, norm, keep, failures)
 
 
 # Quantities that missed the gate against the reference-order yardstick on MI355X, traced, and found to be a different but equally
@@ -133,19 +54,19 @@ class Pool:
 class DevCase:
     def __init__(self, case):
         self.R, self.S = case["R"], case["S"]
-        self.t = {k: _dev(case[k]) for k in ("rays_o", "rays_d", "z", "sdf", "rgb", "grad", "voxels")}
+        self.t = {k: dev(case[k]) for k in ("rays_o", "rays_d", "z", "sdf", "rgb", "grad", "voxels")}
 
     def head(self, with_grad=True):
         t = self.t
-        return [_p(t["rays_o"]), _p(t["rays_d"]), _p(t["z"]), _p(t["sdf"]), _p(t["rgb"])] + ([_p(t["grad"])] if with_grad else []) + \
-               [_p(t["voxels"]), C.RES, self.R, self.S]
+        return [ptr(t["rays_o"]), ptr(t["rays_d"]), ptr(t["z"]), ptr(t["sdf"]), ptr(t["rgb"])] + ([ptr(t["grad"])] if with_grad else []) + \
+               [ptr(t["voxels"]), C.RES, self.R, self.S]
 
 
 def k_forward(dc):
     from nicer_slam_amd._native import lib, check
     R, S = dc.R, dc.S
-    out = dict(weights=_nan(R, S), rgb_values=_nan(R, 3), depth=_nan(R), nmap=_nan(R, 3), entropy=_nan(R))
-    check(lib.nsa_composite_forward(*dc.head(), *[_p(out[k]) for k in O.COMPOSITE_OUT], _st()))
+    out = dict(weights=nan(R, S), rgb_values=nan(R, 3), depth=nan(R), nmap=nan(R, 3), entropy=nan(R))
+    check(lib.nsa_composite_forward(*dc.head(), *[ptr(out[k]) for k in O.COMPOSITE_OUT], st()))
     torch.cuda.synchronize()
     return {k: v.cpu() for k, v in out.items()}
 
@@ -154,9 +75,9 @@ def k_backward(dc, cot):
     """cot: {name: fp32 CPU tensor}; absent = NULL"""
     from nicer_slam_amd._native import lib, check
     R, S = dc.R, dc.S
-    d = {k: _dev(cot.get(k)) for k in C.COTANGENTS}
-    g = [_nan(R, S), _nan(R, S, 3), _nan(R, S, 3)]
-    check(lib.nsa_composite_backward(*dc.head(), *[_p(d[k]) for k in C.COTANGENTS], *[_p(t) for t in g], _st()))
+    d = {k: dev(cot.get(k)) for k in C.COTANGENTS}
+    g = [nan(R, S), nan(R, S, 3), nan(R, S, 3)]
+    check(lib.nsa_composite_backward(*dc.head(), *[ptr(d[k]) for k in C.COTANGENTS], *[ptr(t) for t in g], st()))
     torch.cuda.synchronize()
     return [t.cpu() for t in g]
 
@@ -164,9 +85,9 @@ def k_backward(dc, cot):
 def k_track(dc, gt, n_total):
     from nicer_slam_amd._native import lib, check
     R, S = dc.R, dc.S
-    gtd = _dev(gt)
-    rgbv, loss, g = _nan(R, 3), _nan(R), [_nan(R, S), _nan(R, S, 3), _nan(R, S, 3)]
-    check(lib.nsa_composite_track(*dc.head(with_grad=False), _p(gtd), n_total, _p(rgbv), _p(loss), *[_p(t) for t in g], _st()))
+    gtd = dev(gt)
+    rgbv, loss, g = nan(R, 3), nan(R), [nan(R, S), nan(R, S, 3), nan(R, S, 3)]
+    check(lib.nsa_composite_track(*dc.head(with_grad=False), ptr(gtd), n_total, ptr(rgbv), ptr(loss), *[ptr(t) for t in g], st()))
     torch.cuda.synchronize()
     return rgbv.cpu(), loss.cpu(), [t.cpu() for t in g]
 
@@ -186,7 +107,7 @@ def _composite_rows(case, pool, tag=""):
     out = k_forward(dc)
     for k in O.COMPOSITE_OUT:
         assert bool(torch.isfinite(out[k]).all()), k
-        pool.add(f"{tag}forward: {k}", out[k], getattr(o64, k), getattr(o32, k), _fwd_norm(getattr(o64, k)), ~left if k == "depth" else None)
+        pool.add(f"{tag}forward: {k}", out[k], getattr(o64, k), getattr(o32, k), fwd_norm(getattr(o64, k)), ~left if k == "depth" else None)
     c, cot = C.composite_cotangents(case, seed=200 + S)
     zero_grad = torch.zeros(R, dtype=torch.bool)
     zero_grad[case["zero_grad_rays"]] = True
@@ -217,8 +138,8 @@ def _composite_rows(case, pool, tag=""):
     r64 = O.composite_track(a[0], a[1], a[2], *a[4:], gt, n_total)
     r32 = O.composite_track(a[0], a[1], a[2], *a[4:], gt, n_total, dtype=F32)
     keep = r64[3] >= C.KINK
-    pool.add(f"{tag}track: rgb_values", rgbv, r64[0], r32[0], _fwd_norm(r64[0]))
-    pool.add(f"{tag}track: ray_loss", ray_loss, r64[1], r32[1], _fwd_norm(r64[1]))
+    pool.add(f"{tag}track: rgb_values", rgbv, r64[0], r32[0], fwd_norm(r64[0]))
+    pool.add(f"{tag}track: ray_loss", ray_loss, r64[1], r32[1], fwd_norm(r64[1]))
     inv = torch.full((R,), 1.0 / (3 * n_total), dtype=torch.float64)
     for what, x, b, y in zip(("g_sdf", "g_rgb", "g_grad"), g, r64[2], r32[2]):
         assert bool(torch.isfinite(x).all())
@@ -301,8 +222,8 @@ def test_composite_rays_are_independent_bit_for_bit():
 def k_cam_to_pose(cam):
     from nicer_slam_amd._native import lib, check
     b = cam.shape[0]
-    camd, pose = _dev(cam), _nan(b, 4, 4)
-    check(lib.nsa_cam_to_pose(_p(camd), b, _p(pose), _st()))
+    camd, pose = dev(cam), nan(b, 4, 4)
+    check(lib.nsa_cam_to_pose(ptr(camd), b, ptr(pose), st()))
     torch.cuda.synchronize()
     return pose.cpu()
 
@@ -310,9 +231,9 @@ def k_cam_to_pose(cam):
 def k_rays_forward(uv, pose, K):
     from nicer_slam_amd._native import lib, check
     b, n = uv.shape[:2]
-    u, p, k = _dev(uv), _dev(pose), _dev(K)
-    o, d, ds = _nan(b * n, 3), _nan(b * n, 3), _nan(b * n)
-    check(lib.nsa_rays_forward(_p(u), _p(p), _p(k), b, n, _p(o), _p(d), _p(ds), _st()))
+    u, p, k = dev(uv), dev(pose), dev(K)
+    o, d, ds = nan(b * n, 3), nan(b * n, 3), nan(b * n)
+    check(lib.nsa_rays_forward(ptr(u), ptr(p), ptr(k), b, n, ptr(o), ptr(d), ptr(ds), st()))
     torch.cuda.synchronize()
     return o.cpu(), d.cpu(), ds.cpu()
 
@@ -320,9 +241,9 @@ def k_rays_forward(uv, pose, K):
 def k_rays_pose_backward(uv, pose, K, g_o, g_d):
     from nicer_slam_amd._native import lib, check
     b, n = uv.shape[:2]
-    u, p, k, go, gd = (_dev(t) for t in (uv, pose, K, g_o, g_d))
-    gp = _nan(b, 4, 4)
-    check(lib.nsa_rays_pose_backward(_p(u), _p(p), _p(k), b, n, _p(go), _p(gd), _p(gp), _st()))
+    u, p, k, go, gd = (dev(t) for t in (uv, pose, K, g_o, g_d))
+    gp = nan(b, 4, 4)
+    check(lib.nsa_rays_pose_backward(ptr(u), ptr(p), ptr(k), b, n, ptr(go), ptr(gd), ptr(gp), st()))
     torch.cuda.synchronize()
     return gp.cpu()
 
@@ -330,9 +251,9 @@ def k_rays_pose_backward(uv, pose, K, g_o, g_d):
 def k_pose_grad_to_cam(cam, g_pose):
     from nicer_slam_amd._native import lib, check
     b = cam.shape[0]
-    c, g = _dev(cam), _dev(g_pose)
-    out = _nan(b, 7)
-    check(lib.nsa_pose_grad_to_cam(_p(c), _p(g), b, _p(out), _st()))
+    c, g = dev(cam), dev(g_pose)
+    out = nan(b, 7)
+    check(lib.nsa_pose_grad_to_cam(ptr(c), ptr(g), b, ptr(out), st()))
     torch.cuda.synchronize()
     return out.cpu()
 
@@ -340,9 +261,9 @@ def k_pose_grad_to_cam(cam, g_pose):
 def k_track_head(uv1, K1, cam1):
     from nicer_slam_amd._native import lib, check
     n = uv1.shape[0]
-    u, k, c = _dev(uv1), _dev(K1), _dev(cam1)
-    pose, o, d, ds = _nan(4, 4), _nan(n, 3), _nan(n, 3), _nan(n)
-    check(lib.nsa_track_head(_p(u), _p(k), _p(c), n, _p(pose), _p(o), _p(d), _p(ds), _st()))
+    u, k, c = dev(uv1), dev(K1), dev(cam1)
+    pose, o, d, ds = nan(4, 4), nan(n, 3), nan(n, 3), nan(n)
+    check(lib.nsa_track_head(ptr(u), ptr(k), ptr(c), n, ptr(pose), ptr(o), ptr(d), ptr(ds), st()))
     torch.cuda.synchronize()
     return pose.cpu(), o.cpu(), d.cpu(), ds.cpu()
 
@@ -361,15 +282,15 @@ def test_rays_and_pose_chain_vs_float64(capsys):
             # cam -> pose
             pose = k_cam_to_pose(cam)
             p64, p32 = O.camera_from_tensor(cam.double()), O.camera_from_tensor(cam)
-            per_image.add("cam_to_pose: pose", pose, p64, p32, _fwd_norm(p64))
+            per_image.add("cam_to_pose: pose", pose, p64, p32, fwd_norm(p64))
             # pose (the kernel's, fp32) -> rays
             o, d, ds = k_rays_forward(uv, pose, K)
             r64, r32 = O.rays(uv, pose, K), O.rays(uv, pose, K, dtype=F32)
             assert torch.equal(o.reshape(b, n, 3), pose[:, None, :3, 3].expand(-1, n, -1)), "rays_o is not the pose's translation"
             d64, d32 = r64.rays_d.detach().reshape(-1, 3), r32.rays_d.detach().reshape(-1, 3)
-            per_ray.add("rays_forward: rays_d", d, d64, d32, _fwd_norm(d64))
+            per_ray.add("rays_forward: rays_d", d, d64, d32, fwd_norm(d64))
             s64, s32 = r64.depth_scale.detach().reshape(-1), r32.depth_scale.detach().reshape(-1)
-            per_ray.add("rays_forward: depth_scale", ds, s64, s32, _fwd_norm(s64))
+            per_ray.add("rays_forward: depth_scale", ds, s64, s32, fwd_norm(s64))
             # g_rays -> g_pose at that pose
             gp = k_rays_pose_backward(uv, pose, K, g_o, g_d)
             assert bool(torch.isfinite(gp).all())
@@ -387,10 +308,10 @@ def test_rays_and_pose_chain_vs_float64(capsys):
             for i in range(b):
                 hp, ho, hd, hs = k_track_head(uv[i], K[i], cam[i])
                 assert torch.equal(ho, cam[i, 4:].expand(n, 3)), "track_head: rays_o is not the camera's translation"
-                per_image.add("track_head: pose", hp[None], p64[i:i + 1], p32[i:i + 1], _fwd_norm(p64[i:i + 1]))
-                per_ray.add("track_head: rays_d", hd, c64.rays_d.detach()[i], c32.rays_d.detach()[i], _fwd_norm(c64.rays_d.detach()[i]))
+                per_image.add("track_head: pose", hp[None], p64[i:i + 1], p32[i:i + 1], fwd_norm(p64[i:i + 1]))
+                per_ray.add("track_head: rays_d", hd, c64.rays_d.detach()[i], c32.rays_d.detach()[i], fwd_norm(c64.rays_d.detach()[i]))
                 per_ray.add("track_head: depth_scale", hs, c64.depth_scale.detach()[i], c32.depth_scale.detach()[i],
-                            _fwd_norm(c64.depth_scale.detach()[i]))
+                            fwd_norm(c64.depth_scale.detach()[i]))
     with capsys.disabled():
         print(f"\n  rays and pose, b = {C.RAYS_B} x n = {C.RAYS_N} pooled")
         per_ray.judge("", fails)
@@ -407,9 +328,9 @@ def test_rays_backward_vs_float64(S, capsys):
     with capsys.disabled():
         print()
         for with_dir in (True, False):
-            z, gx, gdir = _dev(cs["z"]), _dev(cs["g_x"]), _dev(cs["g_dir"]) if with_dir else None
-            go, gd = _nan(R, 3), _nan(R, 3)
-            check(lib.nsa_rays_backward(_p(z), _p(gx), _p(gdir), R, S, _p(go), _p(gd), _st()))
+            z, gx, gdir = dev(cs["z"]), dev(cs["g_x"]), dev(cs["g_dir"]) if with_dir else None
+            go, gd = nan(R, 3), nan(R, 3)
+            check(lib.nsa_rays_backward(ptr(z), ptr(gx), ptr(gdir), R, S, ptr(go), ptr(gd), st()))
             torch.cuda.synchronize()
             a64 = O.rays_backward(cs["z"], cs["g_x"], cs["g_dir"] if with_dir else None)
             a32 = O.rays_backward(cs["z"], cs["g_x"], cs["g_dir"] if with_dir else None, dtype=F32)
@@ -424,8 +345,8 @@ def test_l1_loss_vs_float64(capsys):
     for n in C.L1_N:
         for seed in range(8):
             pred, target = C.l1_case(n, seed)
-            p, t, loss, g = _dev(pred), _dev(target), _nan(1), _nan(n)
-            check(lib.nsa_l1_loss(_p(p), _p(t), n, _p(loss), _p(g), _st()))
+            p, t, loss, g = dev(pred), dev(target), nan(1), nan(n)
+            check(lib.nsa_l1_loss(ptr(p), ptr(t), n, ptr(loss), ptr(g), st()))
             torch.cuda.synchronize()
             l64, g64 = O.l1(pred, target)
             l32, g32 = O.l1(pred, target, dtype=F32)
@@ -453,18 +374,18 @@ def k_slam_loss(out, gt, weights, whole, shape):
     bs, n, S, E = shape
     R = bs * n
     d = {k: _guarded(out[k]) for k in ("rgb_values", "depth_values", "normal_map", "sdf")}
-    gth = _dev(out["grad_theta"]) if E else None
-    gnei = _dev(out["grad_theta_nei"]) if (E and out["grad_theta_nei"] is not None) else None
+    gth = dev(out["grad_theta"]) if E else None
+    gnei = dev(out["grad_theta_nei"]) if (E and out["grad_theta_nei"] is not None) else None
     g = {k: _guarded(gt[k]) for k in ("rgb", "depth", "gt_depth", "gt_depth_mask", "mask", "normal")}
-    res = dict(rgb_values=_nan(R, 3), depth_values=_nan(R), normal_map=_nan(R, 3), grad_theta=_nan(E, 3) if E else None,
-               grad_theta_nei=_nan(E, 3) if gnei is not None else None)
-    terms = _nan(8)
+    res = dict(rgb_values=nan(R, 3), depth_values=nan(R), normal_map=nan(R, 3), grad_theta=nan(E, 3) if E else None,
+               grad_theta_nei=nan(E, 3) if gnei is not None else None)
+    terms = nan(8)
     ws = torch.full(((int(lib.nsa_slam_loss_workspace(bs, n, E)) + 1) // 2 + 8,), NAN, device="cuda", dtype=torch.float64)
-    desc = LossDesc(bs, n, S, E, _p(d["rgb_values"]), _p(g["rgb"]), _p(d["depth_values"]), _p(g["depth"]), _p(g["gt_depth"]),
-                    _p(g["gt_depth_mask"]), _p(g["mask"]), _p(d["sdf"]), _p(d["normal_map"]), _p(g["normal"]), _p(gth), _p(gnei),
+    desc = LossDesc(bs, n, S, E, ptr(d["rgb_values"]), ptr(g["rgb"]), ptr(d["depth_values"]), ptr(g["depth"]), ptr(g["gt_depth"]),
+                    ptr(g["gt_depth_mask"]), ptr(g["mask"]), ptr(d["sdf"]), ptr(d["normal_map"]), ptr(g["normal"]), ptr(gth), ptr(gnei),
                     *[float(w) for w in weights], int(bool(whole)),
-                    *[_p(res[k]) for k in O.LOSS_LEAVES], _p(terms))
-    check(lib.nsa_slam_loss(ctypes.byref(desc), ws.data_ptr(), _st()))
+                    *[ptr(res[k]) for k in O.LOSS_LEAVES], ptr(terms))
+    check(lib.nsa_slam_loss(ctypes.byref(desc), ws.data_ptr(), st()))
     torch.cuda.synchronize()
     return terms.cpu(), {k: (None if v is None else v.cpu()) for k, v in res.items()}
 

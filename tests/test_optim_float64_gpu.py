@@ -3,11 +3,11 @@ Adam (csrc/map_tail.hip: nsa_adam_table_step / _clear / _zero_grad in their floa
 csrc/track_tail.hip: nsa_adam_step / _scaled and the steps inside nsa_track_tail and nsa_track_finish), nicer_slam_amd.optim.Adam itself,
 the tracker's two reductions, the flat weight norm and its backward, and -- exactly -- the voxel counter and the Morton keys.
 
-The method and the gate are tests/test_gemm_float64_gpu.py's: e_k = |kernel - float64|, e_32 = |fp32 yardstick - float64|, per element
+The method is tests/test_gemm_float64_gpu.py's, the gate tests/gate64.py: e_k = |kernel - float64|, e_32 = |fp32 yardstick - float64|, per element
 (or per row) divided by a norm taken from the float64 side; rms(e_k) <= 1.5 rms(e_32) and max(e_k) <= 3 max(e_32), everything finite.
 Adam is judged class by class (tests/optim_cases.py: typical, untouched row, never touched, eps regime, subnormal, large, cancelling): the
 kernels of map_tail.hip against the fp32 order documented above their adam_one, the camera kernels of track_tail.hip against the larger of
-that order and their own documented one (gate_larger); the norms are max(|m0|, |g|), max(v0, v64) and max(|p0|, |p64 - p0|).  Class C is held to equality.  Class E's moments are reported, not gated.
+that order and their own documented one (gate64.gate with kernel_order); the norms are max(|m0|, |g|), max(v0, v64) and max(|p0|, |p64 - p0|).  Class C is held to equality.  Class E's moments are reported, not gated.
 
 Every buffer a kernel may write (and every gradient it reads) lies between 8 sentinel floats on either side that must come back bit for bit.
 tests/test_optim_ref64_cpu.py holds the references to torch and shows that the classes catch fourteen mutants.
@@ -22,7 +22,8 @@ import torch
 import objective_cases as OC
 import optim_cases as C
 import optim_ref64 as R
-from test_objective_float64_gpu import Pool, gate_larger, report
+from devcall import st
+from gate64 import Pool
 
 pytestmark = pytest.mark.gpu
 F32, F64 = torch.float32, torch.float64
@@ -34,10 +35,6 @@ NSA_OK, NSA_EBADARG = 0, 4
 def _lib():
     from nicer_slam_amd._native import lib
     return lib
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class Buf:
@@ -77,7 +74,7 @@ def _bits(t):
 
 def _refs(case, t, hyper, lr_step=0, gamma=1.0, g64=None, camera=False):
     """-> (float64, fp32 yardstick, second fp32 yardstick).  The kernels of map_tail.hip have ONE yardstick, the order documented above
-    their adam_one (handed over twice: gate_larger is then the plain gate); camera=True (k_adam and the steps inside the tracker tails)
+    their adam_one (handed over twice: the two-yardstick gate is then the plain one); camera=True (k_adam and the steps inside the tracker tails)
     adds the order documented in track_tail.hip, and the larger error counts."""
     b1, b2, eps, lr = hyper
     a = (case["m0"], case["v0"], t, lr, b1, b2, eps, lr_step, gamma)
@@ -88,7 +85,7 @@ def _refs(case, t, hyper, lr_step=0, gamma=1.0, g64=None, camera=False):
 
 
 def _judge(failures):
-    return C.AdamJudge(gate_larger, report, failures)
+    return C.AdamJudge(failures)
 
 
 def _finish(judge, tag, capsys):
@@ -108,9 +105,9 @@ def run_table(form, case, t, hyper, shift=(0, 0, 0, 0), what=""):
     p, g, m, v = (Buf(case[k], shift=s) for k, s in zip(("p0", "g", "m0", "v0"), shift))
     if form == "zero_grad":
         assert not bool(case["g"].any())
-        rc = _lib().nsa_adam_table_step_zero_grad(p.ptr, m.ptr, v.ptr, case["n"], t, lr, b1, b2, eps, _st())
+        rc = _lib().nsa_adam_table_step_zero_grad(p.ptr, m.ptr, v.ptr, case["n"], t, lr, b1, b2, eps, st())
     else:
-        rc = getattr(_lib(), FORMS[form])(p.ptr, g.ptr, m.ptr, v.ptr, case["n"], t, lr, b1, b2, eps, _st())
+        rc = getattr(_lib(), FORMS[form])(p.ptr, g.ptr, m.ptr, v.ptr, case["n"], t, lr, b1, b2, eps, st())
     assert rc == NSA_OK, (what, rc)
     _intact(what, p, g, m, v)
     if form == "clear":
@@ -180,19 +177,19 @@ def test_table_forms_bad_arguments_and_n_zero():
     p, g, m, v = (b.ptr for b in bufs)
     before = [b.words.clone() for b in bufs]
     for fn in (lib.nsa_adam_table_step, lib.nsa_adam_table_step_clear):
-        assert fn(p, g, m, v, 64, 0, lr, b1, b2, eps, _st()) == NSA_EBADARG              # step = 0
+        assert fn(p, g, m, v, 64, 0, lr, b1, b2, eps, st()) == NSA_EBADARG              # step = 0
         for i in range(4):                                                             # a pointer off by 2 bytes
             a = [p, g, m, v]
             a[i] += 2
-            assert fn(*a, 60, 1, lr, b1, b2, eps, _st()) == NSA_EBADARG
-        assert fn(p, g, m, v, 0, 1, lr, b1, b2, eps, _st()) == NSA_OK                    # n = 0
+            assert fn(*a, 60, 1, lr, b1, b2, eps, st()) == NSA_EBADARG
+        assert fn(p, g, m, v, 0, 1, lr, b1, b2, eps, st()) == NSA_OK                    # n = 0
     z = lib.nsa_adam_table_step_zero_grad
-    assert z(p, m, v, 64, 0, lr, b1, b2, eps, _st()) == NSA_EBADARG
+    assert z(p, m, v, 64, 0, lr, b1, b2, eps, st()) == NSA_EBADARG
     for i in range(3):
         a = [p, m, v]
         a[i] += 2
-        assert z(*a, 60, 1, lr, b1, b2, eps, _st()) == NSA_EBADARG
-    assert z(p, m, v, 0, 1, lr, b1, b2, eps, _st()) == NSA_OK
+        assert z(*a, 60, 1, lr, b1, b2, eps, st()) == NSA_EBADARG
+    assert z(p, m, v, 0, 1, lr, b1, b2, eps, st()) == NSA_OK
     torch.cuda.synchronize()
     for b, w in zip(bufs, before):
         assert torch.equal(b.words, w), "a refused or empty call wrote something"
@@ -215,9 +212,9 @@ def test_non_temporal_forms_at_2_pow_26_plus_5(form, capsys):
     r64 = R.adam_step(case["p0"], case["g"], case["m0"], case["v0"], t, lr, b1, b2, eps)          # float64 on the device
     p, g, m, v = (Buf(case[k]) for k in ("p0", "g", "m0", "v0"))
     if form == "zero_grad":
-        rc = _lib().nsa_adam_table_step_zero_grad(p.ptr, m.ptr, v.ptr, n, t, lr, b1, b2, eps, _st())
+        rc = _lib().nsa_adam_table_step_zero_grad(p.ptr, m.ptr, v.ptr, n, t, lr, b1, b2, eps, st())
     else:
-        rc = _lib().nsa_adam_table_step(p.ptr, g.ptr, m.ptr, v.ptr, n, t, lr, b1, b2, eps, _st())
+        rc = _lib().nsa_adam_table_step(p.ptr, g.ptr, m.ptr, v.ptr, n, t, lr, b1, b2, eps, st())
     assert rc == NSA_OK
     _intact("non-temporal " + form, p, g, m, v)
     assert torch.equal(_bits(g.t), _bits(case["g"]))
@@ -231,9 +228,9 @@ def test_non_temporal_forms_at_2_pow_26_plus_5(form, capsys):
     for lo, cnt in ((0, half), (half, n - half)):
         a = [b.ptr + 4 * lo for b in q]
         if form == "zero_grad":
-            rc = _lib().nsa_adam_table_step_zero_grad(a[0], a[2], a[3], cnt, t, lr, b1, b2, eps, _st())
+            rc = _lib().nsa_adam_table_step_zero_grad(a[0], a[2], a[3], cnt, t, lr, b1, b2, eps, st())
         else:
-            rc = _lib().nsa_adam_table_step(*a, cnt, t, lr, b1, b2, eps, _st())
+            rc = _lib().nsa_adam_table_step(*a, cnt, t, lr, b1, b2, eps, st())
         assert rc == NSA_OK
     torch.cuda.synchronize()
     same = [torch.equal(_bits(x.t), _bits(y.t)) for x, y in zip((p, m, v), (q[0], q[2], q[3]))]
@@ -254,7 +251,7 @@ def run_multi(segs, hyper, what):
     bufs = [[Buf(case[k], shift=shift) for k in ("p0", "g", "m0", "v0")] for case, _t, _lr, shift in segs]
     arr = (AdamSeg * len(segs))(*[AdamSeg(b[0].ptr, b[1].ptr, b[2].ptr, b[3].ptr, case["n"], t, lr)
                                   for b, (case, t, lr, _s) in zip(bufs, segs)])
-    assert _lib().nsa_adam_multi_step(arr, len(segs), b1, b2, eps, _st()) == NSA_OK, what
+    assert _lib().nsa_adam_multi_step(arr, len(segs), b1, b2, eps, st()) == NSA_OK, what
     _intact(what, *[x for b in bufs for x in b])
     for b, (case, _t, _lr, _s) in zip(bufs, segs):
         assert torch.equal(_bits(b[1].cpu()), _bits(case["g"]))
@@ -279,7 +276,7 @@ def test_multi_step_24_segments_vs_float64(name, capsys):
     _finish(judge, f"multi {name}", capsys)
     dummy = Buf(n=8, fill=0.0)
     arr = (AdamSeg * 25)(*[AdamSeg(dummy.ptr, dummy.ptr, dummy.ptr, dummy.ptr, 8, 1, 0.0) for _ in range(25)])
-    assert _lib().nsa_adam_multi_step(arr, 25, b1, b2, eps, _st()) == NSA_EBADARG
+    assert _lib().nsa_adam_multi_step(arr, 25, b1, b2, eps, st()) == NSA_EBADARG
     assert not failures, [f["what"] for f in failures]
 
 
@@ -358,9 +355,9 @@ def run_camera_sequence(n, seed, hyper, lr_step, gamma, steps, t0, div, judge, t
             loss.t.fill_(best_losses[i])
         if div:
             rc = lib.nsa_adam_step_scaled(p.ptr, g.ptr, dv.ptr, m.ptr, v.ptr, step.ptr, n, lr, b1, b2, eps, lr_step, gamma,
-                                          loss.ptr if best_losses is not None else None, best.ptr if best_losses is not None else None, _st())
+                                          loss.ptr if best_losses is not None else None, best.ptr if best_losses is not None else None, st())
         else:
-            rc = lib.nsa_adam_step(p.ptr, g.ptr, m.ptr, v.ptr, step.ptr, n, lr, b1, b2, eps, lr_step, gamma, _st())
+            rc = lib.nsa_adam_step(p.ptr, g.ptr, m.ptr, v.ptr, step.ptr, n, lr, b1, b2, eps, lr_step, gamma, st())
         assert rc == NSA_OK
         _intact(tag, p, m, v, g, step, loss, best)
         got = (m.cpu(), v.cpu(), p.cpu())
@@ -406,9 +403,9 @@ def test_camera_adam_step_beyond_256_and_bad_arguments():
     step = Buf(torch.tensor([0.0]))
     before = [x.words.clone() for x in b + [step]]
     a = [x.ptr for x in b] + [step.ptr]
-    assert lib.nsa_adam_step(*a, 257, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, _st()) == NSA_EBADARG      # documented: n <= 256
-    assert lib.nsa_adam_step(*a, 0, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, _st()) == NSA_EBADARG
-    assert lib.nsa_adam_step_scaled(a[0], a[1], None, a[2], a[3], a[4], 7, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, None, None, _st()) == NSA_EBADARG
+    assert lib.nsa_adam_step(*a, 257, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, st()) == NSA_EBADARG      # documented: n <= 256
+    assert lib.nsa_adam_step(*a, 0, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, st()) == NSA_EBADARG
+    assert lib.nsa_adam_step_scaled(a[0], a[1], None, a[2], a[3], a[4], 7, 0.01, 0.9, 0.999, 1e-8, 0, 1.0, None, None, st()) == NSA_EBADARG
     torch.cuda.synchronize()
     for x, w in zip(b + [step], before):
         assert torch.equal(x.words, w)
@@ -456,12 +453,12 @@ def run_track_tail(c, weight, slot7, adam=None):
     extra = []
     if adam is None:
         rc = _lib().nsa_track_tail(d["uv"].ptr, d["K"].ptr, d["cam"].ptr, c["R"], d["g_o"].ptr, d["g_d"].ptr, gc.ptr, 0, weight,
-                                   None, None, None, 0.0, 0.9, 0.999, 1e-8, 0, 1.0, None, None, _st())
+                                   None, None, None, 0.0, 0.9, 0.999, 1e-8, 0, 1.0, None, None, st())
     else:
         m, v, step, loss, best, (b1, b2, eps, lr), lr_step, gamma = adam
         extra = [m, v, step, loss, best]
         rc = _lib().nsa_track_tail(d["uv"].ptr, d["K"].ptr, d["cam"].ptr, c["R"], d["g_o"].ptr, d["g_d"].ptr, gc.ptr, 1, weight,
-                                   m.ptr, v.ptr, step.ptr, lr, b1, b2, eps, lr_step, gamma, loss.ptr, best.ptr, _st())
+                                   m.ptr, v.ptr, step.ptr, lr, b1, b2, eps, lr_step, gamma, loss.ptr, best.ptr, st())
     assert rc == NSA_OK
     _intact("nsa_track_tail", gc, *d.values(), *extra)
     for k in ("uv", "K", "g_o", "g_d") + (("cam",) if adam is None else ()):
@@ -478,11 +475,11 @@ def run_track_finish(c, weight, adam=None):
     a = [d["uv"].ptr, d["K"].ptr, d["cam"].ptr, Rn, S, d["z"].ptr, d["g_x"].ptr, d["g_dir"].ptr, d["ray_loss"].ptr, gc.ptr]
     extra = []
     if adam is None:
-        rc = _lib().nsa_track_finish(*a, 0, weight, None, None, None, 0.0, 0.9, 0.999, 1e-8, 0, 1.0, None, ws.ptr, _st())
+        rc = _lib().nsa_track_finish(*a, 0, weight, None, None, None, 0.0, 0.9, 0.999, 1e-8, 0, 1.0, None, ws.ptr, st())
     else:
         m, v, step, best, (b1, b2, eps, lr), lr_step, gamma = adam
         extra = [m, v, step, best]
-        rc = _lib().nsa_track_finish(*a, 1, weight, m.ptr, v.ptr, step.ptr, lr, b1, b2, eps, lr_step, gamma, best.ptr, ws.ptr, _st())
+        rc = _lib().nsa_track_finish(*a, 1, weight, m.ptr, v.ptr, step.ptr, lr, b1, b2, eps, lr_step, gamma, best.ptr, ws.ptr, st())
     assert rc == NSA_OK
     _intact("nsa_track_finish", gc, ws, *d.values(), *extra)
     return gc.cpu(), d["cam"].cpu(), int(ws.words[ws.lo])
@@ -656,7 +653,7 @@ def test_weight_norm_flat_and_backward_vs_float64(n_layers, capsys):
         total = g_flat.numel()
         arr, bufs = _wn_table(layers)
         flat, norms = Buf(n=total, fill=float("nan")), Buf(n=n_rows, fill=float("nan"))
-        assert lib.nsa_weight_norm_flat(arr, n_layers, flat.ptr, norms.ptr, _st()) == NSA_OK
+        assert lib.nsa_weight_norm_flat(arr, n_layers, flat.ptr, norms.ptr, st()) == NSA_OK
         _intact("nsa_weight_norm_flat", flat, norms, *[x for b in bufs for x in b])
         got = flat.cpu()
         ref, n64 = R.weight_norm_flat(layers)
@@ -668,7 +665,7 @@ def test_weight_norm_flat_and_backward_vs_float64(n_layers, capsys):
         assert bool(torch.isfinite(norms.cpu()).all())
         # backward, from the kernel's own fp32 norms
         gf, gp = Buf(g_flat), Buf(n=total - 1 + n_rows, fill=float("nan"))
-        assert lib.nsa_weight_norm_flat_backward(arr, n_layers, norms.ptr, gf.ptr, gp.ptr, _st()) == NSA_OK
+        assert lib.nsa_weight_norm_flat_backward(arr, n_layers, norms.ptr, gf.ptr, gp.ptr, st()) == NSA_OK
         _intact("nsa_weight_norm_flat_backward", gp, gf, norms, *[x for b in bufs for x in b])
         got = gp.cpu()
         ref = R.weight_norm_flat_backward(layers, g_flat)
@@ -697,8 +694,8 @@ def test_weight_norm_nine_layers_is_refused():
     layers = C.wn_layers(8, 0) + C.wn_layers(1, 1)
     arr, bufs = _wn_table(layers)
     out = Buf(n=8, fill=0.0)
-    assert _lib().nsa_weight_norm_flat(arr, 9, out.ptr, out.ptr, _st()) == NSA_EBADARG
-    assert _lib().nsa_weight_norm_flat_backward(arr, 9, out.ptr, out.ptr, out.ptr, _st()) == NSA_EBADARG
+    assert _lib().nsa_weight_norm_flat(arr, 9, out.ptr, out.ptr, st()) == NSA_EBADARG
+    assert _lib().nsa_weight_norm_flat_backward(arr, 9, out.ptr, out.ptr, out.ptr, st()) == NSA_EBADARG
     _intact("nine layers", out)
 
 
@@ -723,7 +720,7 @@ def test_update_voxels_on_crafted_points_exactly(res):
     want = torch.zeros(res ** 3, device="cuda")
     for what, x in _voxel_sets():
         desc, b = _points_desc(x)
-        assert lib.nsa_update_voxels(ctypes.byref(desc), vox.ptr, res, _st()) == NSA_OK
+        assert lib.nsa_update_voxels(ctypes.byref(desc), vox.ptr, res, st()) == NSA_OK
         _intact(f"nsa_update_voxels res={res} {what}", vox, b)
         idx = R.voxel_index(x, res)
         idx = torch.from_numpy(idx[idx >= 0]).cuda()
@@ -738,12 +735,12 @@ def test_morton_keys_on_crafted_points_exactly():
     for what, x in sets:
         desc, b = _points_desc(x)
         keys = Buf(n=x.shape[0], dtype=torch.int32)
-        assert lib.nsa_morton_keys(ctypes.byref(desc), keys.ptr, _st()) == NSA_OK
+        assert lib.nsa_morton_keys(ctypes.byref(desc), keys.ptr, st()) == NSA_OK
         _intact(f"nsa_morton_keys {what}", keys, b)
         assert np.array_equal(keys.cpu().numpy(), R.morton_key(x)), what
     nan = np.array([[np.nan, -1.0, -1.0], [np.nan, np.nan, np.nan], [-5.0, 7.0, np.nan]], dtype=np.float32)
     desc, b = _points_desc(nan)
     keys = Buf(n=3, dtype=torch.int32)
-    assert lib.nsa_morton_keys(ctypes.byref(desc), keys.ptr, _st()) == NSA_OK
+    assert lib.nsa_morton_keys(ctypes.byref(desc), keys.ptr, st()) == NSA_OK
     torch.cuda.synchronize()
     assert keys.cpu().tolist() == [0, 0, int(R.morton_key(np.array([[-1.0, 1.0, -1.0]], dtype=np.float32))[0])]      # NaN -> cell 0

@@ -13,8 +13,7 @@ import torch
 
 import optim_cases as C
 import optim_ref64 as R
-from test_gemm_float64_gpu import gate
-from test_objective_float64_gpu import gate_larger, report
+from gate64 import gate
 
 F32, F64 = torch.float32, torch.float64
 SCHEDULES = ((0, 1.0), (3, 0.5), (50, 0.95))
@@ -149,7 +148,7 @@ def test_camera_order_passes_on_every_class_and_every_adam_mutant_is_caught(caps
         args = (case["p0"], case["g"], case["m0"], case["v0"], t, lr, b1, b2, eps, lr_step, gamma)
         r64, y_t, y_c = R.adam_step(*args), R.adam_step(*args, dtype=F32), R.adam_step(*args, dtype=F32, order="camera")
         tag = f"{name} t={t} StepLR({lr_step},{gamma})"
-        honest = C.AdamJudge(lambda *a: gate(*a[:3], a[3], a[5], a[6], a[7]), report, failures)      # one yardstick: the table order
+        honest = C.AdamJudge(failures, table_order_only=True)
         honest.add(tag + " camera order", case, y_c, r64, y_t, y_t)
         honest.finish(tag + " camera order")
         for mutant in ADAM_MUTANTS:
@@ -157,7 +156,7 @@ def test_camera_order_passes_on_every_class_and_every_adam_mutant_is_caught(caps
                 continue                           # (1 - b^0 = 0: not a number, nothing to judge)
             got = adam_mutant(mutant, case, t, hyper, lr_step, gamma)
             before = set(caught[mutant])
-            j = C.AdamJudge(gate_larger, report, [], caught[mutant])
+            j = C.AdamJudge([], caught[mutant])
             j.add(tag + " " + mutant, case, got, r64, y_t, y_c)
             j.finish(tag + " " + mutant)
             if name == "project":
@@ -226,10 +225,10 @@ def test_weight_norm_backward_mutant_without_the_projection_is_caught(capsys):
     y_b = R.weight_norm_flat_backward(layers, g_flat, dtype=F32, kernel_order=True)
     keep = torch.ones(norms.shape[0], dtype=torch.bool)
     fails = []
-    honest = _wn_rows(layers, g_flat, y_b, ref, y_a, y_a, norms)
-    assert gate_larger("weight norm backward, kernel order for the kernel", *honest, keep, fails), fails
+    two = lambda what, got, r, ya, yb, norm, failures: gate(what, got, r, ya, norm, keep, failures, kernel_order=yb)
+    assert two("weight norm backward, kernel order for the kernel", *_wn_rows(layers, g_flat, y_b, ref, y_a, y_a, norms), fails), fails
     bad = R.weight_norm_flat_backward(layers, g_flat, dtype=F32, drop_projection=True)
-    assert not gate_larger("weight norm backward without v s / |v|^3", *_wn_rows(layers, g_flat, bad, ref, y_a, y_b, norms), keep, [])
+    assert not two("weight norm backward without v s / |v|^3", *_wn_rows(layers, g_flat, bad, ref, y_a, y_b, norms), [])
 
 
 def test_track_tail_reference_and_the_mutant_with_slot_7_unscaled(capsys):

@@ -30,9 +30,10 @@ import torch
 
 import bf16_cases as C
 import bf16_gate as G
+import gemm_cases
 import ref64
 from oracle import render_ref as R
-from test_gemm_float64_gpu import perturbed
+from mlp_calls import perturbed
 
 
 @pytest.fixture(scope="module")
@@ -82,14 +83,14 @@ def _hold_to_oracle(what, theirs, r, k, keep=None):
 def test_quant_sdf_networks_equal_the_bf16_oracle_in_fp32(model, which):
     params, cfg = model
     n = 1500
-    x = C._cube_points(n, 3)
+    x = gemm_cases.cube_points(n, 3)
     nets, prefix = (which,), ref64.NETS[which]
     xs = x.clone()
     so, fo, go = R._net_outputs(params, prefix, getattr(cfg, which), xs, True)
     r = C.refs(C.sdf_forward_case(params, cfg, x, nets))
     for k, o in zip(("sdf", "grad", "feat"), (so[:, 0], go, fo)):
         _hold_to_oracle(f"{which} {k}", o, r, k)
-    cot = (C._cot(n, 4, ()), C._cot(n, 5, (64,)), C._cot(n, 6, (3,)))
+    cot = (gemm_cases.cot(n, 4, ()), gemm_cases.cot(n, 5, (64,)), gemm_cases.cot(n, 6, (3,)))
     for use in ((0, 1, 2), (0,), (1,), (2,)):
         g = [c if i in use else None for i, c in enumerate(cot)]
         (theirs,) = torch.autograd.grad(sum((c * y).sum() for c, y in zip(g, (so[:, 0], fo, go)) if c is not None), xs, retain_graph=True)
@@ -105,7 +106,7 @@ def test_quant_colour_network_equals_the_bf16_oracle_in_fp32(model, precision, g
     n = 1500
     i = C.inputs(params, cfg, n)
     x, d, normals, feat = i.x, i.d, i.normals, i.feat
-    g_rgb = C._cot(n, 7, (3,))
+    g_rgb = gemm_cases.cot(n, 7, (3,))
     ins = [t.clone().requires_grad_(True) for t in (x, normals, d, feat)]
     rgb_o = R.colour_net(params, cq, *ins, color_stage="highfreq" if grid_grad else "base")
     _hold_to_oracle("rgb", rgb_o, C.refs(C.colour_forward_case(params, cfg, x, d, normals, feat)), "rgb")

@@ -1,7 +1,7 @@
 """The per-ray importance sampler k_sample_rays against float64 (tests/sampler_ref64.py), sample by sample, through the C ABI
 (nsa_sample_rays called directly: no network, no model).
 
-The method is tests/test_objective_float64_gpu.py's (gate, gate_larger, _per_point and Pool are imported from there), in TWO classes,
+The method is tests/test_objective_float64_gpu.py's (the gate and its Pool are tests/gate64.py), in TWO classes,
 because the reference's own algorithm is discontinuous in z where a chosen bin sits on the 1e-5 floor (its normalised mass is a hair
 under the den < 1e-5 switch, so an fp32 and a float64 evaluation legitimately take different branches there) and at u = 1 (the last cdf
 entry rounds to 1 or to 1 + 2^-23); it is continuous in u everywhere:
@@ -27,8 +27,8 @@ import torch
 
 import sampler_cases as C
 import sampler_ref64 as S
-from test_gemm_float64_gpu import gate, _per_point        # noqa: F401  (the gate's parts; Pool.judge calls them)
-from test_objective_float64_gpu import Pool, gate_larger, _st, _p, _dev, _nan        # noqa: F401
+from devcall import dev, ptr, st
+from gate64 import Pool
 
 pytestmark = pytest.mark.gpu
 GUARD, GUARD_WORD, NAN_WORD = 64, 0x5A5A5A5A, 0x7FC00000
@@ -51,8 +51,8 @@ class DevCase:
         take = (lambda t: t) if rays is None else (lambda t: t[rays].contiguous())
         self.cs = cs
         self.R = cs["R"] if rays is None else len(rays)
-        self.t = {k: _dev(take(cs[k])) for k in ("rays_o", "rays_d", "z", "sdf", "far")}
-        self.voxels, self.u = _dev(cs["voxels"]), _dev(S.u_lin(cs["N"]))
+        self.t = {k: dev(take(cs[k])) for k in ("rays_o", "rays_d", "z", "sdf", "far")}
+        self.voxels, self.u = dev(cs["voxels"]), dev(S.u_lin(cs["N"]))
         self.extra = None if cs["extra_idx"] is None else cs["extra_idx"].cuda()
         self.eik = take(cs["eik_idx"]).cuda()
 
@@ -65,9 +65,9 @@ class DevCase:
         S_ = cs["S"]
         zb, zv = _guarded(R * S_)
         eb, ze = _guarded(R)
-        rc = lib.nsa_sample_rays(_p(t["rays_o"]), _p(t["rays_d"]), _p(t["z"]), _p(t["sdf"]), _p(t["far"]), _p(self.voxels), a["voxel_res"],
-                                 R, a["E"], a["N"], _p(self.u), _p(self.extra), a["n_extra"], cs["near"],
-                                 _p(self.eik) if with_eik else None, _p(zv), _p(ze) if with_eik else None, _st())
+        rc = lib.nsa_sample_rays(ptr(t["rays_o"]), ptr(t["rays_d"]), ptr(t["z"]), ptr(t["sdf"]), ptr(t["far"]), ptr(self.voxels), a["voxel_res"],
+                                 R, a["E"], a["N"], ptr(self.u), ptr(self.extra), a["n_extra"], cs["near"],
+                                 ptr(self.eik) if with_eik else None, ptr(zv), ptr(ze) if with_eik else None, st())
         torch.cuda.synchronize()
         return rc, zv.cpu().reshape(R, S_), (ze.cpu() if with_eik else None), _guards_ok(zb) and _guards_ok(eb)
 

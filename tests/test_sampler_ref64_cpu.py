@@ -12,8 +12,7 @@ import torch
 import sampler_cases as C
 import sampler_ref64 as S
 from helpers import load, tt, params_of, oracle_config, draws_of
-from test_gemm_float64_gpu import gate
-from test_objective_float64_gpu import Pool
+from gate64 import Pool
 
 F32 = torch.float32
 GOLDENS = ["full_tracking", "full_tracking_poisson", "full_mapping", "full_vis_eval", "full_tracking_rw", "full_mapping_rw",

@@ -1,7 +1,7 @@
 """The keyframe re-projection kernels (csrc/warp_terms.hip, C ABI section 5: nsa_patch_warp_forward / _backward, nsa_flow_forward /
 _backward, nsa_masked_l1 and the workspace functions) against float64 (tests/warp_ref64.py), row by row, through the C ABI.
 
-The method is tests/test_gemm_float64_gpu.py's, and so is the gate (its gate / gate_larger, applied by tests/test_objective_float64_gpu.py's Pool):
+The method is tests/test_gemm_float64_gpu.py's, and the gate is tests/gate64.py (its Pool, with a second yardstick where there is one):
   * e_k = |kernel - float64|, e_32 = |fp32 mode of the same restatement - float64| (the yardstick; tests/test_warp_ref64_cpu.py holds
     that mode to model/warp.py and to the golden, and bounds it on these very inputs),
   * per row, divided by the row's norm: `sampled` rows (target, source, pixel) and `flow` rows (edge, pixel) by max(|float64 row|, 1);
@@ -14,7 +14,7 @@ Kernel order.  g_pose and g_w2c are sums over all threads of an image; the kerne
 butterfly over the 64 lanes of a wave, then k_pose_finish's 21 strided groups of wave partials, then the groups in turn -- where
 fp32 autograd adds them in torch's order (a matmul backward and a blocked sum).  Both are valid fp32 orders of the same sum, so
 these two quantities have a second yardstick in the kernel's order (warp_ref64.pose_grads_kernel_order) and are gated against the
-larger of the two (gate_larger).  sampled, flow and g_depth are per-thread fixed-order expressions and have the one yardstick.
+larger of the two (gate64.gate with kernel_order).  sampled, flow and g_depth are per-thread fixed-order expressions and have the one yardstick.
 
 Inputs: tests/warp_cases.py.  Bitwise: gt_rgb; mask and flat outside the exclusions; everything on a second run.  Left out, counted,
 printed and capped (warp_cases.exclusions / check_caps, derived from the restatement alone, asserted on the CPU too): g_depth rows
@@ -37,29 +37,14 @@ import torch
 
 import warp_cases as C
 import warp_ref64 as R
-from test_objective_float64_gpu import Pool          # (Pool.judge applies test_gemm_float64_gpu.gate, or gate_larger with a second yardstick)
+from devcall import dev, nan, ptr, st
+from gate64 import Pool
 
 pytestmark = pytest.mark.gpu
 F32, F64 = torch.float32, torch.float64
 NSA_OK, NSA_EBADARG = 0, 4
 GUARD = 4096                     # floats behind every workspace
 SENTINEL = -7.25e22
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _dev(t, dtype=F32):
-    return None if t is None else t.detach().to("cuda", dtype).contiguous()
-
-
-def _nan(*shape):
-    return torch.full(shape, float("nan"), device="cuda")
 
 
 def waves(per_image):
@@ -102,11 +87,11 @@ class DevWarp:
     def __init__(self, c):
         from nicer_slam_amd._native import WarpDesc
         self.c = c
-        self.t = {k: _dev(c[k]) for k in ("uv", "pose", "w2c", "K", "depth", "images", "depths")}
-        self.t["frame_index"] = _dev(c["frame_index"], torch.int32)
+        self.t = {k: dev(c[k]) for k in ("uv", "pose", "w2c", "K", "depth", "images", "depths")}
+        self.t["frame_index"] = dev(c["frame_index"], torch.int32)
         t = self.t
-        self.desc = WarpDesc(c["b"], c["n"], c["H"], c["W"], _p(t["uv"]), _p(t["pose"]), _p(t["w2c"]), _p(t["K"]), _p(t["depth"]),
-                             _p(t["images"]), _p(t["depths"]), _p(t["frame_index"]))
+        self.desc = WarpDesc(c["b"], c["n"], c["H"], c["W"], ptr(t["uv"]), ptr(t["pose"]), ptr(t["w2c"]), ptr(t["K"]), ptr(t["depth"]),
+                             ptr(t["images"]), ptr(t["depths"]), ptr(t["frame_index"]))
 
     def ref(self):
         return ctypes.byref(self.desc)
@@ -117,10 +102,10 @@ def k_warp_forward(dw):
     c = dw.c
     b, n, patch = c["b"], c["n"], c["patch"]
     p2 = patch * patch
-    sampled, gt_rgb = _nan(b, b, n, p2, 3), _nan(b, b, n, p2, 3)
+    sampled, gt_rgb = nan(b, b, n, p2, 3), nan(b, b, n, p2, 3)
     mask = torch.full((b, b, n, p2), 0xCC, device="cuda", dtype=torch.uint8)
     flat = torch.full((b, n), 0xCC, device="cuda", dtype=torch.uint8) if patch > 1 else None
-    check(lib.nsa_patch_warp_forward(dw.ref(), patch, _p(sampled), _p(mask), _p(gt_rgb), _p(flat), _st()))
+    check(lib.nsa_patch_warp_forward(dw.ref(), patch, ptr(sampled), ptr(mask), ptr(gt_rgb), ptr(flat), st()))
     torch.cuda.synchronize()
     return sampled.cpu(), mask.cpu(), gt_rgb.cpu(), None if flat is None else flat.cpu()
 
@@ -132,10 +117,10 @@ def k_warp_backward(dw, g_sampled, want_pose):
     size = patch_workspace(b, n, patch, want_pose)
     assert int(lib.nsa_patch_warp_workspace(b, n, patch, int(want_pose))) == size, "nsa_patch_warp_workspace"
     ws = Guarded(size)
-    g = _dev(g_sampled)
-    g_depth = _nan(b, n)
-    g_pose, g_w2c = (_nan(b, 4, 4), _nan(b, 4, 4)) if want_pose else (None, None)
-    check(lib.nsa_patch_warp_backward(dw.ref(), patch, _p(g), _p(g_depth), _p(g_pose), _p(g_w2c), ws.ptr(), _st()))
+    g = dev(g_sampled)
+    g_depth = nan(b, n)
+    g_pose, g_w2c = (nan(b, 4, 4), nan(b, 4, 4)) if want_pose else (None, None)
+    check(lib.nsa_patch_warp_backward(dw.ref(), patch, ptr(g), ptr(g_depth), ptr(g_pose), ptr(g_w2c), ws.ptr(), st()))
     torch.cuda.synchronize()
     assert ws.intact(), f"nsa_patch_warp_backward wrote past its {size} workspace floats"
     return g_depth.cpu(), None if g_pose is None else g_pose.cpu(), None if g_w2c is None else g_w2c.cpu()
@@ -144,8 +129,8 @@ def k_warp_backward(dw, g_sampled, want_pose):
 def k_flow_forward(dw, ii, jj):
     from nicer_slam_amd._native import lib, check
     ne, n = ii.shape[0], dw.c["n"]
-    flow = _nan(ne, n, 2)
-    check(lib.nsa_flow_forward(dw.ref(), _p(ii), _p(jj), ne, _p(flow), _st()))
+    flow = nan(ne, n, 2)
+    check(lib.nsa_flow_forward(dw.ref(), ptr(ii), ptr(jj), ne, ptr(flow), st()))
     torch.cuda.synchronize()
     return flow.cpu()
 
@@ -157,11 +142,11 @@ def k_flow_backward(dw, ii, jj, g_flow, want_pose):
     size = flow_workspace(b, n, ne, want_pose)
     assert int(lib.nsa_flow_workspace(b, n, ne, int(want_pose))) == size, "nsa_flow_workspace"
     ws = Guarded(size)
-    g = _dev(g_flow)
-    g_depth = _nan(b, n)
-    g_pose, g_w2c = (_nan(b, 4, 4), _nan(b, 4, 4)) if want_pose else (None, None)
-    check(lib.nsa_flow_backward(dw.ref(), _p(ii) if ne else None, _p(jj) if ne else None, ne, _p(g) if ne else None, _p(g_depth),
-                                _p(g_pose), _p(g_w2c), ws.ptr(), _st()))
+    g = dev(g_flow)
+    g_depth = nan(b, n)
+    g_pose, g_w2c = (nan(b, 4, 4), nan(b, 4, 4)) if want_pose else (None, None)
+    check(lib.nsa_flow_backward(dw.ref(), ptr(ii) if ne else None, ptr(jj) if ne else None, ne, ptr(g) if ne else None, ptr(g_depth),
+                                ptr(g_pose), ptr(g_w2c), ws.ptr(), st()))
     torch.cuda.synchronize()
     assert ws.intact(), f"nsa_flow_backward wrote past its {size} workspace floats"
     return g_depth.cpu(), None if g_pose is None else g_pose.cpu(), None if g_w2c is None else g_w2c.cpu()
@@ -278,7 +263,7 @@ def flow_result(name):
     o64, o32 = C.evaluate_flow(c, F64), C.evaluate_flow(c, F32)
     g = C.g_flow_of(c, c["edges"])
     dw = DevWarp(c)
-    ii, jj = _dev(c["idii"], torch.int64), _dev(c["idjj"], torch.int64)
+    ii, jj = dev(c["idii"], torch.int64), dev(c["idjj"], torch.int64)
     fwd, bwd = k_flow_forward(dw, ii, jj), k_flow_backward(dw, ii, jj, g, True)
     again = (k_flow_forward(dw, ii, jj),) + k_flow_backward(dw, ii, jj, g, True)
     no_pose = k_flow_backward(dw, ii, jj, g, False)
@@ -364,8 +349,8 @@ def test_flow_without_edges_writes_nothing_forward_and_zeros_backward():
     from nicer_slam_amd._native import lib
     c = C.flow_case("b3 n255 special 5")
     dw = DevWarp(c)
-    flow = _nan(4)
-    assert lib.nsa_flow_forward(dw.ref(), None, None, 0, _p(flow), _st()) == NSA_OK
+    flow = nan(4)
+    assert lib.nsa_flow_forward(dw.ref(), None, None, 0, ptr(flow), st()) == NSA_OK
     torch.cuda.synchronize()
     assert bool(torch.isnan(flow).all())
     none = torch.zeros(0, dtype=torch.int64, device="cuda")
@@ -380,13 +365,13 @@ def k_masked_l1(pred, target, mask, ch, with_grad=True, misalign=False):
     size = l1_workspace(items)
     assert int(lib.nsa_masked_l1_workspace(items)) == size, "nsa_masked_l1_workspace"
     ws = Guarded(size + 2)                                                   # (+ 2: room to hand over a pointer off by one float)
-    p, t = _dev(pred.reshape(-1)) if items else _nan(4), _dev(target.reshape(-1)) if items else _nan(4)
-    m = None if mask is None else _dev(mask, torch.uint8)
-    loss = _nan(1)
+    p, t = dev(pred.reshape(-1)) if items else nan(4), dev(target.reshape(-1)) if items else nan(4)
+    m = None if mask is None else dev(mask, torch.uint8)
+    loss = nan(1)
     g = torch.full((max(items * ch, 1),), SENTINEL, device="cuda") if with_grad else None
     assert ws.t.data_ptr() % 8 == 0
-    rc = lib.nsa_masked_l1(_p(p), _p(t), _p(m) if (m is not None and items) else None, items, ch, _p(loss), _p(g),
-                           ws.t.data_ptr() + (4 if misalign else 0), _st())
+    rc = lib.nsa_masked_l1(ptr(p), ptr(t), ptr(m) if (m is not None and items) else None, items, ch, ptr(loss), ptr(g),
+                           ws.t.data_ptr() + (4 if misalign else 0), st())
     torch.cuda.synchronize()
     assert bool((ws.t[size + 2:] == SENTINEL).all()) and (misalign or bool((ws.t[size:] == SENTINEL).all())), "nsa_masked_l1 wrote past its workspace"
     return rc, loss.cpu()[0], None if g is None else g.cpu(), ws
@@ -430,38 +415,38 @@ def test_every_bad_argument_is_refused_without_a_launch():
     dw = DevWarp(c)
     b, n, patch = c["b"], c["n"], c["patch"]
     p2 = patch * patch
-    out = dict(sampled=_nan(b, b, n, p2, 3), gt_rgb=_nan(b, b, n, p2, 3), g_depth=_nan(b, n), g_pose=_nan(b, 4, 4), g_w2c=_nan(b, 4, 4),
-               flow=_nan(5, n, 2), loss=_nan(1))
+    out = dict(sampled=nan(b, b, n, p2, 3), gt_rgb=nan(b, b, n, p2, 3), g_depth=nan(b, n), g_pose=nan(b, 4, 4), g_w2c=nan(b, 4, 4),
+               flow=nan(5, n, 2), loss=nan(1))
     mask = torch.full((b, b, n, p2), 0xCC, device="cuda", dtype=torch.uint8)
     flat = torch.full((b, n), 0xCC, device="cuda", dtype=torch.uint8)
-    g = _dev(C.g_sampled_of(c))
+    g = dev(C.g_sampled_of(c))
     ws = Guarded(patch_workspace(b, n, patch, True))
     t = dw.t
 
     def desc(**change):
         f = dict(b=b, n=n, H=c["H"], W=c["W"], **{k: t[k] for k in ("uv", "pose", "w2c", "K", "depth", "images", "depths", "frame_index")})
         f.update(change)
-        return ctypes.byref(WarpDesc(f["b"], f["n"], f["H"], f["W"], *(_p(f[k]) for k in ("uv", "pose", "w2c", "K", "depth", "images",
+        return ctypes.byref(WarpDesc(f["b"], f["n"], f["H"], f["W"], *(ptr(f[k]) for k in ("uv", "pose", "w2c", "K", "depth", "images",
                                                                                           "depths", "frame_index"))))
 
     VALID = object()
     # what every entry point that takes the descriptor refuses (warp_ok): no descriptor, b = 0, n = 0, a missing uv, pose, w2c, K, depth
     bad_desc = [None, desc(b=0), desc(n=0)] + [desc(**{k: None}) for k in ("uv", "pose", "w2c", "K", "depth")]
-    ii, jj = _dev(torch.tensor([0, 1, 2, 0, 1]), torch.int64), _dev(torch.tensor([1, 2, 0, 2, 0]), torch.int64)
-    gf = _dev(torch.ones(5, n, 2))
-    gp, gw = _p(out["g_pose"]), _p(out["g_w2c"])
+    ii, jj = dev(torch.tensor([0, 1, 2, 0, 1]), torch.int64), dev(torch.tensor([1, 2, 0, 2, 0]), torch.int64)
+    gf = dev(torch.ones(5, n, 2))
+    gp, gw = ptr(out["g_pose"]), ptr(out["g_w2c"])
 
-    def fwd(d=VALID, ps=patch, sampled=_p(out["sampled"]), m=_p(mask), gt=_p(out["gt_rgb"]), fl=_p(flat)):
-        return lib.nsa_patch_warp_forward(desc() if d is VALID else d, ps, sampled, m, gt, fl, _st())
+    def fwd(d=VALID, ps=patch, sampled=ptr(out["sampled"]), m=ptr(mask), gt=ptr(out["gt_rgb"]), fl=ptr(flat)):
+        return lib.nsa_patch_warp_forward(desc() if d is VALID else d, ps, sampled, m, gt, fl, st())
 
-    def bwd(d=VALID, ps=patch, gs=_p(g), gd=_p(out["g_depth"]), gp=gp, gw=gw, w=ws.ptr()):
-        return lib.nsa_patch_warp_backward(desc() if d is VALID else d, ps, gs, gd, gp, gw, w, _st())
+    def bwd(d=VALID, ps=patch, gs=ptr(g), gd=ptr(out["g_depth"]), gp=gp, gw=gw, w=ws.ptr()):
+        return lib.nsa_patch_warp_backward(desc() if d is VALID else d, ps, gs, gd, gp, gw, w, st())
 
-    def ffwd(d=VALID, i=_p(ii), j=_p(jj), fl=_p(out["flow"])):
-        return lib.nsa_flow_forward(desc() if d is VALID else d, i, j, 5, fl, _st())
+    def ffwd(d=VALID, i=ptr(ii), j=ptr(jj), fl=ptr(out["flow"])):
+        return lib.nsa_flow_forward(desc() if d is VALID else d, i, j, 5, fl, st())
 
-    def fbwd(d=VALID, i=_p(ii), j=_p(jj), gfl=_p(gf), gd=_p(out["g_depth"]), gp=gp, gw=gw, w=ws.ptr()):
-        return lib.nsa_flow_backward(desc() if d is VALID else d, i, j, 5, gfl, gd, gp, gw, w, _st())
+    def fbwd(d=VALID, i=ptr(ii), j=ptr(jj), gfl=ptr(gf), gd=ptr(out["g_depth"]), gp=gp, gw=gw, w=ws.ptr()):
+        return lib.nsa_flow_backward(desc() if d is VALID else d, i, j, 5, gfl, gd, gp, gw, w, st())
 
     rcs = {}
     for k, d in enumerate(bad_desc):
@@ -487,7 +472,7 @@ def test_every_bad_argument_is_refused_without_a_launch():
     rc, loss, g1, l1ws = k_masked_l1(pred, target, m, 3, misalign=True)
     assert rc == NSA_EBADARG and bool(torch.isnan(loss)) and bool((g1 == SENTINEL).all()) and bool((l1ws.t == SENTINEL).all())
     assert ws.t.data_ptr() % 8 == 0
-    l1 = lambda pr=_p(g), ta=_p(g), ch=3, lo=_p(out["loss"]), w=ws.ptr(): lib.nsa_masked_l1(pr, ta, None, 10, ch, lo, None, w, _st())
+    l1 = lambda pr=ptr(g), ta=ptr(g), ch=3, lo=ptr(out["loss"]), w=ws.ptr(): lib.nsa_masked_l1(pr, ta, None, 10, ch, lo, None, w, st())
     rcs.update({"masked_l1: no loss": l1(lo=None), "masked_l1: no workspace": l1(w=None), "masked_l1: no channels": l1(ch=0),
                 "masked_l1: no pred": l1(pr=None), "masked_l1: no target": l1(ta=None)})
     torch.cuda.synchronize()
