@@ -13,48 +13,20 @@ import os
 import re
 import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from benchlib import ROOT, median, median_ms, positionals, time_host, write_results
 from nicer_slam_amd import cloud_normals as C, mesh_eval as E
 from nicer_slam_amd._native import check, lib
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-POINTS = int(sys.argv[2]) if len(sys.argv) > 2 else 200000
 KS = (1, 8, 30, 64)
 LDS_PER_CU = 160 * 1024
 
 
-def timed(fn, reps=REPS):
-    """median ms by device events"""
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
-
-
-def walled(fn, reps=REPS):
-    """median ms by the host clock; fn ends synchronised"""
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append(1e3 * (time.perf_counter() - t0))
-    return float(np.median(ms))
+def parse_args(argv):
+    return positionals(argv, reps=(int, 7), points=(int, 200000))
 
 
 def box(lo, hi):
@@ -91,7 +63,9 @@ def capacities():
     return out
 
 
-def case(name, pts, out):
+def case(name, pts, out, reps):
+    timed = lambda fn: median_ms(fn, reps)                           # median ms by device events
+    walled = lambda fn: median(time_host(fn, reps))                  # median ms by the host clock
     n = pts.shape[0]
     dev = pts.device
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -136,22 +110,21 @@ def case(name, pts, out):
     print(json.dumps({name: r}, indent=1), flush=True)
 
 
-def main():
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_cloud_normals: needs a GPU")
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
     v, f = room()
-    samples, _ = E.sample_surface(v, f, POINTS, 1)
-    case("room", samples.contiguous(), out)
+    samples, _ = E.sample_surface(v, f, a.points, 1)
+    case("room", samples.contiguous(), out, a.reps)
     g = torch.Generator(device="cuda").manual_seed(1)
-    uniform = torch.rand(POINTS, 3, device="cuda", generator=g) * torch.tensor([4.0, 3.0, 2.5], device="cuda")
-    case("uniform", uniform.contiguous(), out)
+    uniform = torch.rand(a.points, 3, device="cuda", generator=g) * torch.tensor([4.0, 3.0, 2.5], device="cuda")
+    case("uniform", uniform.contiguous(), out, a.reps)
     out["k_nn_query_k list capacities"] = capacities()
     print(json.dumps(out["k_nn_query_k list capacities"], indent=1), flush=True)
-    if POINTS == 200000:
-        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, "profiles", "cloud_normals_bench.json"), "w") as fh:
-            fh.write(json.dumps(out, indent=1) + "\n")
+    if a.points == 200000:                                        # (every row was printed as it was made)
+        write_results(out, "cloud_normals_bench.json", echo=False)
 
 
 if __name__ == "__main__":

@@ -5,38 +5,23 @@ in the window) with the bytes they have to move over the time, against the rate 
 run, and the float64 torch restatement of the same rule (world-coordinate composition, grid_sample) on the same device for context.
 Frames are resident on the device; device events around CALLS back-to-back calls, warm-up first, median of REPS.  Needs a GPU; there is no fallback.
 usage: python tools/bench_flow_cues.py [reps=7] [out.json]"""
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from benchlib import median_min_max, positionals, time_events, write_results
 from nicer_slam_amd import flow_cues as fc
 from nicer_slam_amd._native import check, lib
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 CALLS = 20
 H, W = 680, 1200
 K4 = (600.0, 600.0, 599.5, 339.5)
 
 
-def timed(fn, calls=CALLS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(REPS):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1) / calls)
-    return {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms))}
+def parse_args(argv):
+    return positionals(argv, reps=(int, 7), out=(str, None))
 
 
 def scene(n):
@@ -109,7 +94,13 @@ def torch_pipeline(depth, c2w, pairs, near=1e-3, alpha=0.01, beta=0.5):
     return torch.stack(flows), torch.stack(occs).to(torch.uint8)
 
 
-def main():
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    REPS = args.reps
+
+    def timed(fn, calls=CALLS):
+        return dict(zip(("median_ms", "min_ms", "max_ms"), median_min_max(time_events(fn, REPS, calls))))
+
     pairs = [(i // 10, j // 10) for i, j in fc.pair_list(2000)[:32]]
     n = max(max(p) for p in pairs) + 1
     c2w, depth = scene(n)
@@ -159,11 +150,7 @@ def main():
     t["share of the copy's rate"] = t["bytes_per_s"] / copy_bw
     out["kernel nsa_flowcue_consistency, unordered pairs"] = t
 
-    print(json.dumps(out, indent=1))
-    if len(sys.argv) > 2:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[2])), exist_ok=True)
-        with open(sys.argv[2], "w") as fh:
-            json.dump(out, fh, indent=1)
+    write_results(out, path=args.out)
 
 
 if __name__ == "__main__":

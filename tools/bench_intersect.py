@@ -6,41 +6,23 @@ sort; candidates per face and the share of each stage.  The comparison is this u
 version and no runnable reference program, so no time is gated.  Results go to profiles/intersect_bench.json.
 usage: python tools/bench_intersect.py [reps=20] [resolution=128] [tsdf voxels=256] [tsdf frames=100] [brute faces=8192]"""
 import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np
 import torch
 
+from benchlib import mc_sphere, median_ms, mesh_positionals, tsdf_mesh, write_results
 from nicer_slam_amd import mesh_fill, mesh_intersect as M
 from nicer_slam_amd._native import check, lib
 from nicer_slam_amd.mesh_eval import TriIndex
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-BRUTE_F = int(sys.argv[5]) if len(sys.argv) > 5 else 8192
+
+def parse_args(argv):
+    return mesh_positionals(argv, reps=20, resolution=128, brute_faces=(int, 8192))
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
-
-
-def passes(ix, brute=False):
+def passes(ix, reps, brute=False):
     """ms of the count and the emit entry points on their own, and the totals"""
+    timed = lambda fn: median_ms(fn, reps)
     dev, F = ix.device, ix.F
     s = torch.cuda.current_stream(dev).cuda_stream
     buf, _ = ix._ray_tree()
@@ -59,7 +41,7 @@ def passes(ix, brute=False):
     return out
 
 
-def case(name, mesh, out):
+def case(name, mesh, out, reps):
     v, f = mesh["verts"].contiguous(), mesh["faces"].contiguous()
     r = {"V": int(v.shape[0]), "F": int(f.shape[0])}
 
@@ -67,10 +49,10 @@ def case(name, mesh, out):
         ix = TriIndex(v, f)
         ix._ray_tree()
         return ix
-    r["index and tree build ms"] = timed(build, max(3, REPS // 4))
+    r["index and tree build ms"] = median_ms(build, max(3, reps // 4))
     ix = build()
-    r.update(passes(ix))
-    r["whole call ms (read back, sort, flags)"] = timed(lambda: ix.self_intersections())
+    r.update(passes(ix, reps))
+    r["whole call ms (read back, sort, flags)"] = median_ms(lambda: ix.self_intersections(), reps)
     rep = ix.self_intersections(return_report=True)[3]
     r["report"] = rep
     r["candidates per face"] = rep["n_candidates"] / max(1, rep["n_faces"])
@@ -81,23 +63,19 @@ def case(name, mesh, out):
     return ix
 
 
-def main():
-    from bench_raycast import mc_sphere
-    import bench_mesh_clean
-    out = {"reps": REPS}
-    sphere = mc_sphere(RES)
-    case(f"marching-cubes sphere {RES}^3", sphere, out)
-    small = TriIndex(sphere["verts"].contiguous(), sphere["faces"][:BRUTE_F].contiguous())
-    tree, brute = passes(small), passes(small, brute=True)
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"reps": a.reps}
+    sphere = mc_sphere(a.resolution)
+    case(f"marching-cubes sphere {a.resolution}^3", sphere, out, a.reps)
+    small = TriIndex(sphere["verts"].contiguous(), sphere["faces"][:a.brute_faces].contiguous())
+    tree, brute = passes(small, a.reps), passes(small, a.reps, brute=True)
     t, b = tree["count pass ms"] + tree["emit pass ms"], brute["count pass ms"] + brute["emit pass ms"]
     out[f"first {small.F} faces of the sphere"] = {"tree": tree, "brute": brute, "brute / tree": b / t}
     print("brute force", json.dumps(out[f"first {small.F} faces of the sphere"]))
-    room = mesh_fill.fill_holes(bench_mesh_clean.tsdf_mesh(), method="auto", normals="none")
-    case("tsdf room, holes filled (method auto)", room, out)
-    path = os.path.join(ROOT, "profiles", "intersect_bench.json")
-    with open(path, "w") as fh:
-        json.dump(out, fh, indent=1)
-    print("->", path)
+    room = mesh_fill.fill_holes(tsdf_mesh(a.voxels, a.frames), method="auto", normals="none")
+    case("tsdf room, holes filled (method auto)", room, out, a.reps)
+    print("->", write_results(out, "intersect_bench.json", echo=False))    # (every row was printed as it was made)
 
 
 if __name__ == "__main__":

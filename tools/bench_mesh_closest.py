@@ -9,41 +9,22 @@ exact sum on the first 20000 of each, and mesh_sdf_grid(sign="winding") beside t
 `rocprofv3 --kernel-trace --stats` run of this script.  Baseline: a chunked torch float64 brute force on the same GPU at a size it
 finishes in a few seconds (queries x faces given below), compared against the index on the same inputs.
 usage: python tools/bench_mesh_closest.py [reps=5] [resolution=512] [out=profiles/mesh_closest_bench.json] [legs=all|winding]"""
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_eval as M
-
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "mesh_closest_bench.json")
-LEGS = sys.argv[4] if len(sys.argv) > 4 else "all"
+from benchlib import median_ms, model_mesh, positionals, write_results
+from nicer_slam_amd import mesh_eval as M
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return positionals(argv, reps=(int, 5), resolution=(int, 512), out=(str, None),      # out: None is profiles/mesh_closest_bench.json
+                       legs=(str, "all"))
 
 
-def query_case(name, ix, q, out):
-    out[name + " query ms"] = timed(lambda: ix.query(q))
+def query_case(name, ix, q, out, reps):
+    out[name + " query ms"] = median_ms(lambda: ix.query(q), reps)
     dist, _, _, n = ix.query(q, counts=True)
     n = n.double()
     out[name + " faces evaluated/query"] = {"mean": float(n.mean()), "median": float(n.median()), "max": int(n.max())}
@@ -64,8 +45,8 @@ def walked(ix, face, feature):
     return torch.where((feature > 0) & (face >= 0), n, torch.zeros_like(n)).double()
 
 
-def signed_case(name, ix, q, out):
-    out[name + " signed query ms"] = timed(lambda: ix.signed_query(q))
+def signed_case(name, ix, q, out, reps):
+    out[name + " signed query ms"] = median_ms(lambda: ix.signed_query(q), reps)
     dist, face, _, feature = ix.signed_query(q)
     n = walked(ix, face, feature)
     out[name + " incident faces walked/query"] = {"mean": float(n.mean()), "max": int(n.max())}
@@ -75,7 +56,8 @@ def signed_case(name, ix, q, out):
                                                         float(((feature == 3) | (feature == 5) | (feature == 6)).double().mean())]
 
 
-def sdf_rows(ix, surf, near, cube, out):
+def sdf_rows(ix, surf, near, cube, out, reps):
+    timed = lambda fn, n=reps: median_ms(fn, n)
     from nicer_slam_amd import mesh_sdf
     out["adjacency bytes"] = int(M.lib.nsa_tri_adjacency_workspace(ix.V, ix.F))
 
@@ -84,8 +66,8 @@ def sdf_rows(ix, surf, near, cube, out):
         ix.adjacency(True)
 
     out["adjacency build ms (weld included)"] = timed(build)
-    signed_case("on surface 200k", ix, surf, out)
-    signed_case("near surface (sigma 0.01) 200k", ix, near, out)
+    signed_case("on surface 200k", ix, surf, out, reps)
+    signed_case("near surface (sigma 0.01) 200k", ix, near, out, reps)
     h = max(ix.layout()["cell size"])
     for cells in (2, 5, 20):
         band = cells * h
@@ -98,11 +80,12 @@ def sdf_rows(ix, surf, near, cube, out):
         out[key + " cells visited/query"] = {"mean": float(n_cells.double().mean()), "max": int(n_cells.max())}
     res = {}
     out["mesh_sdf_grid 256^3, band 4 voxels, ms"] = timed(lambda: res.update(g=mesh_sdf.mesh_sdf_grid(ix, 256, (-1.0, 1.0),
-                                                                                                   band=4 * 2.0 / 255)), reps=max(1, REPS // 2))
+                                                                                                   band=4 * 2.0 / 255)), max(1, reps // 2))
     out["mesh_sdf_grid 256^3 share within the band"] = float(torch.isfinite(res["g"]).double().mean())
 
 
-def winding_rows(ix, surf, near, cube, out):
+def winding_rows(ix, surf, near, cube, out, reps):
+    timed = lambda fn, n=reps: median_ms(fn, n)
     import math
     from nicer_slam_amd import mesh_sdf
     out["winding tree bytes"] = int(M.lib.nsa_tri_winding_workspace(ix.F))
@@ -121,24 +104,26 @@ def winding_rows(ix, surf, near, cube, out):
             out[key + " nodes accepted/query"] = {"mean": float(acc.double().mean()), "max": int(acc.max())}
             out[key + " faces summed/query"] = {"mean": float(ev.double().mean()), "max": int(ev.max())}
         sub = q[:20000].contiguous()
-        out[f"{name[:-5]} 20k winding exact ms"] = timed(lambda: ix.winding(sub, beta=math.inf), reps=max(1, REPS // 2))
+        out[f"{name[:-5]} 20k winding exact ms"] = timed(lambda: ix.winding(sub, beta=math.inf), max(1, reps // 2))
         exact = ix.winding(sub, beta=math.inf)
         for beta in (2.0, 3.0):
             out[f"{name[:-5]} 20k max |w(beta {beta:g}) - w exact|"] = float((ix.winding(sub, beta=beta) - exact).abs().max())
     res = {}
     for sign in ("normal", "winding"):
         out[f"mesh_sdf_grid 256^3, band 4 voxels, sign {sign}, ms"] = timed(
-            lambda: res.update({sign: mesh_sdf.mesh_sdf_grid(ix, 256, (-1.0, 1.0), band=4 * 2.0 / 255, sign=sign)}), reps=max(1, REPS // 2))
+            lambda: res.update({sign: mesh_sdf.mesh_sdf_grid(ix, 256, (-1.0, 1.0), band=4 * 2.0 / 255, sign=sign)}), max(1, reps // 2))
     both = torch.isfinite(res["normal"])
     out["mesh_sdf_grid 256^3 share of band points where the two signs differ"] = float(
         ((res["normal"] < 0) != (res["winding"] < 0))[both].double().mean())
 
 
-def main():
-    out = {"reps": REPS, "legs": LEGS}
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    reps, timed = a.reps, lambda fn, n=a.reps: median_ms(fn, n)
+    finish = lambda out: write_results(out, "mesh_closest_bench.json", a.out)
+    out = {"reps": reps, "legs": a.legs}
     g = torch.Generator(device="cuda").manual_seed(0)
-    from bench_mesh import model
-    mesh = inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False)
+    mesh = model_mesh(a.resolution)
     v, f = mesh["verts"], mesh["faces"]
     out["mesh V"], out["mesh F"] = int(v.shape[0]), int(f.shape[0])
     out["index bytes"] = int(M.lib.nsa_tri_workspace(f.shape[0]))
@@ -146,28 +131,28 @@ def main():
     surf, _ = M.sample_surface(v, f, 200000, 0)
     near = surf + 0.01 * torch.randn(surf.shape, device="cuda", generator=g)
     cube = torch.rand(200000, 3, device="cuda", generator=g) * 2 - 1
-    if LEGS == "winding":
-        winding_rows(ix, surf, near, cube, out)
+    if a.legs == "winding":
+        winding_rows(ix, surf, near, cube, out, reps)
         return finish(out)
     out["build ms"] = timed(lambda: M.TriIndex(v, f))
     lay = ix.layout()
     out["layout"] = lay
     out["large-list share"] = lay["large faces"] / f.shape[0]
     out["skipped (index, non-finite, zero area)"] = list(ix.skipped)
-    query_case("on surface 200k", ix, surf, out)
-    query_case("near surface (sigma 0.01) 200k", ix, near, out)
-    query_case("uniform in the cube 200k", ix, cube, out)
-    sdf_rows(ix, surf, near, cube, out)
-    winding_rows(ix, surf, near, cube, out)
+    query_case("on surface 200k", ix, surf, out, reps)
+    query_case("near surface (sigma 0.01) 200k", ix, near, out, reps)
+    query_case("uniform in the cube 200k", ix, cube, out, reps)
+    sdf_rows(ix, surf, near, cube, out, reps)
+    winding_rows(ix, surf, near, cube, out, reps)
 
     # the torch float64 brute force of the tests, at a size it finishes in a few seconds; the index on the same inputs beside it
     from test_mesh_closest_gpu import _brute_torch
-    small = inference.extract_mesh(model(), 128, (-1.0, 1.0), color=False)
+    small = model_mesh(128)
     sv, sf = small["verts"], small["faces"]
     sq = near[:16384].contiguous()
     out["brute force size"] = [int(sq.shape[0]), int(sf.shape[0])]
     res = {}
-    out["torch float64 brute force ms"] = timed(lambda: res.update(b=_brute_torch(sq, sv, sf)), reps=1)
+    out["torch float64 brute force ms"] = timed(lambda: res.update(b=_brute_torch(sq, sv, sf)), 1)
     six = M.TriIndex(sv, sf)
     out["index at the brute-force size: build ms"] = timed(lambda: M.TriIndex(sv, sf))
     out["index at the brute-force size: query ms"] = timed(lambda: six.query(sq))
@@ -182,17 +167,9 @@ def main():
     for mode in ("samples", "mesh"):
         met = {}
         out[f"mesh_metrics surface={mode} ms"] = timed(lambda: met.update(M.mesh_metrics(moved, mesh, surface=mode)),
-                                                       reps=max(1, REPS // 2))
+                                                       max(1, reps // 2))
         out[f"mesh_metrics surface={mode} accuracy, completion"] = [met["accuracy"], met["completion"]]
     finish(out)
-
-
-def finish(out):
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
-    with open(OUT, "w") as fh:
-        fh.write(text + "\n")
 
 
 if __name__ == "__main__":

@@ -6,40 +6,22 @@ target: its time, and for both results the mean and the largest distance between
 through TriIndex.query (the vertices of one mesh against the surface of the other).  There is no earlier version and no reference
 program, so nothing is compared in time but the two routes.  Results go to profiles/mesh_decimate_bench.json.
 usage: python tools/bench_mesh_decimate.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
-import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_decimate as M, mesh_simplify
+from benchlib import event_window, median, median_ms, mesh_positionals, model_mesh, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_decimate as M, mesh_simplify
 from nicer_slam_amd._native import lib, check
 from nicer_slam_amd.mesh_eval import TriIndex
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
 MAX_ROUNDS = 2000
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return mesh_positionals(argv)
 
 
 def distances(result, mesh):
@@ -51,7 +33,7 @@ def distances(result, mesh):
             "two-sided mean": 0.5 * (float(fwd.mean()) + float(back.mean())), "two-sided max": max(float(fwd.max()), float(back.max()))}
 
 
-def first_round(v, f):
+def first_round(v, f, reps):
     """ms of the three native calls of the first round on the whole mesh, each on its own (the state is made afresh every time)"""
     dev, V, F = v.device, v.shape[0], f.shape[0]
     s = torch.cuda.current_stream(dev).cuda_stream
@@ -84,25 +66,21 @@ def first_round(v, f):
                                           tb.ring_edge.data_ptr(), 0, 1, F // 10, 0, 0.0, 0.04, 1e-3, 0, ws.data_ptr(), state.data_ptr(),
                                           log.data_ptr(), V, totals.data_ptr(), s))
 
-    out = {"nsa_mesh_edges ms": timed(edges), "nsa_mesh_ring ms": timed(rings), "init ms (tables included)": timed(init)}
+    out = {"nsa_mesh_edges ms": median_ms(edges, reps), "nsa_mesh_ring ms": median_ms(rings, reps),
+           "init ms (tables included)": median_ms(init, reps)}
     ms = []
-    for _ in range(REPS + 1):                                     # a round changes the state: a fresh one each time, outside the events
+    for _ in range(reps + 1):                                     # a round changes the state: a fresh one each time, outside the events
         init()
         torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        round_()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    out["nsa_mesh_decimate_round ms"] = float(np.median(ms[1:]))
+        ms.append(event_window(round_))
+    out["nsa_mesh_decimate_round ms"] = median(ms[1:])
     return out
 
 
-def case(name, mesh, out):
+def case(name, mesh, out, reps):
     mesh = {k: mesh[k].contiguous() for k in ("verts", "faces")}
     v, f = mesh["verts"], mesh["faces"]
-    r = {"V": v.shape[0], "F": f.shape[0], "first round": first_round(v, f.to(torch.int32))}
+    r = {"V": v.shape[0], "F": f.shape[0], "first round": first_round(v, f.to(torch.int32), reps)}
     for div in (10, 100):
         target = f.shape[0] // div
         c = {"target": target}
@@ -123,11 +101,11 @@ def case(name, mesh, out):
         c.update(rounds=res[5]["rounds"], collapses=res[5]["collapses"],
                  collapses_per_round={"first": takes[0], "median": float(np.median(takes)), "last": takes[-1], "max": max(takes)},
                  round_wall_ms={"first": walls[0], "median": float(np.median(walls)), "last": walls[-1], "sum": float(np.sum(walls))})
-        c["decimate() ms"] = timed(lambda: M.decimate(mesh, target_faces=target, max_rounds=MAX_ROUNDS, normals=None))
+        c["decimate() ms"] = median_ms(lambda: M.decimate(mesh, target_faces=target, max_rounds=MAX_ROUNDS, normals=None), reps)
         dec = M.decimate(mesh, target_faces=target, max_rounds=MAX_ROUNDS, normals=None)
         c["decimate faces"] = int(dec["faces"].shape[0])
         c["decimate distances"] = distances(dec, mesh)
-        c["simplify(target_faces=) ms"] = timed(lambda: mesh_simplify.simplify(mesh, target_faces=target), reps=3)
+        c["simplify(target_faces=) ms"] = median_ms(lambda: mesh_simplify.simplify(mesh, target_faces=target), 3)
         sim = mesh_simplify.simplify(mesh, target_faces=target)
         c["simplify faces"] = int(sim["faces"].shape[0])
         c["simplify distances"] = distances(sim, mesh)
@@ -135,17 +113,12 @@ def case(name, mesh, out):
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    case(f"model mesh {RES}^3", inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False), out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_decimate_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    case(f"model mesh {a.resolution}^3", model_mesh(a.resolution), out, a.reps)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), out, a.reps)
+    write_results(out, "mesh_decimate_bench.json")
 
 
 if __name__ == "__main__":

@@ -12,50 +12,36 @@ afterwards, and the patch area beside the polar patch's of skip_folded=False.  R
 (profiles/mesh_fill_area_bench_min_area.json for min_area).
 usage: python tools/bench_mesh_fill.py [--method polar|auto|min_area] [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
 import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_fill as M, mesh_topology
+from benchlib import median_ms, mesh_positionals, model_mesh, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_fill as M, mesh_topology
 from nicer_slam_amd._native import lib, check
 
-METHOD = "polar"
-if "--method" in sys.argv:                                        # (taken out: tools/bench_mesh_clean.py reads the same positions)
-    at = sys.argv.index("--method")
-    METHOD = sys.argv[at + 1]
-    del sys.argv[at:at + 2]
-if METHOD not in M.METHODS:
-    raise SystemExit(f"--method must be one of {M.METHODS}")
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
 KW = dict(skip_folded=True)
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    """the four positionals of the mesh benches, and --method M anywhere among them"""
+    argv, method = list(argv), "polar"
+    if "--method" in argv:
+        at = argv.index("--method")
+        method = argv[at + 1]
+        del argv[at:at + 2]
+    if method not in M.METHODS:
+        raise SystemExit(f"--method must be one of {M.METHODS}")
+    a = mesh_positionals(argv)
+    a.method = method
+    return a
 
 
-def native_calls(v, f):
+def native_calls(v, f, reps):
     """ms of the three native calls on the whole mesh, each on its own"""
+    timed = lambda fn: median_ms(fn, reps)
     dev, V, F = v.device, v.shape[0], f.shape[0]
     s = torch.cuda.current_stream(dev).cuda_stream
     t, et = mesh_topology._edge_table(f, V, F, None)
@@ -89,9 +75,10 @@ def patch_area(mesh, first_face):
     return float(0.5 * n.norm(dim=1).sum())
 
 
-def area_case(name, mesh, out):
+def area_case(name, mesh, out, reps, METHOD):
     """one mesh through method=METHOD"""
     import fill_area_ref
+    timed = lambda fn: median_ms(fn, reps)
     from nicer_slam_amd import mesh_sdf
     v, f = mesh["verts"].float().contiguous(), mesh["faces"].to(torch.int32).contiguous()
     mesh = {"verts": v, "faces": f}
@@ -146,17 +133,18 @@ def area_case(name, mesh, out):
     print(name, json.dumps(r), flush=True)
 
 
-def case(name, mesh, out):
-    if METHOD != "polar":
-        return area_case(name, mesh, out)
+def case(name, mesh, out, reps, method):
+    if method != "polar":
+        return area_case(name, mesh, out, reps, method)
     import fill_ref
+    timed = lambda fn: median_ms(fn, reps)
     v, f = mesh["verts"].float().contiguous(), mesh["faces"].to(torch.int32).contiguous()
     mesh = {"verts": v, "faces": f}
     got, rep = M.fill_holes(mesh, return_report=True, **KW)
     r = {"V": v.shape[0], "F": f.shape[0], "totals": rep["totals"],
          "loop edges": {"max": max(rep["n"], default=0), "median": float(np.median(rep["n"])) if rep["n"] else 0.0},
          "rounds of each kind": fill_ref.n_rounds(rep["totals"]["n_boundary"]),
-         "fill_holes() ms": timed(lambda: M.fill_holes(mesh, **KW)), "native calls": native_calls(v, f)}
+         "fill_holes() ms": timed(lambda: M.fill_holes(mesh, **KW)), "native calls": native_calls(v, f, reps)}
     after = mesh_topology.topology(got)
     r["after"] = {k: after[k] for k in ("n_boundary", "n_boundary_loops", "is_watertight", "is_oriented")}
     if rep["totals"]["n_folded"]:                                 # what the star test holds back: the same call without it
@@ -175,21 +163,15 @@ def case(name, mesh, out):
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    full = inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False)
-    case(f"model mesh {RES}^3", full, out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), out)
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    full = model_mesh(a.resolution)
+    case(f"model mesh {a.resolution}^3", full, out, a.reps, a.method)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), out, a.reps, a.method)
     keep = torch.arange(full["faces"].shape[0], device=full["faces"].device) % 97 != 96
-    case(f"model mesh {RES}^3 without every 97th face", {"verts": full["verts"], "faces": full["faces"][keep]}, out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    name = {"polar": "mesh_fill_bench.json", "auto": "mesh_fill_area_bench.json"}.get(METHOD, f"mesh_fill_area_bench_{METHOD}.json")
-    with open(os.path.join(ROOT, "profiles", name), "w") as fh:
-        fh.write(text + "\n")
+    case(f"model mesh {a.resolution}^3 without every 97th face", {"verts": full["verts"], "faces": full["faces"][keep]}, out, a.reps, a.method)
+    write_results(out, {"polar": "mesh_fill_bench.json", "auto": "mesh_fill_area_bench.json"}.get(a.method, f"mesh_fill_area_bench_{a.method}.json"))
 
 
 if __name__ == "__main__":

@@ -7,38 +7,18 @@ half the unions per joining edge, but it joins across every edge of count >= 2),
 host copy of the faces, np.unique of the edge keys, a scipy.sparse.csgraph breadth-first two-colouring over the two-face edges.
 Results go to profiles/mesh_orient_bench.json.
 usage: python tools/bench_mesh_orient.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
-import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_topology as M
+from benchlib import median, median_ms, mesh_positionals, model_mesh, time_host, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_topology as M
 from nicer_slam_amd._native import lib, check
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
 
-
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return mesh_positionals(argv)
 
 
 def host_route(f):
@@ -78,7 +58,8 @@ def host_route(f):
     return acc, n
 
 
-def case(name, mesh, out):
+def case(name, mesh, out, reps):
+    timed = lambda fn: median_ms(fn, reps)
     gen = torch.Generator().manual_seed(7)
     f0 = mesh["faces"].contiguous()
     which = (torch.rand(f0.shape[0], generator=gen) < 0.3).to(f0.device)
@@ -131,30 +112,19 @@ def case(name, mesh, out):
     r["orient(outward=None) ms"] = timed(lambda: M.orient(scrambled, outward=None))
     r["edge_table() ms"] = timed(lambda: M.edge_table(f, V))
     try:
-        host_route(f)
-        ts = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            colour, ncomp = host_route(f)
-            ts.append((time.perf_counter() - t0) * 1e3)
-        r["host components"] = int(ncomp)
-        r["host copy + np.unique + scipy breadth-first two-colouring ms"] = float(np.median(ts))
+        r["host components"] = int(host_route(f)[1])
+        r["host copy + np.unique + scipy breadth-first two-colouring ms"] = median(time_host(lambda: host_route(f), 3, warmup=False))
     except ImportError:
         r["host copy + np.unique + scipy breadth-first two-colouring ms"] = None
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    case(f"model mesh {RES}^3", inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False), out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_orient_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    case(f"model mesh {a.resolution}^3", model_mesh(a.resolution), out, a.reps)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), out, a.reps)
+    write_results(out, "mesh_orient_bench.json")
 
 
 if __name__ == "__main__":

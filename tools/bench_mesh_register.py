@@ -12,21 +12,16 @@ Results go to profiles/mesh_register_bench.json.
 usage: python tools/bench_mesh_register.py [reps=7] [rows=200000,2000000]"""
 import json
 import math
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+from benchlib import median, median_ms, positionals, time_host, write_results
 from nicer_slam_amd import _native, inference, mesh_eval as E, mesh_register as M, mesh_smooth
 from nicer_slam_amd._native import check, lib
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-ROWS = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [200000, 2000000]
+DEFAULT_ROWS = [200000, 2000000]
 MAX_CORR = 0.1
 MAX_GRID = 1280                      # marching cubes takes up to 2^31 samples: the 2 M case gets the finest blob that fits
 
@@ -43,32 +38,8 @@ def rigid(axis, deg, t):
 MOTION = rigid([0.2, 1.0, -0.4], 3.0, [0.03, -0.02, 0.025])
 
 
-def timed(fn, reps=REPS):
-    """median ms by device events"""
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
-
-
-def walled(fn, reps=REPS):
-    """median ms by the host clock; fn ends synchronised"""
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append(1e3 * (time.perf_counter() - t0))
-    return float(np.median(ms))
+def parse_args(argv):
+    return positionals(argv, reps=(int, 7), rows=(lambda s: [int(x) for x in s.split(",")], DEFAULT_ROWS))
 
 
 def blob(res):
@@ -101,7 +72,9 @@ def composed_system(cur, idx, tgt, nrm):
     return torch.cat([A.reshape(-1), b, (r * r).sum()[None], (d * d).sum(1)[ok].sum()[None], ok.sum()[None].double()]).cpu()
 
 
-def case(n, out):
+def case(n, out, reps):
+    timed = lambda fn: median_ms(fn, reps)                           # median ms by device events
+    walled = lambda fn, k=reps: median(time_host(fn, k))             # median ms by the host clock
     mesh, res = mesh_with_about(n)
     gv, gf = mesh["verts"].float().contiguous(), mesh["faces"].to(torch.int32).contiguous()
     r = {"rows": n, "grid": res, "target vertices": gv.shape[0], "target faces": gf.shape[0]}
@@ -196,18 +169,16 @@ def case(n, out):
     print(json.dumps({f"{n} rows": r}, indent=1), flush=True)
 
 
-def main():
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_mesh_register: needs a GPU")
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS, "max_corr": MAX_CORR}
-    for n in ROWS:
-        case(n, out)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "max_corr": MAX_CORR}
+    for n in a.rows:
+        case(n, out, a.reps)
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    if ROWS == [200000, 2000000]:
-        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-        with open(os.path.join(ROOT, "profiles", "mesh_register_bench.json"), "w") as fh:
-            fh.write(text + "\n")
+    if a.rows == DEFAULT_ROWS:                                    # (every row was printed as it was made)
+        write_results(out, "mesh_register_bench.json", echo=False)
 
 
 if __name__ == "__main__":

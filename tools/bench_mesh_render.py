@@ -6,54 +6,29 @@ view (= covered (face, pixel) pairs, counted by the kernel).  Device events, med
 usage: python tools/bench_mesh_render.py [--model-res 512] [--room-voxels 256] [--views 32] [--visible-views 1000] [--reps 5] [--json OUT]"""
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
+
+from benchlib import ROOM_HALF, model_mesh, ring, time_events, write_results
 
 H, W, FOCAL = 680, 1200, 600.0
 
 
 def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    ms.sort()
-    return ms[len(ms) // 2]
-
-
-def model_mesh(res):
-    argv, sys.argv = sys.argv, sys.argv[:1]             # (bench_mesh reads its own positional arguments on import)
-    try:
-        import bench_mesh
-    finally:
-        sys.argv = argv
-    from nicer_slam_amd import inference
-    return inference.extract_mesh(bench_mesh.model(), res, bench_mesh.BOUND, color=False)
+    """the upper middle sample of ``reps`` (the median for an odd count, such as the default)"""
+    return sorted(time_events(fn, reps))[reps // 2]
 
 
 def room_mesh(voxels, frames=64):
-    import bench_tsdf
     import synthetic_sequence as ss
     from nicer_slam_amd.tsdf import TSDFVolume
-    poses = bench_tsdf.ring(frames)
+    poses = ring(frames)
     K = torch.eye(4)
     K[0, 0] = K[1, 1] = 400.0
     K[0, 2], K[1, 2] = 319.5, 239.5
-    c, d, _ = ss.render_analytic_room(torch.from_numpy(poses), K, 480, 640, "cuda", bench_tsdf.ROOM_HALF)
+    c, d, _ = ss.render_analytic_room(torch.from_numpy(poses), K, 480, 640, "cuda", ROOM_HALF)
     vl = 1.44 / voxels
     vol = TSDFVolume((-0.72,) * 3, (0.72,) * 3, vl, 4 * vl, color=False)
     vol.integrate(d.reshape(-1, 480, 640), None, poses, K)
@@ -109,8 +84,7 @@ def oracle_baseline():
                 device_ms_per_view=ms / 4)
 
 
-@torch.no_grad()
-def main():
+def parse_args(argv):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--model-res", type=int, default=512)
     ap.add_argument("--room-voxels", type=int, default=256)
@@ -118,11 +92,15 @@ def main():
     ap.add_argument("--visible-views", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--json")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+@torch.no_grad()
+def main(argv=None):
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_mesh_render: needs a GPU")
-    import bench_tsdf
-    poses = bench_tsdf.ring(args.views).astype(np.float64)
+    poses = ring(args.views).astype(np.float64)
     out = dict(device=torch.cuda.get_device_name(0), results=[])
     if args.room_voxels:
         out["results"].append(bench(f"tsdf room {args.room_voxels}^3", room_mesh(args.room_voxels), poses, args))
@@ -133,9 +111,7 @@ def main():
     out["oracle_baseline"] = oracle_baseline()
     print(json.dumps(out["oracle_baseline"]), flush=True)
     if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
+        write_results(out, path=args.json, echo=False)            # (every row was printed as it was made)
 
 
 if __name__ == "__main__":

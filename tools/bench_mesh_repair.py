@@ -4,22 +4,23 @@ onto itself by index (vertex v renamed v mod V / 2: two sheets on every vertex, 
 and ``mesh_topology.topology`` on the same mesh as the yardstick -- both are dominated by the same radix sort of 3 F keys (topology
 sorts twice, the split once more on top of the edge table it needs).  Device events, warm-up first, medians.  Results go to
 profiles/mesh_repair_bench.json.
-usage: python tools/bench_mesh_repair.py [reps=5] [resolution (unused)] [tsdf voxels=256] [tsdf frames=100]"""
-import json
-import os
+usage: python tools/bench_mesh_repair.py [reps=5] [resolution (unused)] [tsdf voxels=256] [tsdf frames=100]
+(the second positional is accepted and ignored: the command line is the other mesh benches', and this one has no model mesh)"""
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch
 
+from benchlib import median_ms, mesh_positionals, tsdf_mesh, write_results
 from nicer_slam_amd import mesh_repair as R, mesh_simplify, mesh_topology as M
 from nicer_slam_amd._native import lib, check
-from bench_mesh_clean import timed, tsdf_mesh, REPS, TSDF_N, TSDF_FRAMES
 
 
-def case(name, mesh, out):
+def parse_args(argv):
+    return mesh_positionals(argv)
+
+
+def case(name, mesh, out, reps):
+    timed = lambda fn: median_ms(fn, reps)
     f = mesh["faces"].contiguous()
     V, F = mesh["verts"].shape[0], f.shape[0]
     H = 3 * F
@@ -47,19 +48,16 @@ def case(name, mesh, out):
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    mesh = tsdf_mesh()
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", mesh, out)
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    mesh = tsdf_mesh(a.voxels, a.frames)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", mesh, out, a.reps)
     extent = float((mesh["verts"].amax(0) - mesh["verts"].amin(0)).max())
-    case("the same, clustered at extent / 96 (mean)", mesh_simplify.simplify(mesh, cell=extent / 96, placement="mean"), out)
+    case("the same, clustered at extent / 96 (mean)", mesh_simplify.simplify(mesh, cell=extent / 96, placement="mean"), out, a.reps)
     half = (mesh["verts"].shape[0] + 1) // 2
-    case("the same, folded by index (v mod V / 2)", dict(verts=mesh["verts"][:half].contiguous(), faces=mesh["faces"] % half), out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_repair_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+    case("the same, folded by index (v mod V / 2)", dict(verts=mesh["verts"][:half].contiguous(), faces=mesh["faces"] % half), out, a.reps)
+    write_results(out, "mesh_repair_bench.json")
 
 
 if __name__ == "__main__":

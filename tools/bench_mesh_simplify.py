@@ -6,38 +6,18 @@ the triples -- which is timed beside it (it computes the same vertex and face co
 the downstream effect: the TriIndex build and one render_depth before and after.  Results go to profiles/mesh_simplify_bench.json.
 usage: python tools/bench_mesh_simplify.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
 import ctypes
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_raycast, mesh_simplify as M
+from benchlib import look_at, median_ms, mesh_positionals, model_mesh, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_raycast, mesh_simplify as M
 from nicer_slam_amd._native import lib, check
 from nicer_slam_amd.mesh_eval import TriIndex
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
 
-
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return mesh_positionals(argv)
 
 
 def composed(v, f, origin, h, eps=1e-3):
@@ -85,28 +65,20 @@ def composed(v, f, origin, h, eps=1e-3):
     return named.numel(), faces.shape[0], verts
 
 
-def look_at(eye, target, up=(0.0, 0.0, 1.0)):
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    z = (target - eye) / np.linalg.norm(target - eye)
-    x = np.cross(z, up)
-    x /= np.linalg.norm(x)
-    T = np.eye(4)
-    T[:3, 0], T[:3, 1], T[:3, 2], T[:3, 3] = x, np.cross(z, x), z, eye
-    return T
-
-
-def downstream(mesh):
+def downstream(mesh, reps):
     """ms of a TriIndex build and of one 480 x 640 render_depth from inside the bounding box"""
     v, f = mesh["verts"], mesh["faces"]
     lo, hi = M._extent(v)
     mid = [(a + b) / 2 for a, b in zip(lo, hi)]
     c2w = look_at(mid, [mid[0] + 1.0, mid[1] + 0.3, mid[2] + 0.1])
     K = (400.0, 400.0, 319.5, 239.5)
-    return {"TriIndex build ms": timed(lambda: TriIndex(v, f)),
-            "render_depth 480x640 ms (tree build included)": timed(lambda: mesh_raycast.render_depth(mesh, c2w, K, (480, 640), channels=("depth",)))}
+    return {"TriIndex build ms": median_ms(lambda: TriIndex(v, f), reps),
+            "render_depth 480x640 ms (tree build included)": median_ms(
+                lambda: mesh_raycast.render_depth(mesh, c2w, K, (480, 640), channels=("depth",)), reps)}
 
 
-def case(name, mesh, voxel, out):
+def case(name, mesh, voxel, out, reps):
+    timed = lambda fn: median_ms(fn, reps)
     v, f = mesh["verts"].contiguous(), mesh["faces"].contiguous()
     normals, colors = mesh.get("normals"), mesh.get("colors")
     V, F = v.shape[0], f.shape[0]
@@ -150,25 +122,20 @@ def case(name, mesh, voxel, out):
         c["composed / simplify()"] = c["composed torch route ms"] / c["simplify() ms"]
         r["cells"][f"{k} voxels"] = c
     target = F // 10
-    r["target_faces"] = {"target": target, "simplify(target_faces=F/10) ms": timed(lambda: M.simplify(mesh, target_faces=target), reps=3)}
+    r["target_faces"] = {"target": target, "simplify(target_faces=F/10) ms": median_ms(lambda: M.simplify(mesh, target_faces=target), 3)}
     small = M.simplify(mesh, target_faces=target, return_map=True)
     r["target_faces"].update(cell=small["cell"], cell_in_voxels=small["cell"] / voxel, **small["totals"])
-    r["downstream before"] = downstream(mesh)
-    r["downstream after target_faces"] = downstream({k: small[k] for k in ("verts", "faces")})
+    r["downstream before"] = downstream(mesh, reps)
+    r["downstream after target_faces"] = downstream({k: small[k] for k in ("verts", "faces")}, reps)
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    case(f"model mesh {RES}^3", inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False), 2.0 / (RES - 1), out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), 1.44 / TSDF_N, out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_simplify_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    case(f"model mesh {a.resolution}^3", model_mesh(a.resolution), 2.0 / (a.resolution - 1), out, a.reps)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), 1.44 / a.voxels, out, a.reps)
+    write_results(out, "mesh_simplify_bench.json")
 
 
 if __name__ == "__main__":

@@ -8,40 +8,19 @@ tests/smooth_ref.py on the host.  A third mesh, a synthetic lattice of [lattice 
 that the positions and neighbour lists do not fit the caches; the host oracle is left out there.  Results go to
 profiles/mesh_smooth_bench.json.
 usage: python tools/bench_mesh_smooth.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100] [lattice side=3000, 0: none]"""
-import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_smooth as M, mesh_topology as MT
+from benchlib import median_ms, mesh_positionals, model_mesh, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_smooth as M, mesh_topology as MT
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
-LATTICE = int(sys.argv[5]) if len(sys.argv) > 5 else 3000
 TAUBIN = M.factors_of("taubin", 10)
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return mesh_positionals(argv, lattice=(int, 3000))
 
 
 def composed_setup(f, V):
@@ -77,7 +56,8 @@ def lattice(n, seed=2):
     return dict(verts=v, faces=f)
 
 
-def case(name, mesh, out, host=True):
+def case(name, mesh, out, reps, host=True):
+    timed = lambda fn: median_ms(fn, reps)
     v, f = mesh["verts"].float().contiguous(), mesh["faces"].contiguous()
     V, F = v.shape[0], f.shape[0]
     plain = dict(verts=v, faces=f)
@@ -136,19 +116,14 @@ def case(name, mesh, out, host=True):
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    case(f"model mesh {RES}^3", inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False), out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), out)
-    if LATTICE:
-        case(f"lattice {LATTICE}^2, random heights", lattice(LATTICE), out, host=False)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_smooth_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    case(f"model mesh {a.resolution}^3", model_mesh(a.resolution), out, a.reps)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), out, a.reps)
+    if a.lattice:
+        case(f"lattice {a.lattice}^2, random heights", lattice(a.lattice), out, a.reps, host=False)
+    write_results(out, "mesh_smooth_bench.json")
 
 
 if __name__ == "__main__":

@@ -4,38 +4,18 @@ points are timed without the wrappers' read-back of the totals as well.  The hos
 np.unique of the int64 edge keys, scipy.sparse.csgraph.connected_components over the faces -- is timed as the only runnable baseline;
 there is no earlier version of this capability to compare with.  Results go to profiles/mesh_topology_bench.json.
 usage: python tools/bench_mesh_topology.py [reps=5] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
-import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_topology as M
+from benchlib import median, median_ms, mesh_positionals, model_mesh, time_host, tsdf_mesh, write_results
+from nicer_slam_amd import mesh_topology as M
 from nicer_slam_amd._native import lib, check
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 512
-TSDF_N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-TSDF_FRAMES = int(sys.argv[4]) if len(sys.argv) > 4 else 100
 
-
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return mesh_positionals(argv)
 
 
 def host_route(f, V):
@@ -58,7 +38,8 @@ def host_route(f, V):
     return len(count), int((count == 1).sum()), n
 
 
-def case(name, mesh, out):
+def case(name, mesh, out, reps):
+    timed = lambda fn: median_ms(fn, reps)
     f = mesh["faces"].contiguous()
     V, F = mesh["verts"].shape[0], f.shape[0]
     H = 3 * F
@@ -91,32 +72,22 @@ def case(name, mesh, out):
     r["topology() ms"] = timed(lambda: M.topology(mesh))
     r["topology(weld=True) ms"] = timed(lambda: M.topology(mesh, weld=True))
     try:
-        host_route(f, V)
-        ts = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            E, B, n = host_route(f, V)
-            ts.append((time.perf_counter() - t0) * 1e3)
+        E, B, n = host_route(f, V)
         assert (E, B) == (rep["n_edges"], rep["n_boundary"]), (E, B, rep)
         if rep["n_contributing"] == F:                            # (the host route takes every face as it is)
             assert n == rep["n_components"], (n, rep)
-        r["host copy + np.unique + scipy connected_components ms"] = float(np.median(ts))
+        r["host copy + np.unique + scipy connected_components ms"] = median(time_host(lambda: host_route(f, V), 3, warmup=False))
     except ImportError:
         r["host copy + np.unique + scipy connected_components ms"] = None
     out[name] = r
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
-    from bench_mesh import model
-    case(f"model mesh {RES}^3", inference.extract_mesh(model(), RES, (-1.0, 1.0), color=False), out)
-    import bench_mesh_clean                                       # (reads the same command line)
-    case(f"tsdf room {TSDF_N}^3, {TSDF_FRAMES} frames", bench_mesh_clean.tsdf_mesh(), out)
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "mesh_topology_bench.json"), "w") as fh:
-        fh.write(text + "\n")
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    out = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    case(f"model mesh {a.resolution}^3", model_mesh(a.resolution), out, a.reps)
+    case(f"tsdf room {a.voxels}^3, {a.frames} frames", tsdf_mesh(a.voxels, a.frames), out, a.reps)
+    write_results(out, "mesh_topology_bench.json")
 
 
 if __name__ == "__main__":

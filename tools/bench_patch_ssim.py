@@ -3,40 +3,25 @@ mapping iteration of 16 x 16 x 256 patches holds), with the bytes it has to move
 mask byte per pixel -- over the time, and the torch restatement (model/warp.py::patch_ssim_term, forward + backward) on the same
 device for context.  Device events around CALLS back-to-back launches on preallocated buffers, warm-up first, median of REPS.
 usage: python tools/bench_patch_ssim.py [reps=7]"""
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np
 import torch
 
+from benchlib import median_min_max, median_ms, positionals, time_events, write_results
 from nicer_slam_amd._native import lib, check
 from nicer_slam_amd.fused.warp import patch_ssim
 from nicer_slam_amd.model.warp import patch_ssim_term
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 CALLS = 20
 N = 65536
 
 
-def timed(fn, calls=1):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(REPS):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1) / calls)
-    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+def parse_args(argv):
+    return positionals(argv, reps=(int, 7))
 
 
-def main():
+def main(argv=None):
+    REPS = parse_args(sys.argv[1:] if argv is None else argv).reps
     out = {"device": torch.cuda.get_device_name(0), "reps": REPS, "calls per rep": CALLS, "patches": N}
     g = torch.Generator(device="cuda").manual_seed(0)
     st = torch.cuda.current_stream().cuda_stream
@@ -49,7 +34,7 @@ def main():
         ws = torch.empty((int(lib.nsa_patch_ssim_workspace(N)) + 1) // 2, device="cuda", dtype=torch.float64)
         call = lambda: check(lib.nsa_patch_ssim(x.data_ptr(), y.data_ptr(), mb.data_ptr(), N, p, loss.data_ptr(), grad.data_ptr(),
                                                 ws.data_ptr(), st))
-        ms, lo, hi = timed(call, CALLS)
+        ms, lo, hi = median_min_max(time_events(call, REPS, CALLS))
         nbytes = 3 * 4 * x.numel() + m.numel()
         key = f"p={p}"
         out[key + " nsa_patch_ssim with gradient ms (median, min, max)"] = [ms, lo, hi]
@@ -65,11 +50,11 @@ def main():
         def twin():
             xr.grad = None
             patch_ssim_term(xr, y, m, p).backward()
-        out[key + " fused.warp.patch_ssim forward + backward ms"] = timed(through_autograd)[0]
-        out[key + " torch restatement forward + backward ms"] = timed(twin)[0]
+        out[key + " fused.warp.patch_ssim forward + backward ms"] = median_ms(through_autograd, REPS)
+        out[key + " torch restatement forward + backward ms"] = median_ms(twin, REPS)
         out[key + " loss"] = float(loss)
         del x, y, m, grad, xr
-    print(json.dumps(out, indent=1))
+    write_results(out)
 
 
 if __name__ == "__main__":

@@ -5,64 +5,30 @@ those pixels; the tree build, its bytes, and the nodes visited and faces tested 
 ray cast is built once outside the timed window, as a tracking or mapping loop would hold it; the rasteriser has no index to build.
 Device events, warm-up first, medians of `reps` runs with their spread; the two sides alternate within one process.
 usage: python tools/bench_raycast.py [reps=20] [resolution=128] [out=profiles/raycast_bench.json]"""
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np
 import torch
 
-from nicer_slam_amd import inference, mesh_raycast, mesh_render
+from benchlib import look_at, mc_sphere, median_min_max, positionals, time_pair, write_results
+from nicer_slam_amd import mesh_raycast, mesh_render
 from nicer_slam_amd.mesh_eval import TriIndex
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-RES = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "raycast_bench.json")
 H, W = 480, 640
 
 
-def mc_sphere(res, r=0.5, bound=1.0):
-    ax = torch.linspace(-bound, bound, res, dtype=torch.float64)
-    X, Y, Z = torch.meshgrid(ax, ax, ax, indexing="ij")
-    vol = (torch.sqrt(X ** 2 + Y ** 2 + Z ** 2) - r).float().cuda()
-    step = float(ax[1] - ax[0])
-    return inference.marching_cubes(vol, 0.0, (step,) * 3, (-bound,) * 3)
+def parse_args(argv):
+    return positionals(argv, reps=(int, 20), resolution=(int, 128), out=(str, None))     # out: None is profiles/raycast_bench.json
 
 
-def look_at(eye, target, up=(0.0, 0.0, 1.0)):
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    z = (target - eye) / np.linalg.norm(target - eye)
-    x = np.cross(z, up)
-    x /= np.linalg.norm(x)
-    T = np.eye(4)
-    T[:3, 0], T[:3, 1], T[:3, 2], T[:3, 3] = x, np.cross(z, x), z, eye
-    return T
-
-
-def timed_pair(a, b, reps=REPS):
-    """medians and (min, max) in ms of a() and b(), alternating, after one warm-up of each"""
-    out = []
-    for fn in (a, b):
-        fn()
-    torch.cuda.synchronize()
-    ms = ([], [])
-    for _ in range(reps):
-        for k, fn in enumerate((a, b)):
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            fn()
-            t1.record()
-            torch.cuda.synchronize()
-            ms[k].append(t0.elapsed_time(t1))
-    for m in ms:
-        out.append({"median ms": float(np.median(m)), "min ms": float(min(m)), "max ms": float(max(m))})
-    return out
-
-
-def main():
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    REPS, RES = args.reps, args.resolution
     assert torch.cuda.is_available(), "bench_raycast.py needs an MI355X"
+
+    def timed_pair(fa, fb):
+        """median, min and max in ms of fa() and fb(), alternating, after one warm-up of each"""
+        return [dict(zip(("median ms", "min ms", "max ms"), median_min_max(ms))) for ms in time_pair(fa, fb, REPS)]
+
     m = mc_sphere(RES)
     mesh = {"verts": m["verts"], "faces": m["faces"]}
     out = {"device": torch.cuda.get_device_name(0), "resolution": RES, "faces": int(m["faces"].shape[0]), "view": [H, W], "reps": REPS}
@@ -107,10 +73,7 @@ def main():
     po, pd = mesh_raycast.camera_rays(c2w, K, (H, W), px, device="cuda")
     alone, rays = timed_pair(lambda: ix.raycast(po, pd, tmin=0.01), lambda: mesh_raycast.camera_rays(c2w, K, (H, W), px, device="cuda"))
     out["1024 rays raycast alone"], out["1024 camera rays made in torch"] = alone, rays
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    with open(OUT, "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(json.dumps(out, indent=1))
+    write_results(out, "raycast_bench.json", args.out)
 
 
 if __name__ == "__main__":

@@ -4,38 +4,22 @@ same device for context; one 680x1200 view through inference.render_image(mode="
 of 2580 (the reference's split_n_pixels) and 65536 rays; evaluate_views on 4 views end to end.  Device events, warm-up first,
 medians of REPS runs; per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
 usage: python tools/bench_render_eval.py [reps=5]"""
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np
 import torch
 import torch.nn.functional as F
 
+from benchlib import median_ms, model, positionals, write_results
 from nicer_slam_amd import inference
 from nicer_slam_amd.render_eval import image_metrics, evaluate_views, _uv
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 # float64 operations per pixel and channel: 3 products + 2 x 5 x 11 FMAs (two separable passes, FMA = 2) + 13 for the formula
 # + 3 for the squared error; bytes: both images read once (the halo re-reads hit the caches)
 FLOP_PER_VALUE = 3 + 2 * 5 * 11 * 2 + 13 + 3
 
 
-def timed(fn, reps=REPS):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        torch.cuda.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return float(np.median(ms))
+def parse_args(argv):
+    return positionals(argv, reps=(int, 5))
 
 
 def ref_fp32(x, y, H, W, w):
@@ -50,17 +34,6 @@ def ref_fp32(x, y, H, W, w):
     return m.mean((1, 2, 3)), ((a - b) ** 2).mean((1, 2, 3))
 
 
-def model():
-    from nicer_slam_amd.utils.conf import replica_model_conf
-    from nicer_slam_amd.model.network import SLAMNetwork
-    torch.manual_seed(4)
-    m = SLAMNetwork(replica_model_conf(use_warp_loss=False)).cuda()
-    with torch.no_grad():
-        for enc in (m.implicit_network.coarse.encoding, m.implicit_network.fine.encoding, m.rendering_network.encoding):
-            enc.embeddings.uniform_(-0.05, 0.05)
-    return m.eval()
-
-
 def view(H, W, n):
     K = torch.eye(4, device="cuda")[None].repeat(n, 1, 1)
     K[:, 0, 0] = K[:, 1, 1] = 600.0
@@ -71,7 +44,9 @@ def view(H, W, n):
     return K, poses
 
 
-def main():
+def main(argv=None):
+    REPS = parse_args(sys.argv[1:] if argv is None else argv).reps
+    timed = lambda fn, reps=REPS: median_ms(fn, reps)
     out = {"device": torch.cuda.get_device_name(0), "reps": REPS}
     g = torch.Generator(device="cuda").manual_seed(0)
     import ssim_ref
@@ -107,7 +82,7 @@ def main():
     out["evaluate_views 4 x 680x1200 ms"] = timed(lambda: evaluate_views(m, K, poses, gt, (H, W)), reps=max(1, REPS // 2))
     r = evaluate_views(m, K, poses, gt, (H, W))
     out["evaluate_views psnr / ssim means"] = [r["psnr_mean"], r["ssim_mean"]]
-    print(json.dumps(out, indent=1))
+    write_results(out)
 
 
 if __name__ == "__main__":

@@ -16,43 +16,17 @@ import json
 import os
 import subprocess
 import sys
-import time
 
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from benchlib import ROOM_HALF, ROOT, ring, time_host, write_results
 
 STREAM_BW = 6.3e12          # bytes / s a float4 streaming copy reaches on an MI355X (8.0 TB/s HBM3E peak)
-ROOM_HALF = (0.62, 0.5, 0.56)
-
-
-def ring(n):
-    """n camera-to-world matrices on a ring inside the room, looking outwards, pitched up and down"""
-    out = np.tile(np.eye(4), (n, 1, 1))
-    for k in range(n):
-        a = 2 * np.pi * k / n
-        el = 0.6 * np.sin(7.0 * a)
-        fwd = np.array([np.cos(a) * np.cos(el), np.sin(el), np.sin(a) * np.cos(el)])
-        right = np.cross(np.array([0.0, 1.0, 0.0]), fwd)
-        right /= np.linalg.norm(right)
-        out[k, :3, 0], out[k, :3, 1], out[k, :3, 2] = right, np.cross(fwd, right), fwd
-        out[k, :3, 3] = [0.22 * np.cos(a), 0.05 * np.sin(3 * a), 0.22 * np.sin(a)]
-    return out.astype(np.float32)
 
 
 def timed(fn, repeat=1):
-    """seconds of each of ``repeat`` runs of fn(), each ending in a device synchronise"""
-    out = []
-    for _ in range(repeat):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(time.perf_counter() - t0)
-    return out
+    """seconds of each of ``repeat`` runs of fn(), each ending in a device synchronise; no warm-up: (a) and (b) time first runs"""
+    return [ms / 1e3 for ms in time_host(fn, repeat, warmup=False)]
 
 
 def run(args):
@@ -108,7 +82,7 @@ def run(args):
     return res
 
 
-def main():
+def parse_args(argv):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--voxels", type=int, default=512)
     ap.add_argument("--frames", type=int, default=1000)
@@ -116,7 +90,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-child", action="store_true", help="skip (d)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     res = run(args)
     nocull = os.path.join(ROOT, "nicer_slam_amd", "lib", "libnicer_slam_amd_tsdfnocull.so")
     if not args.no_child and not os.environ.get("NSA_LIB_TAG"):
@@ -129,11 +107,9 @@ def main():
             res["d_without_culling"] = json.loads(r.stdout.strip().splitlines()[-1])
         else:
             res["d_without_culling"] = "not measured: no side-by-side library built with -DNSA_X_TSDF_NOCULL"
-    line = json.dumps(res)
-    print(line)
+    print(json.dumps(res))                                        # one line: the parent of a child run reads the last one
     if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(json.dumps(res, indent=1) + "\n")
+        write_results(res, path=args.out, echo=False)
 
 
 if __name__ == "__main__":

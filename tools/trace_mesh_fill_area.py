@@ -11,8 +11,7 @@ import glob
 import json
 import os
 import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from types import SimpleNamespace
 
 
 def summarise(folder):
@@ -50,16 +49,25 @@ def summarise(folder):
     return out
 
 
-def main():
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+def parse_args(argv):
+    """--summarise DIR, or the positionals of tools/bench_mesh_fill.py: [reps (unused)] [resolution=512] [tsdf voxels=256] [tsdf frames=100]"""
+    if len(argv) > 1 and argv[0] == "--summarise":
+        return SimpleNamespace(summarise=argv[1])
+    from benchlib import mesh_positionals
+    a = mesh_positionals(argv)
+    a.summarise = None
+    return a
+
+
+def main(argv=None):
+    a = parse_args(sys.argv[1:] if argv is None else argv)
+    if a.summarise:
+        return summarise(a.summarise)
     import torch
-    from nicer_slam_amd import inference, mesh_fill as M
-    import bench_mesh_clean                                       # (reads the same command line)
-    from bench_mesh import model
-    res = getattr(bench_mesh_clean, "RES", 512)
-    room = bench_mesh_clean.tsdf_mesh()
-    full = inference.extract_mesh(model(), res, (-1.0, 1.0), color=False)
+    from benchlib import model_mesh, tsdf_mesh
+    from nicer_slam_amd import mesh_fill as M
+    room = tsdf_mesh(a.voxels, a.frames)
+    full = model_mesh(a.resolution)
     keep = torch.arange(full["faces"].shape[0], device=full["faces"].device) % 97 != 96
     masked = {"verts": full["verts"], "faces": full["faces"][keep]}
     for mesh, method in ((room, "auto"), (masked, "min_area")):
@@ -71,7 +79,4 @@ def main():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "--summarise":
-        summarise(sys.argv[2])
-    else:
-        main()
+    main()
