@@ -64,6 +64,44 @@ def colour_coarse_case(params, cfg, x, d, normals, feat, g_rgb, grid_grad, g_sdf
     return call
 
 
+def layer(l):
+    return f"[dW{l} | db{l}]"
+
+
+def sdf_weight_grad_case(params, cfg, x, which, gs, gf, gg):
+    """the per-point weight gradients of sdf_backward_case's graph (the same roundings in the same order: the same Margin and kept set)
+    -> per layer "[dW_l | db_l]" [P, out, in + 1], and the Softplus outputs "H_k" [P, 64] (value path: a FORWARD quantity)"""
+    def call(**kw):
+        r = ref64.sdf_weight_grads(params, cfg, x, which, gs, gf, gg, **kw)
+        out = {layer(l): rows for l, rows in enumerate(r.rows)}
+        out.update({f"H{k}": r.acts[k] for k in range(1, len(r.acts))})
+        return out
+    return call
+
+
+def colour_weight_grad_case(params, cfg, x, d, normals, feat, g_rgb, grid_grad):
+    def call(**kw):
+        r = ref64.colour_weight_grads(params, cfg, x, normals, d, feat, g_rgb, grid_grad, **kw)
+        out = {layer(l): rows for l, rows in enumerate(r.rows)}
+        out.update({f"H{k}": r.acts[k] for k in range(1, len(r.acts))})
+        return out
+    return call
+
+
+def weight_grad_cases(params, cfg, n=N, i=None):
+    """name -> (call, c_p, backward = True, colour?): the emission-row gates of tests/test_gemm_bf16_gpu.py, on the points and
+    cotangents of the d/dx cases.  Not part of all_cases: a case's references are some GB at n = 4 123 (fine network), so they are
+    built one case at a time and dropped."""
+    out, i = {}, inputs(params, cfg, n) if i is None else i
+    for which in ("coarse", "fine"):
+        for name, (gs, gf, gg, c) in i.fam.items():
+            out[f"weight gradients {which}: {name}"] = (sdf_weight_grad_case(params, cfg, i.xb, which, gs, gf, gg), c, True, False)
+    for gg_ in (0, 1):
+        out[f"weight gradients colour grid_grad {gg_}"] = (colour_weight_grad_case(params, cfg, i.x, i.d, i.normals, i.feat, i.g_rgb, gg_),
+                                                            i.c, True, True)
+    return out
+
+
 def inputs(params, cfg, n=N):
     """every input of the suite (the fp32 suite's builders and seeds at n points): xf / xb the points of the SDF forwards / backwards,
     fam the cotangent families, x, d, normals, feat, c, g_rgb, g_sdf the colour kernels' inputs and cotangents"""

@@ -1,5 +1,5 @@
 """The per-point gate that holds a bf16-operand kernel to the float64-accumulating bf16 reference (test infrastructure, no GPU needed:
-tests/test_ref64_bf16_cpu.py proves on the CPU that it passes two correct fp32 emulations and refuses four subtly wrong ones,
+tests/test_ref64_bf16_cpu.py proves on the CPU that it passes the correct fp32 emulations and refuses five subtly wrong ones,
 tests/test_gemm_bf16_gpu.py applies it to the HIP kernels).
 
 A bf16-operand result cannot be held to float64 by one flat per-point tolerance: an operand within working-precision noise of a bf16
@@ -28,10 +28,14 @@ MIN_SHARE, MIN_KEPT = 0.10, 400
 REPORT = []
 
 
-def gate(what, got, b64, y32, f64, norm, margin, backward, keep=None, failures=None, threshold=None, quiet=False):
+def gate(what, got, b64, y32, f64, norm, margin, backward, keep=None, failures=None, threshold=None, quiet=False, second=None):
     """got: the result under test; b64 / y32 / f64: the float64-accumulating bf16 reference, the fp32-accumulating one and plain
     float64; norm [P]: what a point's error is divided by (rows with norm 0 must be exactly 0 in ``got`` and are left out);
-    margin: the ref64.Margin of the references; keep: rows to judge at all (colour kernels: off the ReLU kinks)."""
+    margin: the ref64.Margin of the references; keep: rows to judge at all (colour kernels: off the ReLU kinks).
+    second: a second, equally valid fp32 yardstick (the other summation order): the quantity is then judged against the larger of the
+    two rms(e_y) and, independently, the larger of the two max(e_y) -- gate64.gate's kernel_order rule.  The per-point weight
+    gradients need it: there the two correct fp32 emulations refuse EACH OTHER under one yardstick (coarse, g_sdf alone: rms ratio 1.58
+    on dW0 against the limit 1.5; tests/test_ref64_bf16_cpu.py)."""
     threshold = THRESHOLD if threshold is None else threshold
     got, b64, y32, f64 = (t.reshape(t.shape[0], -1).double() for t in (got, b64, y32, f64))
     zero = norm == 0
@@ -51,12 +55,16 @@ def gate(what, got, b64, y32, f64, norm, margin, backward, keep=None, failures=N
         return _done(r, failures, quiet)
     rms = lambda e: float((e ** 2).mean().sqrt()) if e.numel() else 0.0
     bound = 3.0 * float(e_y[kept].max())                                  # "the fp32 bound" of this tensor
+    rms_y = rms(e_y[kept])
+    if second is not None:
+        e_2 = per_point(second.reshape(second.shape[0], -1).double() - b64, nz)
+        bound, rms_y = max(bound, 3.0 * float(e_2[kept].max())), max(rms_y, rms(e_2[kept]))
     effect = max(float(eff[judged].max()), bound)
     moved = kept & ~(e_k <= bound)                                        # kept points that claim the left-out rule (NaN included)
     strict = kept & ~moved
     loose = judged & ~(e_k <= bound)
     flips = e_k[loose]
-    r.update(rms_k=rms(e_k[strict]), rms_y=rms(e_y[kept]), max_k=float(e_k[strict].max()) if bool(strict.any()) else 0.0,
+    r.update(rms_k=rms(e_k[strict]), rms_y=rms_y, max_k=float(e_k[strict].max()) if bool(strict.any()) else 0.0,
              max_y=bound / 3.0, moved=int(moved.sum()) / n_k, loose=int(loose.sum()) / n_j,
              flip=(float(flips.max()) / effect if flips.numel() else 0.0), effect=effect,
              finite=bool(torch.isfinite(got[judged]).all()))

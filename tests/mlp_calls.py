@@ -2,7 +2,8 @@
 tests/test_gemm_float64_gpu.py (fp32 operands), tests/test_gemm_bf16_gpu.py (Net(precision="bf16"): every k_* helper then calls the
 nsa_*_bf16 entry point itself) and, for single kernels, tests/test_grid_float64_gpu.py.  Inputs are explicit fp32 points (colour
 kernels: one sample per ray at z = 0, so x = o exactly); operands come from tests/gemm_cases.py.  The check_* functions are the
-bit-for-bit properties that need no reference, shared by the fp32 and the bf16 suite."""
+bit-for-bit properties that need no reference, shared by the fp32 and the bf16 suite; for the _params entries they cover the
+emission buffer too, region by region (tests/emit_rows.py names the regions and says which are functions of the point alone)."""
 import ctypes
 import os
 import re
@@ -10,6 +11,7 @@ import re
 import numpy as np
 import torch
 
+import emit_rows
 from devcall import ptr, st
 from gemm_cases import colour_inputs, cot, cube_points, scaled
 from helpers import load, params_of, oracle_config
@@ -206,6 +208,34 @@ def k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="plain", 
 
 
 # ------------------------------------------------------------------------------------------------------------------ properties
+def emit_outputs(emit, P, regions):
+    """the emission buffer as outputs of a run: "emit <region>" -> [P, rows] on the host (a point's column as a row)"""
+    return {f"emit {name}": emit[r0:r0 + n, :P].t().contiguous().cpu() for name, (r0, n, _point_only) in regions.items()}
+
+
+def sdf_regions(net, which, tile):
+    gd, _keep, _pk = net.sdf(which, tile)
+    return emit_rows.sdf_regions(gd.n_hidden, tile)
+
+
+def point_only(key):
+    """is this output of a _params run a function of the point alone (untouched by the cotangents)?"""
+    name = key[5:] if key.startswith("emit ") else None
+    return name is not None and (name in ("IN", "H0") or name[0] == "H" or name[:2] == "DA")
+
+
+def _sdf_params_run(net, which, tile, x, gs, gf, gg):
+    out, emit = k_sdf_backward(net, which, tile, x, gs, gf, gg, params=True)
+    out.update(emit_outputs(emit, x.shape[0], sdf_regions(net, which, tile)))
+    return out
+
+
+def _colour_params_run(net, xc, d, normals, feat, g_rgb, grid_grad):
+    out, emit = k_colour_backward(net, xc, d, normals, feat, g_rgb, grid_grad, kind="params")
+    out.update(emit_outputs(emit, xc.shape[0], emit_rows.colour_regions()))
+    return out
+
+
 def backward_runs(net, x, xc, d, normals, feat):
     """name -> f(scale [P]) running one backward kernel with every cotangent of point p multiplied by scale[p]"""
     P = x.shape[0]
@@ -217,12 +247,12 @@ def backward_runs(net, x, xc, d, normals, feat):
             runs[f"sdfnet_backward {which} t{tile}"] = (
                 lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(scaled(b, s) for b in base)))
             runs[f"sdfnet_backward_params {which} t{tile}"] = (
-                lambda s, which=which, tile=tile: k_sdf_backward(net, which, tile, x, *(scaled(b, s) for b in base), params=True)[0])
+                lambda s, which=which, tile=tile: _sdf_params_run(net, which, tile, x, *(scaled(b, s) for b in base)))
     for grid_grad in (0, 1):
         runs[f"colour_backward gg {grid_grad}"] = (
             lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, scaled(g_rgb, s), grid_grad))
         runs[f"colour_backward_params gg {grid_grad}"] = (
-            lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, scaled(g_rgb, s), grid_grad, kind="params")[0])
+            lambda s, grid_grad=grid_grad: _colour_params_run(net, xc, d, normals, feat, scaled(g_rgb, s), grid_grad))
         runs[f"colour_coarse_backward gg {grid_grad}"] = (
             lambda s, grid_grad=grid_grad: k_colour_backward(net, xc, d, normals, feat, scaled(g_rgb, s), grid_grad, kind="coarse",
                                                              g_sdf=scaled(g_sdf, s)))
@@ -231,7 +261,10 @@ def backward_runs(net, x, xc, d, normals, feat):
 
 def check_backwards_point_independent(net, P):
     """every backward kernel at P points, bit for bit: other points' cotangents change nothing (a point whose cotangents are all zero
-    comes out exactly 0), and cotangents x 2^k (k = -40, -13, 17, 40) scale every output by exactly 2^k"""
+    comes out exactly 0), and cotangents x 2^k (k = -40, -13, 17, 40) scale every output by exactly 2^k.  The _params runs also
+    return their emission buffer, one output per region: the cotangent regions (TIN, TH_k, AB_k, FB; colour AB1, AB2, OB) obey the
+    same three rules (scaling exact from 2^-102 on: below, terms lost to fp32 underflow show), the point-only regions (H0, H_k, DA_k; colour
+    IN, H1, H2) must not move at all."""
     x = cube_points(P, 60)
     xc, d, normals, feat = colour_inputs(net, P, 61)
     ones = torch.ones(P).double()
@@ -244,13 +277,34 @@ def check_backwards_point_independent(net, P):
         moved = run(other)
         for k in ref:
             assert torch.equal(moved[k][~odd], ref[k][~odd]), f"{name}: other points' cotangents change d/d {k}"
+            if k.startswith("emit "):
+                if point_only(k):
+                    assert torch.equal(moved[k], ref[k]), f"{name}: the cotangents change the point-only region {k}"
+                else:
+                    assert bool((moved[k][other == 0] == 0).all()), f"{name}: a point with all-zero cotangents has a non-zero {k}"
         for kexp in (-40, -13, 17, 40):
             s = torch.where(odd, torch.full((P,), 2.0 ** kexp).double(), ones)
             out = run(s)
             for k in ref:
-                want = ref[k].double() * s.reshape((-1,) + (1,) * (ref[k].dim() - 1))
-                assert torch.equal(out[k].double(), want), \
-                    f"{name}: cotangents x 2^{kexp} do not scale d/d {k} by 2^{kexp}: {int((out[k].double() != want).sum())} entries"
+                want = ref[k].double() if point_only(k) else ref[k].double() * s.reshape((-1,) + (1,) * (ref[k].dim() - 1))
+                got = out[k].double()
+                if k.startswith("emit "):
+                    # Scaling is exact as long as nothing underflows, in EITHER run.  A Softplus slope of 1e-34 times a tangent is a
+                    # legitimate emission entry (TH_k, and a term of AB_k = sp' acc + e_k); it, or 2^-40 times it, lies below the
+                    # smallest normal fp32 number 2^-126, where an fp32 product loses bits or is flushed.  Such a term moves a sum by up
+                    # to its own size, which a sum below 2^24 x 2^-126 can see: where the entry of either run is below 2^-102 it only
+                    # has to be within 2^-125 (two lost terms; times 2^k if they were lost in the unscaled run), from there on exact.
+                    sk = s.reshape((-1,) + (1,) * (ref[k].dim() - 1))
+                    under = torch.minimum(ref[k].double().abs(), want.abs()) < 2.0 ** -102
+                    off = ((got - want).abs() / sk.clamp_min(1.0).expand_as(got))[under]
+                    assert bool((off <= 2.0 ** -125).all()), \
+                        f"{name}: cotangents x 2^{kexp}: an entry of {k} in the underflow range is off by {float(off.max()):.3e}"
+                    got, want = got[~under], want[~under]
+                    bad = got != want
+                    assert not bool(bad.any()), (f"{name}: cotangents x 2^{kexp} do not scale {k} by 2^{kexp}: {int(bad.sum())} entries, "
+                                                 f"got {got[bad][:4].tolist()} want {want[bad][:4].tolist()}")
+                assert torch.equal(got, want), \
+                    f"{name}: cotangents x 2^{kexp} do not scale d/d {k} by 2^{kexp}: {int((got != want).sum())} entries"
 
 
 def check_forwards_point_independent(net):

@@ -28,7 +28,17 @@ through it), from which ``Margin`` forms the per-point ROUNDING MARGIN: how far 
 nearest rounding boundary (the midpoint of two neighbouring bf16 values), in units of the measured fp32 noise of the vector the
 operand belongs to (class Margin states the unit).  On a point that is kept, two correct implementations take the same rounding
 decisions and agree to working-precision noise; the others may flip (tests/bf16_gate.py).  ``Quant.margin`` is the same distance
-in units of the operand's own bf16 spacing (no knowledge of the noise), kept for the report."""
+in units of the operand's own bf16 spacing (no knowledge of the noise), kept for the report.
+
+``sdf_weight_grads`` / ``colour_weight_grads`` evaluate the same graphs (bit for bit: the same calls in the same order, so d/dx and the
+rounding trace are today's) and return, PER POINT, the gradient of the kernels' objective with respect to every layer's effective
+matrix and bias -- what the MAP kernels' emission rows encode before nsa_emit_gemm sums them over the points (tests/emit_rows.py) --
+and the layer inputs.  Every layer takes a zero-stride per-point leaf [P, out, in] next to its shared matrix (class _LinP / _LinQP:
+the forward ignores the leaf, the backward returns g (x) x to it and applies itself to g and the transposed leaf, so the share of the
+double backward through grad sdf arrives too); the bias gradient is the gradient at the layer's output.  In quant mode the outer
+product is formed from the UNROUNDED vectors: the MAP bodies emit their registers before the GEMM rounds them."""
+import types
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -91,6 +101,7 @@ def rne_bf16(x):
 
 
 FAULTS = ("truncated weights", "unrounded cotangents", "neighbour's operand group", "rounded sdf row")
+WEIGHT_GRAD_FAULTS = ("rounded emission rows",)     # only the per-point weight gradients see it (g (x) x of the rounded vectors)
 
 
 class Quant:
@@ -101,7 +112,7 @@ class Quant:
     fault: None, or one of FAULTS: a deliberately WRONG emulation (tests/test_ref64_bf16_cpu.py: the gate must refuse each)."""
 
     def __init__(self, weights=None, order="natural", fault=None):
-        assert (order in ("natural", "permuted") or order[0] == "permuted") and (fault is None or fault in FAULTS), (order, fault)
+        assert (order in ("natural", "permuted") or order[0] == "permuted") and (fault is None or fault in FAULTS + WEIGHT_GRAD_FAULTS), (order, fault)
         self.weights, self.order, self.fault = weights, order, fault
         self._w, self._perm = {}, {}
         self.trace = []                     # every operand matrix [P, K] as it reached a rounding, in order (Margin)
@@ -215,20 +226,87 @@ class _LinQ(torch.autograd.Function):
         return _LinQ.apply(_RoundQ.apply(g, ctx.q, True), ctx.wr.t().contiguous(), ctx.q), None, None
 
 
-def _lin(params, prefix, h, dtype, quant=None, exact_rows=0):
+class Taps:
+    """What a graph records for the weight gradients.  per_point: every layer gets a zero-stride leaf [P, out, in] (class _LinP);
+    otherwise (whole batch, quant is None) the effective matrix and bias themselves become leaves of the unchanged graph."""
+
+    def __init__(self, per_point=True):
+        self.per_point, self.layers = per_point, []            # layers: (prefix, leaves, layer input, layer output)
+
+    def leaf(self, P, w):
+        return torch.zeros((), dtype=w.dtype).expand(P, *w.shape).requires_grad_(True)
+
+
+class _LinP(torch.autograd.Function):
+    """y = F.linear(x, w, b) exactly; zw [P, out, in] receives the per-point g (x) x, of this product and of every derivative of it"""
+
+    @staticmethod
+    def forward(ctx, x, w, b, zw):
+        ctx.save_for_backward(x, w, zw)
+        return F.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, zw = ctx.saved_tensors
+        gx = _LinP.apply(g, w.t(), None, zw.transpose(1, 2)) if ctx.needs_input_grad[0] else None       # (as autograd: no unneeded GEMM)
+        return gx, None, None, g.unsqueeze(2) * x.unsqueeze(1)
+
+
+class _LinQP(torch.autograd.Function):
+    """_LinQ(_RoundQ(x)) in one node (the same roundings in the same order); zw receives g (x) x of the UNROUNDED vectors"""
+
+    @staticmethod
+    def forward(ctx, x, wr, q, cotangent, zw):
+        ctx.save_for_backward(x, zw)
+        ctx.wr, ctx.q = wr, q
+        return q.matmul(q.round(x, cotangent), wr)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, zw = ctx.saved_tensors
+        # (no GEMM, hence no recorded rounding, where _LinQ's node would not exist: the trace stays sdf_backward's)
+        gx = _LinQP.apply(g, ctx.wr.t().contiguous(), ctx.q, True, zw.transpose(1, 2)) if ctx.needs_input_grad[0] else None
+        if ctx.q.fault == "rounded emission rows":
+            return gx, None, None, None, rne_bf16(g)[0].unsqueeze(2) * rne_bf16(x)[0].unsqueeze(1)
+        return gx, None, None, None, g.unsqueeze(2) * x.unsqueeze(1)
+
+
+def _lin(params, prefix, h, dtype, quant=None, exact_rows=0, taps=None):
     """quant: rows [exact_rows:] are matrix-core rows (bf16 operands), rows [:exact_rows] vector-ALU rows (unrounded)"""
     if quant is None:
         g, v, b = (params[f"{prefix}.{k}"].to(dtype) for k in ("weight_g", "weight_v", "bias"))
-        return F.linear(h, v * (g / v.norm(2, dim=1, keepdim=True)), b)
+        w = v * (g / v.norm(2, dim=1, keepdim=True))
+        if taps is None:
+            return F.linear(h, w, b)
+        if not taps.per_point:
+            w, b = w.detach().requires_grad_(True), b.detach().requires_grad_(True)
+            y = F.linear(h, w, b)
+            taps.layers.append((prefix, (w, b), h, y))
+            return y
+        zw = taps.leaf(h.shape[0], w)
+        y = _LinP.apply(h, w, b, zw)
+        taps.layers.append((prefix, zw, h, y))
+        return y
     w, wr, b = quant.weight(params, prefix, dtype)
     if quant.fault == "rounded sdf row" and exact_rows < w.shape[0]:
         exact_rows = 0
+    assert taps is None or taps.per_point
+    zw = taps.leaf(h.shape[0], w) if taps is not None else None
     parts = []
     if exact_rows:
-        parts.append(F.linear(h, w[:exact_rows], b[:exact_rows]))
+        if zw is None:
+            parts.append(F.linear(h, w[:exact_rows], b[:exact_rows]))
+        else:
+            parts.append(_LinP.apply(h, w[:exact_rows], b[:exact_rows], zw[:, :exact_rows]))
     if exact_rows < w.shape[0]:
-        parts.append(_LinQ.apply(_RoundQ.apply(h, quant, False), wr[exact_rows:], quant) + b[exact_rows:])
-    return torch.cat(parts, dim=-1)
+        if zw is None:
+            parts.append(_LinQ.apply(_RoundQ.apply(h, quant, False), wr[exact_rows:], quant) + b[exact_rows:])
+        else:
+            parts.append(_LinQP.apply(h, wr[exact_rows:], quant, False, zw[:, exact_rows:]) + b[exact_rows:])
+    y = torch.cat(parts, dim=-1)
+    if taps is not None:
+        taps.layers.append((prefix, zw, h, y))
+    return y
 
 
 def weights_of_model(model):
@@ -250,11 +328,11 @@ def weights_of_model(model):
     return out
 
 
-def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None, quant=None):
+def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None, quant=None, taps=None):
     feat = _grid(exact, prefix, x, x0, params[prefix + ".encoding.embeddings"], spec.grid, spec.divide_factor, dtype)
     h = torch.cat((_pe(x, spec.multires), feat), dim=-1)
     for l in range(spec.n_linear):
-        h = _lin(params, f"{prefix}.lin{l}", h, dtype, quant, exact_rows=1 if l == spec.n_linear - 1 else 0)
+        h = _lin(params, f"{prefix}.lin{l}", h, dtype, quant, exact_rows=1 if l == spec.n_linear - 1 else 0, taps=taps)
         if l < spec.n_linear - 1:
             h = F.softplus(h, beta=100)
     return h
@@ -263,14 +341,14 @@ def _sdf_net(params, prefix, spec, x, x0, dtype, exact=None, quant=None):
 NETS = {"coarse": "implicit_network.coarse", "fine": "implicit_network.fine"}
 
 
-def _sdf_graph(params, cfg, x0, nets, dtype, exact=None, quant=None):
+def _sdf_graph(params, cfg, x0, nets, dtype, exact=None, quant=None, taps=None):
     assert quant is None or exact is None, "quant: linearised grids only"
     if quant is not None:
         quant.reset(x0.shape[0])
     x = x0.detach().to(dtype).requires_grad_(True)
     sdf, feat, grad = 0, 0, 0
     for which in nets:
-        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype, exact, quant)
+        out = _sdf_net(params, NETS[which], getattr(cfg, which), x, x0, dtype, exact, quant, taps)
         s = out[:, 0]
         (g,) = torch.autograd.grad(s, x, torch.ones_like(s), create_graph=True)
         sdf, feat, grad = sdf + s, feat + out[:, 1:], grad + g
@@ -306,6 +384,66 @@ def sdf_backward(params, cfg, x0, g_sdf=None, g_feat=None, g_grad=None, nets=("c
     return gx
 
 
+def _weight_grads(obj, ins, taps):
+    """-> (d/d ins, the weight gradients of ``taps``: per layer [P, out, in + 1] = [dW_l | db_l] per point, resp. (whole batch)
+    [out, in + 1]; the layer inputs [P, in])"""
+    acts = [h.detach() for _p, _l, h, _y in taps.layers]
+    if not torch.is_tensor(obj):
+        shape = lambda l, h, y: ((h.shape[0],) if taps.per_point else ()) + (y.shape[1], h.shape[1] + 1)
+        return [torch.zeros_like(t).detach() for t in ins], [torch.zeros(shape(l, h, y), dtype=h.dtype) for _p, l, h, y in taps.layers], acts
+    n = len(taps.layers)
+    if taps.per_point:
+        gs = torch.autograd.grad(obj, list(ins) + [l for _p, l, _h, _y in taps.layers] + [y for _p, _l, _h, y in taps.layers], allow_unused=True)
+        gi, gw, gb = gs[:len(ins)], gs[len(ins):len(ins) + n], gs[len(ins) + n:]
+    else:
+        gs = torch.autograd.grad(obj, list(ins) + [l[0] for _p, l, _h, _y in taps.layers] + [l[1] for _p, l, _h, _y in taps.layers], allow_unused=True)
+        gi, gw, gb = gs[:len(ins)], gs[len(ins):len(ins) + n], gs[len(ins) + n:]
+    rows = []
+    for (_p, _l, h, y), w, b in zip(taps.layers, gw, gb):
+        lead = (h.shape[0],) if taps.per_point else ()
+        w = torch.zeros(lead + (y.shape[1], h.shape[1]), dtype=h.dtype) if w is None else w
+        b = torch.zeros(lead + (y.shape[1],), dtype=h.dtype) if b is None else b
+        rows.append(torch.cat((w, b.unsqueeze(-1)), dim=-1))
+    return [torch.zeros_like(t).detach() if g is None else g for g, t in zip(gi, ins)], rows, acts
+
+
+def sdf_weight_grads(params, cfg, x0, which, g_sdf=None, g_feat=None, g_grad=None, dtype=F64, quant=None, per_point=True):
+    """The network ``which`` under the objective of sdf_backward -> namespace(x = d/dx [P,3] (sdf_backward's, bit for bit),
+    rows = per layer [P, out, in + 1]: the point's [dW_l | db_l] with respect to the EFFECTIVE matrix and bias (features in the
+    reference's order), acts = per layer its input [P, in] (acts[0]: the first-layer input, acts[k]: h_k)).
+    per_point = False (quant is None): rows = the whole batch's [out, in + 1], from the unchanged graph with the matrices as leaves."""
+    taps = Taps(per_point)
+    x, sdf, feat, grad = _sdf_graph(params, cfg, x0, (which,), dtype, None, quant, taps)
+    (gx,), rows, acts = _weight_grads(_sdf_objective(sdf, feat, grad, g_sdf, g_feat, g_grad, dtype), (x,), taps)
+    return types.SimpleNamespace(x=gx, rows=rows, acts=acts)
+
+
+def colour_weight_grads(params, cfg, x0, normals, dirs, feats, g_rgb, grid_grad=1, dtype=F64, quant=None, per_point=True):
+    """The colour network under g_rgb . rgb -> namespace(ins = colour_backward's dict, bit for bit; rows, acts as sdf_weight_grads)"""
+    taps = Taps(per_point)
+    ins, rgb = _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, quant=quant, taps=taps)
+    gs, rows, acts = _weight_grads((g_rgb.to(dtype) * rgb).sum(), ins, taps)
+    return types.SimpleNamespace(ins=dict(zip(("x", "normals", "dirs", "feat"), gs)), rows=rows, acts=acts)
+
+
+def sdf_first_layer_input(params, cfg, x0, which, dtype=F64):
+    """[PE(x) | grid features] of the network ``which`` [P, 39 + L C] with the GRID ITSELF in ``dtype`` (grid = "exact").  acts[0] of
+    sdf_weight_grads carries the linearisation's f0, the C oracle's fp32 features promoted: right for everything downstream, but as
+    a reference OF the features it would give an fp32 evaluation an error of exactly 0 there."""
+    spec, x = getattr(cfg, which), x0.detach().to(dtype)
+    with torch.no_grad():
+        feat = ExactGrids().features(NETS[which], x, x0, params[NETS[which] + ".encoding.embeddings"], spec.grid, spec.divide_factor, dtype)
+        return torch.cat((_pe(x, spec.multires), feat), dim=-1)
+
+
+def colour_first_layer_input(params, cfg, x0, normals, dirs, feats, dtype=F64):
+    """[x | PE(d) | n | feature | colour grid features] [P, 129] with the grid itself in ``dtype`` (see sdf_first_layer_input)"""
+    x, n, d, f = (t.detach().to(dtype) for t in (x0, normals, dirs, feats))
+    with torch.no_grad():
+        gf = ExactGrids().features("colour", x, x0, params["rendering_network.encoding.embeddings"], cfg.colour_grid, cfg.colour_divide_factor, dtype)
+        return torch.cat([x, _pe(d, cfg.multires_view), n, f, gf], dim=-1)
+
+
 def sdf_table_grad(params, cfg, x0, which, g_sdf=None, g_feat=None, g_grad=None, dtype=F64):
     """grid="exact": -> (d/dx [P,3], d/d table [rows, C] of the network ``which``, plan).  The table gradient is the value path plus
     the table's share of the double backward through grad sdf.  plan.record lists what reached the grid, in order: ("first", g) for
@@ -321,7 +459,7 @@ def sdf_table_grad(params, cfg, x0, which, g_sdf=None, g_feat=None, g_grad=None,
     return gx, gt, plan
 
 
-def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact=None, quant=None):
+def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact=None, quant=None, taps=None):
     assert quant is None or exact is None, "quant: linearised grids only"
     if quant is not None:
         quant.reset(x0.shape[0])
@@ -331,7 +469,7 @@ def _colour_graph(params, cfg, x0, normals, dirs, feats, grid_grad, dtype, exact
         gf = gf.detach()
     h = torch.cat([x, _pe(d, cfg.multires_view), n, f, gf], dim=-1)
     for l in range(cfg.colour_n_linear):
-        h = _lin(params, f"rendering_network.lin{l}", h, dtype, quant, exact_rows=3 if l == cfg.colour_n_linear - 1 else 0)
+        h = _lin(params, f"rendering_network.lin{l}", h, dtype, quant, exact_rows=3 if l == cfg.colour_n_linear - 1 else 0, taps=taps)
         if l < cfg.colour_n_linear - 1:
             if quant is not None:         # the ReLU kinks of THIS graph (its pre-activations differ from the unrounded ones by a bf16 effect)
                 quant.relu_margin = torch.minimum(quant.relu_margin, h.detach().abs().amin(1).double())

@@ -22,6 +22,9 @@ bit-identity is the right demand and is what is asserted.  (coarse, 32) recomput
 the stored one in the MAP kernel (the fp32 suite's LDS_JACOBIAN_ONLY_IN_MAP: other sums, 143 of 4 123 points differ): that pair
 goes through the gate.
 
+EMISSION ROWS of the _params twins (section "emission rows"): per point and per layer the [dW_l | db_l] they encode against ref64's
+per-point weight gradients in quant mode, both fp32 summation orders as yardsticks; measured figures in DESIGN 7.
+
 MEASURED on the MI355X (N = 4 123, threshold 3; e_k, e_y divided by the float64 output's norm, floor 1, or by c_p):
 (ranges over tilings, accumulate, grid_grad and cotangent families; `cases` = how many gate lines a row sums up)
 | kernel: output | cases | e_k rms | e_k max | e_y rms | e_y max | kept share | loose share (max) | flip / effect (max) |
@@ -58,11 +61,12 @@ import torch
 
 import bf16_cases as C
 import bf16_gate as G
+import emit_rows
 import ref64
 from devcall import st
 from gemm_cases import cot
-from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, fn, k_colour_backward, k_colour_forward,
-                       k_sdf_backward, k_sdf_forward, k_sdf_pair, long_inputs, persistent_sweep, to_hl)
+from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, emit_outputs, fn, k_colour_backward,
+                       k_colour_forward, k_sdf_backward, k_sdf_forward, k_sdf_pair, long_inputs, persistent_sweep, sdf_regions, to_hl)
 
 pytestmark = pytest.mark.gpu
 
@@ -324,6 +328,10 @@ def test_sdf_params_bf16_data_path_and_padding(net, refs, which, tile, capsys):
         end = -(-P // tile) * tile
         assert bool((emit[:, P:end] == 0).all()), f"sdfnet_backward_params_bf16 {which} t{tile} P={P}: padding columns are not 0"
         assert bool(torch.isfinite(emit[:, :P]).all()), f"sdfnet_backward_params_bf16 {which} t{tile} P={P}: non-finite emission rows"
+        if P == N:           # the emission columns of a prefix are the big run's, bit for bit
+            for n in PREFIXES:
+                small = k_sdf_backward(net, which, tile, x[:n].contiguous(), gs[:n], gf[:n], gg[:n], params=True)[1]
+                assert torch.equal(small[:, :n], emit[:, :n]), f"sdfnet_backward_params_bf16 {which} t{tile}: P = {n} changes the emission columns"
         del emit
         outs[P] = out["x"]
         plain = k_sdf_backward(net, which, tile, x[:P].contiguous(), gs[:P], gf[:P], gg[:P])["x"]
@@ -352,6 +360,99 @@ def test_colour_params_bf16_data_path_is_bit_identical_and_padding_zero(net, ref
         assert bool((emit[:, P:end] == 0).all()), "colour_backward_params_bf16: padding columns are not 0"
         for k in plain:
             assert torch.equal(out[k], plain[k]), f"colour_backward_params_bf16 grid_grad {grid_grad}: d/d {k} differs"
+        if P == N:           # the emission columns of a prefix are the big run's, bit for bit
+            for n in PREFIXES:
+                small = k_colour_backward(net, *(t[:n].contiguous() for t in ins), g_rgb[:n].contiguous(), grid_grad, kind="params")[1]
+                assert torch.equal(small[:, :n], emit[:, :n]), f"colour_backward_params_bf16 grid_grad {grid_grad}: P = {n} changes the emission columns"
+
+
+# ------------------------------------------------------------------------------------------------------------------ emission rows
+# The per-point vectors of the _params twins that nsa_emit_gemm multiplies into dW and db, judged BEFORE that sum (one wrong column is
+# one term among thousands after it): per point and per layer the [dW_l | db_l] they encode (tests/emit_rows.py, production's row
+# maps) against ref64's per-point weight gradients in quant mode -- the graphs of the d/dx cases, hence their Margin and kept sets --
+# through the gate with backward = True and BOTH fp32 summation orders as yardsticks (bf16_gate.gate, ``second``); the Softplus / ReLU
+# outputs H_k as forward quantities; H0 / IN, which no bf16 operand enters, through the fp32 suite's gate.  The references of a case
+# are built once, serve both tilings and are dropped (some GB for the fine network).  The MAP kernels are not persistent (one tile
+# per wave), so there is no sweep to run past; the production tie of the helper is the fp32 suite's (nsa_emit_gemm has no bf16 twin).
+def _emission_gates(what, r, c, point, acts, keep, fails):
+    for l, got in enumerate(point):
+        k = C.layer(l)
+        assert got.shape == r.b64[k].shape, (k, got.shape, r.b64[k].shape)
+        G.gate(f"{what}: {k}", got, r.b64[k], r.y32[k], r.f64[k], c, r.margin, True, keep, failures=fails, second=r.perm[k])
+    for k in range(1, len(acts)):
+        b64 = r.b64[f"H{k}"]
+        G.gate(f"{what}: H{k}", acts[k], b64, r.y32[f"H{k}"], r.f64[f"H{k}"], G.fwd_norm(b64), r.margin, False, keep, failures=fails)
+
+
+@pytest.mark.parametrize("which", ["coarse", "fine"])
+def test_sdf_emission_rows_bf16_vs_float64(net, refs, which, capsys):
+    """nsa_sdfnet_backward_params_bf16 at both tilings, every cotangent family (tests/test_gemm_float64_gpu.py::
+    test_sdf_emission_rows_vs_float64 states the regions): the gates above; FB is g_feat itself; TIN, TH_k, AB_k, FB are exactly 0 at
+    points with all-zero cotangents and TIN, TH_k everywhere without g_grad; the point-only regions H0, H_k, DA_k are bit-identical
+    across the families."""
+    x, fam = refs.inp.xb, refs.inp.fam
+    cases = C.weight_grad_cases(net.params, net.cfg, i=refs.inp)
+    spec = getattr(net.cfg, which).grid
+    L, Cdim = spec.num_levels, spec.level_dim
+    h0 = tuple(ref64.sdf_first_layer_input(net.params, net.cfg, x, which, dt) for dt in (torch.float64, torch.float32))
+    fails, gate64_fails, first = [], [], {}
+    with capsys.disabled():
+        print()
+        for name, (gs, gf, gg, c) in fam.items():
+            r = C.refs(cases[f"weight gradients {which}: {name}"][0], refs.weights)
+            for tile in (16, 32):
+                regions = sdf_regions(net, which, tile)
+                NH = sum(1 for k in regions if k.startswith("AB"))
+                _out, emit = k_sdf_backward(net, which, tile, x, gs, gf, gg, params=True)
+                cols = emit_outputs(emit, N, regions)
+                for k, v in cols.items():
+                    if regions[k[5:]][2]:
+                        assert torch.equal(v, first.setdefault((tile, k), v)), f"{which} t{tile}, {name}: the cotangents change the point-only region {k}"
+                    else:
+                        assert bool((v[c == 0] == 0).all()), f"{which} t{tile}, {name}: {k} is not 0 at a point with all-zero cotangents"
+                assert torch.equal(cols["emit FB"], torch.zeros(N, 64) if gf is None else gf), f"{which} t{tile}, {name}: FB is not g_feat"
+                if gg is None:
+                    assert all(not bool(cols[k].any()) for k in cols if k[5:7] in ("TI", "TH")), f"{which} t{tile}, {name}: a tangent without g_grad"
+                acts = emit_rows.sdf_activations(emit, N, L, Cdim, NH, tile)
+                _emission_gates(f"emission rows bf16 {which} t{tile}: {name}", r, c, emit_rows.sdf_point_grads(emit, gs, N, L, Cdim, NH, tile),
+                                acts, None, fails)
+                if name == "all three x c_p":
+                    emit_rows.gate_first_layer_input(f"emission rows bf16 {which} t{tile}: H0", acts[0], h0, L * Cdim, None, gate64_fails)
+                del emit
+            del r
+    assert not gate64_fails, [f["what"] for f in gate64_fails]
+    _done(fails)
+
+
+@pytest.mark.parametrize("grid_grad", [0, 1])
+def test_colour_emission_rows_bf16_vs_float64(net, refs, grid_grad, capsys):
+    """nsa_colour_backward_params_bf16: the gates above off the ReLU kinks; AB1, AB2, OB exactly 0 at points with all-zero
+    cotangents; IN, H1, H2 bit-identical for the other grid_grad and another g_rgb"""
+    i = refs.inp
+    ins = (i.x, i.d, i.normals, i.feat)
+    case = C.weight_grad_cases(net.params, net.cfg, i=i)[f"weight gradients colour grid_grad {grid_grad}"]
+    r = C.refs(case[0], refs.weights)
+    keep = C.kink_keep(r)
+    regions = emit_rows.colour_regions()
+    spec = net.cfg.colour_grid
+    fails, gate64_fails = [], []
+    with capsys.disabled():
+        print()
+        _out, emit = k_colour_backward(net, *ins, i.g_rgb, grid_grad, kind="params")
+        cols = emit_outputs(emit, N, regions)
+        other = emit_outputs(k_colour_backward(net, *ins, C.scaled(cot(N, 16, (3,)), i.c), 1 - grid_grad, kind="params")[1], N, regions)
+        for k, v in cols.items():
+            if regions[k[5:]][2]:
+                assert torch.equal(v, other[k]), f"colour grid_grad {grid_grad}: g_rgb or grid_grad change the point-only region {k}"
+            else:
+                assert bool((v[i.c == 0] == 0).all()), f"colour grid_grad {grid_grad}: {k} is not 0 at a point with all-zero cotangents"
+        acts = emit_rows.colour_activations(emit, N)
+        _emission_gates(f"emission rows bf16 colour grid_grad {grid_grad}", r, i.c, emit_rows.colour_point_grads(emit, N), acts, keep, fails)
+        first = tuple(ref64.colour_first_layer_input(net.params, net.cfg, i.x, i.normals, i.d, i.feat, dt) for dt in (torch.float64, torch.float32))
+        emit_rows.gate_first_layer_input(f"emission rows bf16 colour grid_grad {grid_grad}: IN", acts[0], first, spec.num_levels * spec.level_dim,
+                                         keep, gate64_fails)
+    assert not gate64_fails, [f["what"] for f in gate64_fails]
+    _done(fails)
 
 
 # ------------------------------------------------------------------------------------------------------------------ properties

@@ -12,16 +12,20 @@ alone and all three at independent scales; g_sdf alone at 2^20..2^40 (the accumu
 operand vector is zero); weights with max |w| in [64, 127.9] and rows below 2^-11.  Bit-for-bit properties that need no reference:
 point independence (other points' inputs changed, ragged P) and scale equivariance of the backwards (cotangents x 2^k).
 Inputs are explicit fp32 points (colour kernels: one sample per ray at z = 0, so x = o exactly), identical for kernel and references.
-The gate is tests/gate64.py, the kernel calls tests/mlp_calls.py, the operands tests/gemm_cases.py."""
+The gate is tests/gate64.py, the kernel calls tests/mlp_calls.py, the operands tests/gemm_cases.py.
+The EMISSION ROWS of the _params kernels (the per-point vectors nsa_emit_gemm multiplies into dW and db) are held the same way: per
+point and per layer, the [dW_l | db_l] they encode (tests/emit_rows.py, production's row maps) against ref64.sdf_weight_grads /
+colour_weight_grads in float64, the fp32 evaluation of the same graph as the yardstick (section "emission rows" below)."""
 import numpy as np
 import pytest
 import torch
 
+import emit_rows
 import ref64
 from gate64 import fwd_norm, gate
 from gemm_cases import KINK, N_BIG, SMALL_P, colour_inputs, cot, cube_points, scaled, scales, sdf_families
-from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, k_colour_backward, k_colour_forward,
-                       k_sdf_backward, k_sdf_forward, k_sdf_pair)
+from mlp_calls import (Net, check_backwards_point_independent, check_forwards_point_independent, emit_outputs, k_colour_backward,
+                       k_colour_forward, k_sdf_backward, k_sdf_forward, k_sdf_pair, sdf_regions)
 
 pytestmark = pytest.mark.gpu
 
@@ -210,11 +214,13 @@ def test_sdf_params_kernel_data_path_and_padding(net, which, tile, capsys):
     fam = sdf_families(N_BIG)
     gs, gf, gg, c = fam["all three x c_p"]
     big, smalls = None, []
+    columns = {}
     for P in (33, 4097, N_BIG):
         x = x_big[:P].contiguous()
         out, emit = k_sdf_backward(net, which, tile, x, gs[:P], gf[:P], gg[:P], params=True)
         end = -(-P // tile) * tile
         assert bool((emit[:, P:end] == 0).all()), f"sdfnet_backward_params {which} t{tile} P={P}: padding columns are not 0"
+        columns[P] = emit[:, :P].cpu()
         del emit
         if (which, tile) not in LDS_JACOBIAN_ONLY_IN_MAP:
             plain = k_sdf_backward(net, which, tile, x, gs[:P], gf[:P], gg[:P])["x"]
@@ -225,6 +231,12 @@ def test_sdf_params_kernel_data_path_and_padding(net, which, tile, capsys):
             smalls.append(out["x"])
         else:
             big = out["x"]
+    # the emission columns of a prefix are the big run's, bit for bit (every SMALL_P: one tile, a ragged one, across tile borders)
+    for P in SMALL_P:
+        if P not in columns:
+            columns[P] = k_sdf_backward(net, which, tile, x_big[:P].contiguous(), gs[:P], gf[:P], gg[:P], params=True)[1][:, :P].cpu()
+    for P, small in columns.items():
+        assert torch.equal(small, columns[N_BIG][:, :P]), f"sdfnet_backward_params {which} t{tile}: P = {P} changes the emission columns"
     if (which, tile) in LDS_JACOBIAN_ONLY_IN_MAP:
         for small in smalls:
             assert torch.equal(small, big[:small.shape[0]]), f"sdfnet_backward_params: P = {small.shape[0]} changes d/dx"
@@ -245,6 +257,221 @@ def test_colour_params_kernel_data_path_is_bit_identical_and_padding_zero(net, P
         assert bool((emit[:, P:end] == 0).all()), "colour_backward_params: padding columns are not 0"
         for k in plain:
             assert torch.equal(out[k], plain[k]), f"colour_backward_params grid_grad {grid_grad}: d/d {k} differs"
+        if P == N_BIG:       # the emission columns of a prefix are the big run's, bit for bit
+            for n in SMALL_P:
+                small = k_colour_backward(net, xc[:n].contiguous(), d[:n].contiguous(), normals[:n].contiguous(), feat[:n].contiguous(),
+                                          g_rgb[:n].contiguous(), grid_grad, kind="params")[1]
+                assert torch.equal(small[:, :n], emit[:, :n]), f"colour_backward_params grid_grad {grid_grad}: P = {n} changes the emission columns"
+
+
+# ------------------------------------------------------------------------------------------------------------------ emission rows
+# A wrong lane partner, scale hint or accumulator scaling changes ONE point's emission column; after nsa_emit_gemm that is one term among
+# thousands in every weight-gradient element and no per-tensor tolerance sees it.  So the rows are judged before the sum: per point and
+# per layer, [dW_l | db_l] as the rows encode it (emit_rows.sdf_point_grads / colour_point_grads: sdf_flat_grad / colour_flat_grad
+# without the sum, on production's row maps) through gate64.gate against ref64's per-point weight gradients, norm c_p.  The d/dx
+# identity of the _params twins does not cover them: AB_k, DA_k and TH_k leave the registers at other places of the chain than g_x, and
+# the row index arithmetic (Emitter::hid, 2 slot + half, 4 slot + quarter) has nothing to do with g_x.
+# Every _params kernel reads the grid Jacobian from LDS, in both tilings and for both networks (kJacLds = (NH > 1) || MAP): the one
+# documented second operation order of this file (LDS_JACOBIAN_ONLY_IN_MAP) is a difference between the plain and the MAP kernel of
+# (coarse, 32), not between two valid orders of the MAP kernel, and ref64 has no evaluation in it; the rows have the one yardstick.
+# None of the MAP kernels is persistent or grid-strided (one tile per wave, render_sdfnet.hip / render_sdfnet4.hip / render_colour.hip
+# launch ceil(tiles / waves) workgroups), so there is no sweep to run past.
+N_WG = 2075                                     # 64 x 32 + 27 = 129 x 16 + 11: ragged for both tilings
+
+
+class WeightGradRefs:
+    """ref64's per-point weight gradients at the first N_WG points of the suite's seeds, float64 and the fp32 yardstick: built once per
+    (network, family), shared by the two tilings, left unchanged (the yardstick is kept in fp32, the rest in float64)"""
+
+    def __init__(self, net):
+        self.net, self._sdf, self._colour, self._col_in = net, {}, {}, None
+        self.x = cube_points(N_BIG, 5)[:N_WG].contiguous()
+        self.fam = {name: tuple(None if t is None else t[:N_WG].contiguous() for t in f) for name, f in sdf_families(N_BIG).items()}
+
+    def sdf(self, which, name):
+        if (which, name) not in self._sdf:
+            gs, gf, gg, _c = self.fam[name]
+            self._sdf[which, name] = tuple(ref64.sdf_weight_grads(self.net.params, self.net.cfg, self.x, which, gs, gf, gg, dtype=dt)
+                                           for dt in (torch.float64, torch.float32))
+        return self._sdf[which, name]
+
+    def colour_inputs(self):
+        """-> x, d, normals, feat, g_rgb, c, keep (the suite's kink rule)"""
+        if self._col_in is None:
+            from oracle import render_ref as R
+            x, d, normals, feat = (t[:N_WG].contiguous() for t in colour_inputs(self.net, N_BIG, 7))
+            c = scales(N_BIG, 8)[:N_WG]
+            g_rgb = scaled(cot(N_BIG, 9, (3,)), scales(N_BIG, 8))[:N_WG].contiguous()
+            keep = R.colour_relu_margin(self.net.params, self.net.cfg, x, normals, d, feat) >= KINK
+            assert int((~keep).sum()) <= N_WG // 100, int((~keep).sum())
+            self._col_in = (x, d, normals, feat, g_rgb, c, keep)
+        return self._col_in
+
+    def sdf_input(self, which):
+        """the first-layer input with the grid itself in float64 / fp32 (ref64.sdf_first_layer_input says why)"""
+        if ("in", which) not in self._sdf:
+            self._sdf["in", which] = tuple(ref64.sdf_first_layer_input(self.net.params, self.net.cfg, self.x, which, dt)
+                                           for dt in (torch.float64, torch.float32))
+        return self._sdf["in", which]
+
+    def colour_input(self):
+        if "in" not in self._colour:
+            x, d, normals, feat, _g, _c, _keep = self.colour_inputs()
+            self._colour["in"] = tuple(ref64.colour_first_layer_input(self.net.params, self.net.cfg, x, normals, d, feat, dt)
+                                       for dt in (torch.float64, torch.float32))
+        return self._colour["in"]
+
+    def colour(self, grid_grad):
+        if grid_grad not in self._colour:
+            x, d, normals, feat, g_rgb, _c, _keep = self.colour_inputs()
+            self._colour[grid_grad] = tuple(ref64.colour_weight_grads(self.net.params, self.net.cfg, x, normals, d, feat, g_rgb, grid_grad,
+                                                                      dtype=dt) for dt in (torch.float64, torch.float32))
+        return self._colour[grid_grad]
+
+
+@pytest.fixture(scope="module")
+def wg(net):
+    return WeightGradRefs(net)
+
+
+def _tie_to_production(what, got, point, magnitude):
+    """the sum over the points of the helper's per-point gradients is production's flat gradient of the same buffer, to
+    test_mapping_gpu.py::test_emit_gemm_vs_float64's bound: error / sum |a b| < 1e-6 per element"""
+    want, scale = emit_rows.flat(point).sum(0), emit_rows.flat(magnitude).sum(0)
+    err = float(((got.double().cpu() - want).abs() / scale.clamp_min(1e-300)).max())
+    print(f"  {what}: production's flat gradient vs the sum of the per-point gradients, max error / sum |a b| {err:.2e}")
+    assert got.shape == want.shape and err < 1e-6, (what, err)
+
+
+@pytest.mark.parametrize("which,tile", [("coarse", 16), ("coarse", 32), ("fine", 16), ("fine", 32)])
+def test_sdf_emission_rows_vs_float64(net, wg, which, tile, capsys):
+    """nsa_sdfnet_backward_params, every cotangent family (the single-cotangent ones separate the AB . H share from the DA . T share):
+      * per layer, the point's [dW_l | db_l] from the emission rows within the gate of float64, norm c_p;
+      * the value-path regions H0, H_k directly, per point with fwd_norm, against the float64 activations (an error there could hide
+        behind a small AB);
+      * FB is g_feat itself (the last layer's db[p] is the cotangent: the yardstick's error is exactly 0, so equality);
+      * at points with all-zero cotangents TIN, TH_k, AB_k and FB are exactly 0 (DA_k is not a cotangent region, below);
+      * COTANGENT INDEPENDENCE, from the kernel bodies (sdfnet_bwd_body.inc, sdfnet4_bwd_body.inc, hidden_forward*, reverse_pass*):
+        H0, H_1..H_NH and DA_1..DA_NH are functions of the point alone (DA_k = sp'(a_k) dh_k comes from the reverse pass that starts at
+        the packed sdf row; no cotangent enters it) and must be bit-identical across the six families; TIN and TH_k are linear in
+        g_grad (exactly 0 without it), AB_k in all three cotangents, FB = g_feat;
+      * the helper's sum over the points is production's sdf_flat_grad of the same buffer (nsa_emit_row + nsa_emit_gemm)."""
+    from nicer_slam_amd.fused import mapping
+    spec = getattr(net.cfg, which).grid
+    L, C = spec.num_levels, spec.level_dim
+    regions = sdf_regions(net, which, tile)
+    NH = sum(1 for k in regions if k.startswith("AB"))
+    P, x = N_WG, wg.x
+    fails, first = [], None
+    with capsys.disabled():
+        print()
+        for name, (gs, gf, gg, c) in wg.fam.items():
+            r64, r32 = wg.sdf(which, name)
+            _out, emit = k_sdf_backward(net, which, tile, x, gs, gf, gg, params=True)
+            cols = emit_outputs(emit, P, regions)
+            zero = c == 0
+            for k, v in cols.items():
+                if regions[k[5:]][2]:
+                    if first is not None:
+                        assert torch.equal(v, first[k]), f"{which} t{tile}, {name}: the cotangents change the point-only region {k}"
+                else:
+                    assert bool((v[zero] == 0).all()), f"{which} t{tile}, {name}: {k} is not 0 at a point with all-zero cotangents"
+            want_fb = torch.zeros(P, 64) if gf is None else gf
+            assert torch.equal(cols["emit FB"], want_fb), f"{which} t{tile}, {name}: FB is not g_feat"
+            if gg is None:
+                assert all(not bool(cols[k].any()) for k in cols if k[5:7] in ("TI", "TH")), f"{which} t{tile}, {name}: a tangent without g_grad"
+            point = emit_rows.sdf_point_grads(emit, gs, P, L, C, NH, tile)
+            assert len(point) == len(r64.rows) == NH + 1
+            for l, (got, r, y) in enumerate(zip(point, r64.rows, r32.rows)):
+                assert got.shape == r.shape, (l, got.shape, r.shape)
+                gate(f"emission rows {which} t{tile}: {name}: [dW{l} | db{l}]", got, r, y, c, failures=fails)
+            if first is None:
+                first = cols
+                acts = emit_rows.sdf_activations(emit, P, L, C, NH, tile)
+                emit_rows.gate_first_layer_input(f"emission rows {which} t{tile}: H0", acts[0], wg.sdf_input(which), L * C, None, fails)
+                for k in range(1, NH + 1):
+                    gate(f"emission rows {which} t{tile}: H{k}", acts[k], r64.acts[k], r32.acts[k], fwd_norm(r64.acts[k]), failures=fails)
+                # production on the same buffer: two more rows for nsa_emit_row, the columns past the last tile zero (mapping.new_emit)
+                buf = torch.cat((emit, torch.zeros(2, emit.shape[1], device="cuda")))
+                buf[:, -(-P // tile) * tile:] = 0
+                flat = mapping.sdf_flat_grad(buf, gs.cuda().contiguous(), P, L, C, NH=NH, tile=tile)
+                torch.cuda.synchronize()
+                _tie_to_production(f"sdf_flat_grad {which} t{tile}", flat, point, emit_rows.sdf_point_grads(emit, gs, P, L, C, NH, tile, True))
+            del emit
+    assert not fails, [f["what"] for f in fails]
+
+
+@pytest.mark.parametrize("grid_grad", [0, 1])
+def test_colour_emission_rows_vs_float64(net, wg, grid_grad, capsys):
+    """nsa_colour_backward_params: per layer the point's [dW_l | db_l] from the emission rows within the gate of float64 (norm c_p,
+    the suite's kink rule), IN, H1, H2 directly with fwd_norm; at points with zero cotangents AB1, AB2, OB are exactly 0.
+    COTANGENT INDEPENDENCE (colour_bwd_body.inc): IN, H1 = relu(a1), H2 = relu(a2) are functions of the point alone -- bit-identical
+    for both grid_grad and for another g_rgb; AB1, AB2, OB are linear in g_rgb.  The helper's sum over the points is production's
+    colour_flat_grad of the same buffer."""
+    from nicer_slam_amd.fused import mapping
+    x, d, normals, feat, g_rgb, c, keep = wg.colour_inputs()
+    r64, r32 = wg.colour(grid_grad)
+    regions = emit_rows.colour_regions()
+    P = N_WG
+    fails = []
+    with capsys.disabled():
+        print(f"\n  colour: {int((~keep).sum())} of {P} points within {KINK} of a ReLU kink left out")
+        _out, emit = k_colour_backward(net, x, d, normals, feat, g_rgb, grid_grad, kind="params")
+        cols = emit_outputs(emit, P, regions)
+        _o2, emit2 = k_colour_backward(net, x, d, normals, feat, scaled(cot(P, 16, (3,)), c), 1 - grid_grad, kind="params")
+        other = emit_outputs(emit2, P, regions)
+        del emit2
+        for k, v in cols.items():
+            if regions[k[5:]][2]:
+                assert torch.equal(v, other[k]), f"colour grid_grad {grid_grad}: g_rgb or grid_grad change the point-only region {k}"
+            else:
+                assert bool((v[c == 0] == 0).all()), f"colour grid_grad {grid_grad}: {k} is not 0 at a point with all-zero cotangents"
+        point = emit_rows.colour_point_grads(emit, P)
+        for l, (got, r, y) in enumerate(zip(point, r64.rows, r32.rows)):
+            assert got.shape == r.shape, (l, got.shape, r.shape)
+            gate(f"emission rows colour grid_grad {grid_grad}: [dW{l} | db{l}]", got, r, y, c, keep, failures=fails)
+        acts = emit_rows.colour_activations(emit, P)
+        spec = net.cfg.colour_grid
+        emit_rows.gate_first_layer_input(f"emission rows colour grid_grad {grid_grad}: IN", acts[0], wg.colour_input(), spec.num_levels * spec.level_dim, keep, fails)
+        for k in (1, 2):
+            gate(f"emission rows colour grid_grad {grid_grad}: H{k}", acts[k], r64.acts[k], r32.acts[k], fwd_norm(r64.acts[k]), keep, failures=fails)
+        buf = emit.clone()
+        buf[:, -(-P // 32) * 32:] = 0
+        flat = mapping.colour_flat_grad(buf)
+        torch.cuda.synchronize()
+        _tie_to_production(f"colour_flat_grad grid_grad {grid_grad}", flat, point, emit_rows.colour_point_grads(emit, P, True))
+    assert not fails, [f["what"] for f in fails]
+
+
+@pytest.mark.parametrize("P", [1, 4095, 4097])
+def test_emit_row_is_exact(P):
+    """nsa_emit_row (the ones row and the g_sdf row of sdf_flat_grad, with the Morton order gather): dst[p] = src[order[p]], src[p] or
+    fill for p < P and 0 in [P, n), bit for bit against torch indexing; bad arguments are refused without a launch"""
+    from devcall import st
+    from nicer_slam_amd._native import lib
+    from nicer_slam_amd.fused.mapping import emit_ld
+    g = torch.Generator().manual_seed(40 + P)
+    n = emit_ld(P)
+    src = (torch.randn(P, generator=g) * torch.exp2(torch.randint(-60, 41, (P,), generator=g).float())).cuda()
+    src[::7] = -0.0
+    order = torch.randperm(P, generator=g).to(torch.int32).cuda()
+    tail = torch.zeros(n - P, device="cuda")
+    row = lambda: torch.full((n + 64,), float("nan"), device="cuda")            # 64 sentinels past the row
+    bits = lambda t: t.view(torch.int32)
+    for what, s, o, fill, want in (("src[order[p]]", src, order, 0.0, src[order.long()]), ("src[p]", src, None, 5.0, src),
+                                   ("fill", None, None, 1.0, torch.ones(P, device="cuda")),
+                                   ("fill, order without src", None, order, -2.5, torch.full((P,), -2.5, device="cuda"))):
+        dst = row()
+        assert lib.nsa_emit_row(dst.data_ptr(), None if s is None else s.data_ptr(), None if o is None else o.data_ptr(), P, n, fill, st()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(bits(dst[:n]), bits(torch.cat((want, tail)))), f"nsa_emit_row P = {P}: {what}"
+        assert bool(torch.isnan(dst[n:]).all()), f"nsa_emit_row P = {P}: {what} writes past n"
+    dst = row()
+    assert lib.nsa_emit_row(None, src.data_ptr(), None, P, n, 0.0, st()) != 0, "a NULL destination is accepted"
+    assert lib.nsa_emit_row(dst.data_ptr(), src.data_ptr(), None, P, P - 1, 0.0, st()) != 0, "P > n is accepted"
+    assert lib.nsa_emit_row(dst.data_ptr(), src.data_ptr(), None, 0, 0, 0.0, st()) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(dst).all()), "a refused or empty call wrote to the destination"
 
 
 # ------------------------------------------------------------------------------------------------------------------ properties

@@ -9,6 +9,12 @@
 (3) The margin threshold is fixed against the reference alone: bf16_gate.THRESHOLD is the smallest value of bf16_gate.LADDER at
     which both correct emulations stay within the gate for every family while every family keeps >= 10 % of its judged points and
     >= 400 points.
+(4) The same on the PER-POINT WEIGHT GRADIENTS (tests/bf16_cases.py::weight_grad_cases: what the emission rows of the _params twins
+    encode), judged with both fp32 summation orders as yardsticks (bf16_gate.gate, ``second``): a third correct emulation passes in
+    every layer of every family of both SDF networks and the colour network; under ONE yardstick the correct emulations refuse each
+    other (coarse, g_sdf alone: dW0); "truncated weights", "unrounded cotangents" and "rounded emission rows" (g (x) x formed from
+    the rounded vectors: the oracle's _LinQ, which the MAP bodies by design do not do) are refused in at least one layer of every
+    family they reach.
 
 MEASURED (this module; full_vis_eval with every weight_v perturbed by 0.05; margin in units of the operand's measured fp32 noise,
 ref64.Margin).  Both correct emulations within the gate on every family: only at THRESHOLD = 3 of the ladder 1e-4, 3e-4, ..., 300 --
@@ -171,3 +177,77 @@ def test_threshold_is_the_smallest_of_the_ladder_that_holds(judged, capsys):
     assert G.THRESHOLD == min(t for t in G.LADDER if holds[t]), holds
     for name, n in shares.items():
         assert n >= G.MIN_KEPT and n >= G.MIN_SHARE * C.N, (name, n)
+
+
+# ------------------------------------------------------------------------------------------------------------------ (4) weight gradients
+WEIGHT_GRAD_FAULTS = ("truncated weights", "unrounded cotangents", "rounded emission rows")
+
+
+@pytest.fixture(scope="module")
+def weight_grad_cases(model):
+    params, cfg = model
+    return C.weight_grad_cases(params, cfg)
+
+
+def _layers_ok(r, got, norm, keep, second, what=None):
+    """layer -> does ``got`` pass the backward gate there? (second: both summation orders as yardsticks)"""
+    return {k: G.gate(f"{what}: {k}", got[k], r.b64[k], r.y32[k], r.f64[k], norm, r.margin, True, keep, quiet=what is None,
+                      second=r.perm[k] if second else None) for k in r.b64 if k.startswith("[dW")}
+
+
+@pytest.mark.parametrize("network", ["coarse", "fine", "colour"])
+def test_weight_gradient_gate_passes_the_correct_emulations_and_refuses_the_wrong_ones(weight_grad_cases, network, capsys):
+    """MEASURED (N = 4 123, both yardsticks): the third emulation passes everywhere; "truncated weights" is refused in every layer of
+    every family; "rounded emission rows" in dW0 of every family; "unrounded cotangents" wherever a feature or gradient cotangent is
+    present, in the fine network also with g_sdf alone (dW0, dW1) -- in the coarse network with g_sdf alone it does not reach the
+    weight gradients at all (the only derivative GEMM there is the one towards x), and the test says so instead of demanding it.
+    Under one yardstick the permuted emulation is refused on dW0 of coarse "g_sdf alone" (the reason for ``second``)."""
+    single_refusals = []
+    with capsys.disabled():
+        print()
+        for name, (call, norm, _backward, colour) in weight_grad_cases.items():
+            if not name.startswith(f"weight gradients {network}"):
+                continue
+            r = C.refs(call)
+            keep = C.kink_keep(r) if colour else None
+            kept = r.margin.kept(G.THRESHOLD) & (norm != 0) & (keep if keep is not None else True)
+            assert int(kept.sum()) >= G.MIN_KEPT, (name, int(kept.sum()))
+            third = C.emulate(call, order=("permuted", 1))
+            for label, got in (("natural", r.y32), ("permuted", r.perm), ("permuted, other order", third)):
+                ok = _layers_ok(r, got, norm, keep, True, f"[{label}] {name}" if got is third else None)
+                assert all(ok.values()), f"the gate refuses the correct emulation '{label}' on {name}: {ok}"
+                if not all(_layers_ok(r, got, norm, keep, False).values()):
+                    single_refusals.append((label, name))
+            for k in r.b64:                                  # the value path as a forward quantity
+                if k.startswith("H"):
+                    assert G.gate(f"{name}: {k}", third[k], r.b64[k], r.y32[k], r.f64[k], G.fwd_norm(r.b64[k]), r.margin, False, keep, quiet=True)
+            for fault in WEIGHT_GRAD_FAULTS:
+                wrong = C.emulate(call, fault=fault)
+                reached = any(not torch.equal(wrong[k], r.y32[k]) for k in wrong if k.startswith("[dW"))
+                ok = _layers_ok(r, wrong, norm, keep, True)
+                print(f"  [{fault}] {name}: " + ("refused in " + ", ".join(k for k, v in ok.items() if not v) if not all(ok.values())
+                                                   else "does not reach the weight gradients" if not reached else "ACCEPTED"))
+                assert not reached or not all(ok.values()), f"the gate accepts '{fault}' on {name}"
+                if fault != "unrounded cotangents":
+                    assert reached, f"'{fault}' does not reach {name}"
+            del r, third
+        print(f"  under ONE yardstick a correct emulation is refused on: {single_refusals}")
+    if network == "coarse":
+        assert ("permuted", "weight gradients coarse: g_sdf alone x c_p") in single_refusals, "one yardstick suffices: drop bf16_gate.gate's second"
+
+
+def test_second_yardstick_only_ever_loosens_towards_the_other_correct_order():
+    """bf16_gate.gate(second=...): without it nothing changes; with it the rms and the bound are the larger of the two orders'"""
+    g = torch.Generator().manual_seed(5)
+    P = 2000
+    b64 = torch.randn(P, 8, generator=g, dtype=torch.float64)
+    y1, y2 = b64 + 1e-6 * torch.randn(P, 8, generator=g, dtype=torch.float64), b64 + 2e-6 * torch.randn(P, 8, generator=g, dtype=torch.float64)
+    margin = type("M", (), {"kept": lambda self, t: torch.ones(P, dtype=torch.bool)})()
+    norm = torch.ones(P, dtype=torch.float64)
+    args = lambda got, y: (got, b64, y, b64 + 1e-3, norm, margin, True)
+    G.REPORT.clear()
+    assert not G.gate("y2 against y1", *args(y2, y1), quiet=True)
+    assert G.gate("y2 against y1 and y2", *args(y2, y1), quiet=True, second=y2) and G.gate("y1 against both", *args(y1, y2), quiet=True, second=y1)
+    one, two = G.REPORT[0], G.REPORT[1]
+    assert two["rms_y"] > one["rms_y"] and two["max_y"] > one["max_y"] and abs(two["rms_y"] / one["rms_y"] - 2) < 0.2
+    assert not G.gate("3 x y2 against both", *args(b64 + 3.2 * (y2 - b64), y1), quiet=True, second=y2)
