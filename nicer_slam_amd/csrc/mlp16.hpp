@@ -301,6 +301,57 @@ __device__ __forceinline__ void gemm16_lds_part(const float* lds_block, int lane
     __builtin_amdgcn_sched_barrier(0);   // keep later layers' LDS reads from being hoisted above this GEMM
 }
 
+// The same for TWO operands of one staged part: acc0 += A b0 and acc1 += A b1 from ONE stream of fragment reads (every a[t][pc] is
+// read once and multiplied with both operands' pieces; two independent accumulator sets on the matrix pipe).  Each operand keeps
+// what gemm16_lds_part gives it alone -- its own point scale (and with it the all-zero rule of point_scale_of), its own hint, its
+// own PRE / POST accumulator scaling, the same products in the same order per accumulator -- so each result is bit for bit that of
+// its own single-operand GEMM.
+template <int KG, int MT, int G0, int NG, bool PRE = true, bool POST = true>
+__device__ __forceinline__ void gemm16_lds_part2(const float* lds_block, int lane, const float (&b0)[8 * KG], f32x4v (&acc0)[MT],
+                                                 const float (&b1)[8 * KG], f32x4v (&acc1)[MT], const float* hint0 = nullptr,
+                                                 const float* hint1 = nullptr) {
+    const lds_u4* w4 = (const lds_u4*)lds_block + lane;
+    constexpr int TC = MT <= 4 ? MT : (MT % 3 == 0 ? 3 : 4);
+    static_assert(MT % TC == 0, "tile chunking");
+    PointScale ps0{1.0f, 0}, ps1{1.0f, 0};
+    if constexpr (kPieces == 2) {
+        ps0 = point_scale16<8 * KG>(b0, hint0);
+        ps1 = point_scale16<8 * KG>(b1, hint1);
+        if constexpr (PRE) {
+            scale_acc16<MT, false>(acc0, ps0.kpre);
+            scale_acc16<MT, false>(acc1, ps1.kpre);
+        }
+    }
+#pragma unroll
+    for (int gl = 0; gl < NG; ++gl) {
+        const int g = G0 + gl;
+        float x0[8], x1[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            x0[e] = kPieces == 2 ? b0[8 * g + e] * ps0.s : b0[8 * g + e];
+            x1[e] = kPieces == 2 ? b1[8 * g + e] * ps1.s : b1[8 * g + e];
+        }
+        B16 bp0, bp1;
+        split_b16(x0, bp0);
+        split_b16(x1, bp1);
+#pragma unroll
+        for (int c = 0; c < MT / TC; ++c) {
+            u32x4 a[TC][3];
+#pragma unroll
+            for (int t = 0; t < TC; ++t)
+#pragma unroll
+                for (int pc = 0; pc < kPieces; ++pc) a[t][pc] = w4[(((c * TC + t) * NG + gl) * kLdsPieces + pc) * 64];
+            mma16_tiles<TC>(a, bp0, &acc0[c * TC]);
+            mma16_tiles<TC>(a, bp1, &acc1[c * TC]);
+        }
+    }
+    if constexpr (kPieces == 2 && POST) {
+        scale_acc16<MT, true>(acc0, -ps0.kpre);
+        scale_acc16<MT, true>(acc1, -ps1.kpre);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep later layers' LDS reads from being hoisted above this GEMM
+}
+
 template <class Seq, int NW, int BUF, int KG, int MT, int P0, int G0, int NG, bool PRE = true, bool POST = true>
 __device__ __forceinline__ void gemm16_staged_part(float* stage, const float* __restrict__ wp, int part, int lane,
                                                    const float (&b)[8 * KG], f32x4v (&acc)[MT], const float* __restrict__ wp1 = nullptr,
@@ -387,6 +438,47 @@ __device__ __forceinline__ void gemm16_staged(float* stage, const float* __restr
     gemm16_staged_part<Seq, NW, BUF, KG, MT, 0, 0, (KG < M ? KG : M), true, NP == 1>(stage, wp, p0, lane, b, acc, wp1, hint);
     if constexpr (NP > 1) gemm16_staged_part<Seq, NW, BUF, KG, MT, 1, M, (KG - M < M ? KG - M : M), false, NP == 2>(stage, wp, p0 + 1, lane, b, acc, wp1, hint);
     if constexpr (NP > 2) gemm16_staged_part<Seq, NW, BUF, KG, MT, 2, 2 * M, KG - 2 * M, false, true>(stage, wp, p0 + 2, lane, b, acc, wp1, hint);
+}
+
+// Two operands through logical GEMM `opi` (gemm16_lds_part2): every part is staged ONCE and waited for once.
+template <class Seq, int NW, int BUF, int KG, int MT, int G0, int NG, bool PRE, bool POST>
+__device__ __forceinline__ void gemm16_staged_part2(float* stage, const float* __restrict__ wp, int part, int lane,
+                                                    const float (&b0)[8 * KG], f32x4v (&acc0)[MT], const float (&b1)[8 * KG],
+                                                    f32x4v (&acc1)[MT], const float* __restrict__ wp1, const float* hint0,
+                                                    const float* hint1) {
+    stage_wait();
+    const StagePart nxt = part_at<Seq, BUF>(part + 1);
+    if (nxt.mt) stage_issue_part<NW>(wp, nxt, stage + ((part + 1) & 1) * BUF, wp1);
+    gemm16_lds_part2<KG, MT, G0, NG, PRE, POST>(stage + (part & 1) * BUF, lane, b0, acc0, b1, acc1, hint0, hint1);
+}
+
+template <class Seq, int NW, int BUF, int KG, int MT>
+__device__ __forceinline__ void gemm16_staged2(float* stage, const float* __restrict__ wp, int opi, int lane,
+                                               const float (&b0)[8 * KG], f32x4v (&acc0)[MT], const float (&b1)[8 * KG],
+                                               f32x4v (&acc1)[MT], const float* hint0 = nullptr, const float* hint1 = nullptr,
+                                               const float* __restrict__ wp1 = nullptr) {
+    if constexpr (seq_resident<Seq>::value) {
+        gemm16_lds_part2<KG, MT, 0, KG>(stage + res_off<Seq>(opi), lane, b0, acc0, b1, acc1, hint0, hint1);
+        return;
+    }
+    constexpr int M = max_groups<BUF>(MT);
+    constexpr int NP = (KG + M - 1) / M;
+    static_assert(NP <= 3, "a staged GEMM is split into at most three parts");
+    const int p0 = first_part<Seq, BUF>(opi);
+    float own0 = 0.0f, own1 = 0.0f;                  // several parts: each operand's maximum of this lane once, handed to every part
+    if constexpr (kPieces == 2 && NP > 1) {
+        if (!hint0) {
+            own0 = abs_max<8 * KG>(b0);
+            hint0 = &own0;
+        }
+        if (!hint1) {
+            own1 = abs_max<8 * KG>(b1);
+            hint1 = &own1;
+        }
+    }
+    gemm16_staged_part2<Seq, NW, BUF, KG, MT, 0, (KG < M ? KG : M), true, NP == 1>(stage, wp, p0, lane, b0, acc0, b1, acc1, wp1, hint0, hint1);
+    if constexpr (NP > 1) gemm16_staged_part2<Seq, NW, BUF, KG, MT, M, (KG - M < M ? KG - M : M), false, NP == 2>(stage, wp, p0 + 1, lane, b0, acc0, b1, acc1, wp1, hint0, hint1);
+    if constexpr (NP > 2) gemm16_staged_part2<Seq, NW, BUF, KG, MT, 2 * M, KG - 2 * M, false, true>(stage, wp, p0 + 2, lane, b0, acc0, b1, acc1, wp1, hint0, hint1);
 }
 
 // packed per-feature vector (activation layout [q*16 + s]) -> this lane's 16 values as 4 tiles x 4

@@ -7,6 +7,7 @@
 //                   MAP = true adds table gradients (run-merged atomics) and the emission rows of the weight gradients
 // Reference: ImplicitNetworkGrid.get_outputs/gradient (code/model/base_networks.py:195-221), ImplicitNetworkGrid_COMBINE (:7-47).
 #include <cstdlib>
+#include <type_traits>
 #include "sdf_net4.hpp"
 
 namespace nsa {
@@ -94,6 +95,7 @@ struct Emitter4 {
 // GEMM sequences (block-cooperative weight staging):
 //   forward : W0, W_1..W_{NH-1}, WFEAT | reverse pass W_{NH-1}^T..W_1^T, W0^T                                   2 NH + 1
 //   backward: W0, W_k | W_k^T.., W0^T | tangent W0, W_k | WFEAT^T | reverse sweep W_k^T.., W0^T                  4 NH + 1
+//             (MAP kernels, bf16-operand build; the fp32 data path runs SdfOps4Data below: 2 NH + 1)
 template <int NH, bool BWD>
 struct SdfOps4 {
     using P = SdfPack4<NH>;
@@ -110,6 +112,31 @@ struct SdfOps4 {
     __host__ __device__ static constexpr int kg(int i) { return off(i) == P::kW0 ? QIN_G : 2; }
     __host__ __device__ static constexpr int n_parts() { return first_part<SdfOps4<NH, BWD>, BUF>(n); }
 };
+
+// The data-path backward (MAP == false, fp32 build) stages every block ONCE: the backward sequence above names its forward blocks
+// twice (forward, tangent sweep) and its reverse blocks twice (reverse pass, reverse sweep), and both pairs can walk their layers
+// in lock-step -- layer k of the tangent needs the forward's slope of layer k only; e_k of the reverse sweep needs dh_k, which
+// the reverse pass has at that very step -- with two operands per staged block (mlp16.hpp::gemm16_staged2):
+//   W0, W_1..W_{NH-1}  (h | tangent)   |   WFEAT^T   |   W_{NH-1}^T..W_1^T, W0^T  (da | ab)                       2 NH + 1
+// The MAP kernels keep SdfOps4<NH, true>: their emission rows are written in that order, and they are the bitwise oracle of this one
+// (tests/test_backward_paired_gpu.py).
+template <int NH>
+struct SdfOps4Data {
+    using P = SdfPack4<NH>;
+    using Old = SdfOps4<NH, true>;
+    static constexpr int NW = Old::NW;
+    static constexpr int BUF = Old::BUF;
+    static constexpr int n = 2 * NH + 1;
+    __host__ __device__ static constexpr int off(int i) { return i < NH ? Old::fwd(i) : i == NH ? P::kWFEATT : Old::rev(i - NH - 1); }
+    __host__ __device__ static constexpr int mt(int i) { return off(i) == P::kW0T ? 6 : 4; }
+    __host__ __device__ static constexpr int kg(int i) { return off(i) == P::kW0 ? QIN_G : 2; }
+    __host__ __device__ static constexpr int n_parts() { return first_part<SdfOps4Data<NH>, BUF>(n); }
+};
+// The bf16-operand build keeps the unpaired sequence on its data path too: its GEMMs are six times shorter and run out of a
+// resident image with no staging and no barrier, and the pairing has not been measured there.
+constexpr bool kPairedBwd4 = kPieces != 1;
+template <int NH, bool MAP>
+using SdfBwdSeq4 = std::conditional_t<MAP || !kPairedBwd4, SdfOps4<NH, true>, SdfOps4Data<NH>>;
 
 // `wp`: this network's packed block (per-feature vectors).  A sequence over TWO networks (SdfOpsPair) stages from `s0` / `s1`, the
 // blocks of its net 0 / net 1; a one-network sequence leaves them null and stages from `wp`.
@@ -351,7 +378,7 @@ __global__ __launch_bounds__(64 * NSA_NW4_PAIR, NSA_OCC4_FWD) void k_sdfnet4_fwd
 template <int L, int C, int NH, bool MAP>
 __global__ __launch_bounds__(64 * NSA_NW4_BWD, NSA_OCC4_BWD) void k_sdfnet4_bwd(SdfNet4Args a, GridGeom16 geom) {
     using P = SdfPack4<NH>;
-    using Seq = SdfOps4<NH, true>;
+    using Seq = SdfBwdSeq4<NH, MAP>;
     using E = SE4<NH>;
     TS_BEGIN
     __shared__ __attribute__((aligned(16))) float stage[2 * Seq::BUF];
@@ -402,7 +429,7 @@ template <int L, int C, int NH>
 __global__ __launch_bounds__(64 * NSA_NW4_BWD, NSA_OCC4_BWD) void k_sdfnet4_bwd_res(SdfNet4Args a, GridGeom16 geom) {
     constexpr bool MAP = false;
     using P = SdfPack4<NH>;
-    using Seq = ResidentSeq<SdfOps4<NH, true>>;
+    using Seq = ResidentSeq<SdfBwdSeq4<NH, MAP>>;
     using E = SE4<NH>;
     __shared__ __attribute__((aligned(16))) float stage[res_off<Seq>(Seq::n)];
     __shared__ LevelGeom s_geom[16];

@@ -223,22 +223,35 @@ __device__ __forceinline__ void slots_to_x4(const float (&x)[3], float divide_fa
 // Tangent of the first-layer input along n (a cotangent of grad sdf): tin[slot] = sum_d (d in[slot]/d x_d) n_d -- the grid
 // Hessian term is NOT part of it (hashgrid.py:134) -- and the positional-encoding second-derivative term
 //   xbar_d += n_d * sum_k -(4^k) (sin * dl_sin + cos * dl_cos).
-__device__ __forceinline__ void pe_tangent4(int q, const float (&in)[QIN], const float (&n)[3], const float (&dl)[QIN],
-                                            float (&tin)[QIN], float (&xbar)[3]) {
-    xbar[0] = xbar[1] = xbar[2] = 0.0f;
+// (two halves: the tangent needs in and n only; the xbar term needs dl, which the data-path backward has much later)
+__device__ __forceinline__ void pe_tangent_tin4(int q, const float (&in)[QIN], const float (&n)[3], float (&tin)[QIN]) {
 #pragma unroll
     for (int m = 0; m < 5; ++m) {
         const PairSel ps = pe_pair(m, q, n);                 // xa = the cotangent component n_d of this pair's coordinate
         const float s = m == 4 && q >= 2 ? 0.0f : in[2 * m], c = m == 4 && q >= 2 ? 0.0f : in[2 * m + 1];   // (q == 3 keeps x there)
         tin[2 * m] = ps.sc * c * ps.xa;
         tin[2 * m + 1] = -ps.sc * s * ps.xa;
-        pe_add(m, q, xbar, -ps.sc * ps.sc * (s * dl[2 * m] + c * dl[2 * m + 1]) * ps.xa);
     }
     tin[8] = q == 3 ? n[0] : tin[8];
     tin[9] = q == 3 ? n[1] : tin[9];
     tin[10] = q == 3 ? n[2] : 0.0f;
 #pragma unroll
     for (int s = 11; s < 16; ++s) tin[s] = 0.0f;
+}
+__device__ __forceinline__ void pe_tangent_xbar4(int q, const float (&in)[QIN], const float (&n)[3], const float (&dl)[QIN],
+                                                 float (&xbar)[3]) {
+    xbar[0] = xbar[1] = xbar[2] = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const PairSel ps = pe_pair(m, q, n);
+        const float s = m == 4 && q >= 2 ? 0.0f : in[2 * m], c = m == 4 && q >= 2 ? 0.0f : in[2 * m + 1];
+        pe_add(m, q, xbar, -ps.sc * ps.sc * (s * dl[2 * m] + c * dl[2 * m + 1]) * ps.xa);
+    }
+}
+__device__ __forceinline__ void pe_tangent4(int q, const float (&in)[QIN], const float (&n)[3], const float (&dl)[QIN],
+                                            float (&tin)[QIN], float (&xbar)[3]) {
+    pe_tangent_tin4(q, in, n, tin);
+    pe_tangent_xbar4(q, in, n, dl, xbar);
 }
 
 template <int L, int C>
@@ -305,11 +318,11 @@ __device__ __forceinline__ void slots_to_x_jac4(float divide_factor, const float
         }
 }
 
+// (tangent_tin_from_jac4: the tangent alone, for a caller that has no dl yet and takes pe_tangent_xbar4 later)
 template <int L, int C>
-__device__ __forceinline__ void tangent_from_jac4(float divide_factor, const float* jstore, int q, const float (&in)[QIN],
-                                                  const float (&n)[3], const float (&dl)[QIN], float (&tin)[QIN],
-                                                  float (&xbar)[3]) {
-    pe_tangent4(q, in, n, dl, tin, xbar);
+__device__ __forceinline__ void tangent_tin_from_jac4(float divide_factor, const float* jstore, int q, const float (&in)[QIN],
+                                                      const float (&n)[3], float (&tin)[QIN]) {
+    pe_tangent_tin4(q, in, n, tin);
     const float chain = 1.0f / (2.0f * divide_factor);
 #pragma unroll
     for (int jl = 0; jl < 8 / C; ++jl)
@@ -320,6 +333,13 @@ __device__ __forceinline__ void tangent_from_jac4(float divide_factor, const flo
             for (int gd = 0; gd < 3; ++gd) acc = fmaf(n[gd] * chain, jstore[((jl * 3 + gd) * C + c) * 64], acc);
             tin[16 + jl * C + c] = acc;
         }
+}
+template <int L, int C>
+__device__ __forceinline__ void tangent_from_jac4(float divide_factor, const float* jstore, int q, const float (&in)[QIN],
+                                                  const float (&n)[3], const float (&dl)[QIN], float (&tin)[QIN],
+                                                  float (&xbar)[3]) {
+    tangent_tin_from_jac4<L, C>(divide_factor, jstore, q, in, n, tin);
+    pe_tangent_xbar4(q, in, n, dl, xbar);
 }
 
 // Table gradient of one SDF grid for THIS lane's levels (mapping): per corner row,
